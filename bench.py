@@ -10,6 +10,7 @@ time_dim 2 = 56 six-hour steps per member.  One "step" of this benchmark = ONE s
 one hipGraph launch.  Members are sharded across ranks, no collective (weak scaling).
 
     python bench.py --gpus N --steps K --warmup W        (N > 1: launched by torch.distributed.run, one rank per GPU)
+    --dump-outputs DIR   also writes what the last timed step returned as DIR/*.npy (dump_outputs: seeded sample, <= 64 MB)
 
 Prints ONE JSON line on rank 0.
   value      members x 56 x K x N / wall  [6-h forecast steps / s], state resident in HBM.
@@ -995,6 +996,40 @@ def _free_port():
     return port
 
 
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(series, directory, seed=0):
+    """--dump-outputs: the series the timed rollout returned in its last step, as float32 DIR/<name>.npy, at most 64 MB in all.
+    A series within the budget is written whole (series.npy); a larger one as a fixed, seeded sample: the whole series of
+    the members that fit in 3/4 of the budget (series_members.npy, members in ascending order) and elements drawn over the whole
+    flattened series (series_sample.npy, ascending flat indices).  The selection depends only on the series' shape and `seed`,
+    so two builds run with the same arguments write comparable files.  Returns the record of what was written."""
+    os.makedirs(directory, exist_ok=True)
+    g = torch.Generator().manual_seed(seed)
+    n, numel = int(series.shape[1]), series.numel()
+    arrays, rec = {}, {'dir': os.path.abspath(directory), 'seed': seed, 'series_shape': list(series.shape)}
+    if numel * 4 <= DUMP_BUDGET_BYTES:
+        arrays['series'] = series
+    else:
+        per_member = numel // n * 4
+        k = min(n, DUMP_BUDGET_BYTES * 3 // 4 // per_member)
+        if k:
+            members = torch.randperm(n, generator=g)[:k].sort().values
+            arrays['series_members'] = series[:, members.to(series.device)]
+            rec['members'] = members.tolist()
+        count = min(numel, (DUMP_BUDGET_BYTES - k * per_member) // 4 - 1024)
+        flat = torch.randint(numel, (count,), generator=g).sort().values
+        arrays['series_sample'] = series.reshape(-1)[flat.to(series.device)]
+        rec['sample'] = '%d elements of the flattened series, torch.randint(seed %d) after the member draw' % (count, seed)
+    rec['files'] = {}
+    for name, t in arrays.items():
+        a = t.detach().to(torch.float32).cpu().numpy()
+        np.save(os.path.join(directory, name + '.npy'), a)
+        rec['files'][name + '.npy'] = list(a.shape)
+    return rec
+
+
 def launch_ranks(n, argv, timeout_s):
     """One process per GPU (reference: keras.utils.multi_gpu_model replicates inside one process,
     DLWP/model/models.py:104-109).  The parent only starts the ranks with the torchrun environment (RANK / LOCAL_RANK /
@@ -1051,6 +1086,9 @@ def main():
     ap.add_argument('--activation-dtype', default='float32', choices=['float32', 'bfloat16'],
                     help="storage of the tensors between the layers (BASELINE config 4 uses bfloat16; the headline "
                          "config 2 is float32)")
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the series the last one returned (rank 0: its members) as float32 '
+                         'DIR/<name>.npy, at most 64 MB in all (a fixed, seeded sample of a larger series)')
     a = ap.parse_args()
     grid = tuple(int(v) for v in a.grid.split('x'))
 
@@ -1109,6 +1147,7 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
     finite = bool(torch.isfinite(series[-1]).all().item())
+    dumped = dump_outputs(series, a.dump_outputs) if a.dump_outputs and rank == 0 else None
 
     six_hour_steps = m_total * a.forwards * 2 * a.steps
     value = six_hour_steps / dt
@@ -1133,6 +1172,8 @@ def main():
         'conv_mflop_per_forward_per_member': flops_fwd / 1e6,
         'finite': finite,
     }
+    if dumped:
+        out['dump_outputs'] = dumped
     state = {'printed': False}
     lock = threading.Lock()
 

@@ -69,9 +69,14 @@ def _worker(rank, world, port, n_global, ret):
 
 
 @pytest.mark.parametrize('n_global', [8, 7])
-def test_gloo_world2_dp_step_equals_single_process_step(n_global):
+def test_gloo_world2_dp_step_equals_single_process_step(n_global, monkeypatch):
     world = 2
     port = _free_port()
+    # the workers run the CPU path on a GPU machine too: no device visible to them (else rank 1 would bind a cuda:1 a one-GPU
+    # machine lacks and rank 0 wait for it); should the runtime still show one, both ranks share it as the gloo tests do
+    for k in ('HIP_VISIBLE_DEVICES', 'CUDA_VISIBLE_DEVICES'):
+        monkeypatch.setenv(k, '-1')
+    monkeypatch.setenv('DLWP_SHARE_GPUS', '1')
     ctx = mp.get_context('spawn')
     with ctx.Manager() as mgr:
         ret = mgr.dict()
