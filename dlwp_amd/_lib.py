@@ -28,6 +28,7 @@ ACT_LINEAR, ACT_TANH, ACT_RELU = 0, 1, 2
 SRC_DIRECT, SRC_UPSAMPLE2, SRC_MAXPOOL2 = 0, 1, 2
 OP_CONV2D, OP_PAD2D, OP_MAXPOOL2, OP_UPSAMPLE2, OP_COPYCH, OP_LSTM_GATES, OP_PHASE_WEIGHTS, OP_DEPTH2SPACE = 0, 1, 2, 3, 4, 5, 6, 7
 OP_ROWCONV2D = 8
+OP_BATCHNORM = 9
 BUF_NONE = -1000
 STEP_LANES, STEP_GRAPH, STEP_GRAPH_BRANCHES, STEP_LANES_RECORDED = 0, 1, 2, 3
 
@@ -77,6 +78,12 @@ class Feedback(ctypes.Structure):
     _fields_ = [('rows', ctypes.c_int), ('state_c', ctypes.c_int), ('out_c', ctypes.c_int), ('hw', ctypes.c_int),
                 ('shift', ctypes.c_int), ('tail', ctypes.c_int), ('sol_planes', ctypes.c_int),
                 ('src', ctypes.c_int * FB_MAX_CHANNELS), ('sol', ctypes.c_int * FB_MAX_CHANNELS)]
+
+
+class BatchNorm(ctypes.Structure):
+    """dlwp_batchnorm (include/dlwp_hip.h): shape and hyper-parameters of one BatchNormalization launch"""
+    _fields_ = [('n', ctypes.c_int), ('c', ctypes.c_int), ('hw', ctypes.c_int), ('momentum', ctypes.c_float),
+                ('epsilon', ctypes.c_float)]
 
 
 class LaunchInfo(ctypes.Structure):
@@ -212,6 +219,10 @@ _sig('dlwp_convlstm_step_prepared_bytes', [_vp, Shape4, _P(Conv2d), Shape4, _P(C
 _sig('dlwp_convlstm_step_prepare', [_vp, _vp, _vp, _vp, Shape4, _P(Conv2d), Shape4, _P(Conv2d), _i, _vp])
 _sig('dlwp_convlstm_step_fwd', [_vp] * 10 + [Shape4, _P(Conv2d), Shape4, _P(Conv2d), _i, _vp])
 _sig('dlwp_convlstm_gates_bwd', [_vp] * 9 + [_i] * 8 + [_vp])
+_sig('dlwp_batchnorm_workspace', [BatchNorm], _sz)
+_sig('dlwp_batchnorm_fwd_train', [_vp] * 9 + [_vp, _sz, BatchNorm, _vp])
+_sig('dlwp_batchnorm_fwd_infer', [_vp] * 7 + [BatchNorm, _vp])
+_sig('dlwp_batchnorm_bwd', [_vp] * 9 + [_vp, _sz, BatchNorm, _vp])
 _sig('dlwp_copy_channels', [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp])
 _sig('dlwp_series_merge_time', [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp])
 _sig('dlwp_rollout_workspace_bytes', [_vp, _P(Op), _i, _i], _sz)

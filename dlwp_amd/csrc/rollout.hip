@@ -60,6 +60,12 @@ int enqueue_op(dlwp_handle_t h, const dlwp_op& op, const void* src, void* dst, c
     case DLWP_OP_PHASE_WEIGHTS:   // src / dst / b / aux[0] are parameter buffers (resolved by the caller)
       return dlwp_phase_weights(h, src, b, dst, aux ? aux[0] : nullptr, op.conv.kh, op.conv.kw, op.xs.c, op.conv.cout,
                                 op.conv.halo.top, op.conv.halo.left, dtype, (void*)s);
+    case DLWP_OP_BATCHNORM: {   // w / b = gamma / beta (nullable), aux = moving mean, moving variance; epsilon in op.aux[2]
+      float eps;
+      memcpy(&eps, &op.aux[2], sizeof(float));
+      const dlwp_batchnorm d{op.xs.n, op.xs.c, op.xs.h * op.xs.w, 0.f, eps};
+      return dlwp_batchnorm_fwd_infer(h, src, dst, w, b, aux[0], aux[1], d, (void*)s);
+    }
     case DLWP_OP_COPYCH:
       return dlwp_copy_channels(h, src, dst, op.xs.n, op.xs.c, op.xs.h * op.xs.w, op.conv.in_c_off,
                                 op.conv.in_c_total, op.conv.out_c_off, op.conv.out_c_total, dtype, (void*)s);
@@ -184,6 +190,10 @@ static int create_impl(dlwp_handle_t h, const dlwp_op* plan_in, int n_ops, void*
       DLWP_CHECK_ARG(op.src >= 0 && op.dst >= 0 && op.b >= -1 && op.b < n_buffers &&
                          (op.aux[0] == DLWP_BUF_NONE || (op.aux[0] >= 0 && op.aux[0] < n_buffers)),
                      "rollout op %d: phase-weights buffers out of range", i);
+    if (op.kind == DLWP_OP_BATCHNORM)
+      DLWP_CHECK_ARG(op.w >= -1 && op.w < n_buffers && op.b >= -1 && op.b < n_buffers && op.aux[0] >= 0 && op.aux[0] < n_buffers &&
+                         op.aux[1] >= 0 && op.aux[1] < n_buffers,
+                     "rollout op %d: batch-normalisation buffers out of range", i);
     if (op.kind == DLWP_OP_LSTM_GATES)
       for (int k = 0; k < 3; ++k)
         DLWP_CHECK_ARG((k < 2 && op.aux[k] == DLWP_BUF_NONE) || (op.aux[k] >= 0 && op.aux[k] < n_buffers),
@@ -264,9 +274,14 @@ static int create_impl(dlwp_handle_t h, const dlwp_op* plan_in, int n_ops, void*
         const dlwp_op& op = plan[i];
         if (op.kind == DLWP_OP_PHASE_WEIGHTS) continue;   // done once, at the head of the graph
         const bool weighted = op.kind == DLWP_OP_CONV2D || op.kind == DLWP_OP_ROWCONV2D;
-        const void* w = weighted ? buffers[op.w] : nullptr;
-        const void* b = (weighted && op.b >= 0) ? buffers[op.b] : nullptr;
+        const bool bn = op.kind == DLWP_OP_BATCHNORM;
+        const void* w = (weighted || (bn && op.w >= 0)) ? buffers[op.w] : nullptr;
+        const void* b = ((weighted || bn) && op.b >= 0) ? buffers[op.b] : nullptr;
         void* aux[3] = {nullptr, nullptr, nullptr};
+        if (bn) {                                          // (parameter buffers: the same for every member group)
+          aux[0] = buffers[op.aux[0]];
+          aux[1] = buffers[op.aux[1]];
+        }
         if (op.kind == DLWP_OP_LSTM_GATES)
           for (int k = 0; k < 3; ++k) aux[k] = op.aux[k] == DLWP_BUF_NONE ? nullptr : resolve(op.aux[k], t, g);
         if (op.kind == DLWP_OP_CONV2D && op.conv.lstm_f > 0)

@@ -8,6 +8,7 @@ the autoregressive rollout.  torch is plumbing only (device buffers, streams, H2
 """
 import ctypes
 import os
+import struct
 
 import numpy as np
 import torch
@@ -37,6 +38,7 @@ class Executor(object):
         self._bf16 = set(plan.bf16_buffers()) if activation_dtype == 'bfloat16' else set()
         self._phase = None       # derived (phase-summed) kernels of plan.phase_params: [(w2, b2 | None)]
         self._oct = self._octet_buffers() if self._bf16 and os.environ.get('DLWP_BF16_O8', '1') != '0' else set()
+        self._bn = {}            # (op index, batch size) -> the batch statistics a training forward keeps for the backward
 
     # -- buffers ----------------------------------------------------------------------------------------------------- #
     def scratch(self, n):
@@ -59,6 +61,20 @@ class Executor(object):
                             torch.empty(p['w2_shape'][3], dtype=torch.float32, device=self.device) if p['bias'] else None)
                            for p in self.plan.phase_params]
         return self._phase
+
+    def bn_state(self, k, n):
+        """Device memory of BatchNormalization op k in a training forward of n samples: the batch's mean and 1 / sqrt(var + eps)
+        (read by the backward) and the kernels' workspace.  Allocated once and never freed while the executor lives: a recorded
+        training step holds their addresses."""
+        from . import ops
+        st = self._bn.get((k, n))
+        if st is None:
+            c, h, w = self.plan.ops[k].xs
+            nb = ops.batchnorm_workspace_bytes(ops._lib.BatchNorm(int(n), int(c), int(h) * int(w), 0.0, 0.0))
+            st = self._bn[(k, n)] = {'mean': torch.zeros(c, dtype=torch.float32, device=self.device),
+                                     'invstd': torch.zeros(c, dtype=torch.float32, device=self.device),
+                                     'ws': torch.zeros(max(nb, 16), dtype=torch.uint8, device=self.device)}
+        return st
 
     def conv_weights(self, op):
         """(kernel, bias) tensors a conv launch multiplies with: the layer's, or the derived ones of a restated layer."""
@@ -197,12 +213,14 @@ class Executor(object):
             self._pool2 = found
         return self._pool2
 
-    def run(self, x, outs=None, prepared=None, skip_phasew=False, skip_ops=()):
+    def run(self, x, outs=None, prepared=None, skip_phasew=False, skip_ops=(), training=False):
         """x: device tensor (n, ...) matching the model input; returns the list of output tensors (stored layout).
         prepared: {op index: tensor of ops.conv2d_prepare} -- those convolutions do not transform their weights again;
         skip_phasew: the derived kernels (plan.phase_params) are already up to date (the training step builds them, and every
         prepared form, in front of the forward); skip_ops: op indices left out (the training step takes its loss on the phase
-        channels of a restated output layer: no depth-to-space pass, the output tensor stays unwritten)."""
+        channels of a restated output layer: no depth-to-space pass, the output tensor stays unwritten); training: the forward of a
+        training step -- BatchNormalization normalises with the batch's statistics and updates its moving statistics (else it
+        applies the moving statistics: predict, evaluate, validation)."""
         from . import ops
         n = x.shape[0]
         x = x.reshape((n,) + self.plan._in_store)
@@ -270,6 +288,15 @@ class Executor(object):
                 ops.upsample2(src, out=dst)
             elif op.kind == 'copy':
                 ops.copy_channels(src, dst, op.xs[0], op.in_c_off, op.out_c_off)
+            elif op.kind == 'bn':
+                lay = op.layer
+                if training:
+                    st = self.bn_state(k, n)
+                    ops.batchnorm_fwd_train(src, lay.gamma, lay.beta, lay.moving_mean, lay.moving_variance, st['mean'],
+                                            st['invstd'], st['ws'], lay.momentum, lay.epsilon, out=dst)
+                else:
+                    ops.batchnorm_fwd_infer(src, lay.gamma, lay.beta, lay.moving_mean, lay.moving_variance, lay.epsilon,
+                                            out=dst)
             elif op.kind == 'lstm':
                 zh, cp, co = op.aux
                 ops.convlstm_gates(src, res(zh) if zh is not None else None, res(cp) if cp is not None else None,
@@ -404,6 +431,14 @@ class Executor(object):
             table.append(lay.kernel)
             if lay.bias is not None:
                 table.append(lay.bias)
+        bidx = {}                                  # BatchNormalization: gamma, beta, moving mean, moving variance (index | -1)
+        for lay in self.plan.bn_layers:
+            ent = []
+            for t in (lay.gamma, lay.beta, lay.moving_mean, lay.moving_variance):
+                ent.append(len(table) if t is not None else -1)
+                if t is not None:
+                    table.append(t)
+            bidx[id(lay)] = ent
         pidx = []                                  # derived (phase-summed) kernels: (w2 index, b2 index | -1)
         for w2, b2 in self.phase_buffers():
             pidx.append((len(table), len(table) + 1 if b2 is not None else -1))
@@ -412,7 +447,8 @@ class Executor(object):
                 table.append(b2)
         kind = {'conv': _lib.OP_CONV2D, 'pad': _lib.OP_PAD2D, 'maxpool': _lib.OP_MAXPOOL2,
                 'upsample': _lib.OP_UPSAMPLE2, 'copy': _lib.OP_COPYCH, 'lstm': _lib.OP_LSTM_GATES,
-                'phasew': _lib.OP_PHASE_WEIGHTS, 'd2s': _lib.OP_DEPTH2SPACE, 'rowconv': _lib.OP_ROWCONV2D}
+                'phasew': _lib.OP_PHASE_WEIGHTS, 'd2s': _lib.OP_DEPTH2SPACE, 'rowconv': _lib.OP_ROWCONV2D,
+                'bn': _lib.OP_BATCHNORM}
         arr = (_lib.Op * len(self.plan.ops))()
         for k, (op, d) in enumerate(zip(self.plan.ops, self._descriptors())):
             o = arr[k]
@@ -447,6 +483,10 @@ class Executor(object):
                 o.xs = _lib.Shape4(n, op.xs[0], 1, 1)
             elif op.kind == 'd2s':
                 o.conv.out_c_off, o.conv.out_c_total = op.out_c_off, op.out_c_total
+            elif op.kind == 'bn':                      # inference form: the moving statistics, read at every launch
+                g_i, b_i, o.aux[0], o.aux[1] = bidx[id(op.layer)]
+                o.w, o.b = g_i, b_i
+                o.aux[2] = struct.unpack('<i', struct.pack('<f', op.layer.epsilon))[0]
             elif op.kind == 'maxpool':
                 o.aux[0] = _lib.BF16 if op.src in self._bf16 else _lib.F32
             elif op.kind == 'pad':
@@ -676,6 +716,9 @@ class Model(object):
         on float32 activations."""
         if dtype not in ('float32', 'bfloat16'):
             raise ValueError("activation dtype must be 'float32' or 'bfloat16'")
+        if dtype == 'bfloat16' and self.plan.bn_layers:
+            raise NotImplementedError('bfloat16 activation storage of a model with BatchNormalization layers is not implemented '
+                                      '(the channel-octet layout would need an index map of its own)')
         if dtype != self.activation_dtype:
             self.activation_dtype = dtype
             # interleaved phase stores (dlwp_conv2d.out_d2s) belong to the float32 Winograd kernels; with bfloat16 storage

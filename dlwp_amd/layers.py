@@ -359,6 +359,88 @@ class RowConnected2D(Layer):
         return cfg
 
 
+class BatchNormalization(Layer):
+    """keras.layers.BatchNormalization -- the `('BatchNormalization', None, {'axis': 1})` entry behind each Conv2D of the reference's
+    training scripts (examples/train.py:170-210, commented out there).  Keras 2 defaults.  On the HIP path: 4-D channels_first
+    inputs (axis 1 or -3), statistics over (N, H, W) per channel.  Weights in Keras order [gamma, beta, moving_mean,
+    moving_variance] (gamma without scale=False, beta without center=False); the moving statistics are NON-TRAINABLE: the
+    optimizer and the gradient exchange never see them, training updates them in place."""
+    non_trainable_names = ('moving_mean', 'moving_variance')
+
+    def __init__(self, axis=-1, momentum=0.99, epsilon=1e-3, center=True, scale=True, beta_initializer='zeros',
+                 gamma_initializer='ones', moving_mean_initializer='zeros', moving_variance_initializer='ones',
+                 beta_regularizer=None, gamma_regularizer=None, beta_constraint=None, gamma_constraint=None, renorm=False,
+                 renorm_clipping=None, renorm_momentum=0.99, fused=None, virtual_batch_size=None, adjustment=None, **kwargs):
+        if kwargs.get('trainable', True) is False:
+            raise NotImplementedError('BatchNormalization: trainable=False (frozen statistics) is not implemented')
+        super(BatchNormalization, self).__init__(**kwargs)
+        for nm, v in (('beta_regularizer', beta_regularizer), ('gamma_regularizer', gamma_regularizer),
+                      ('beta_constraint', beta_constraint), ('gamma_constraint', gamma_constraint)):
+            if v is not None:
+                raise NotImplementedError('BatchNormalization: %s is not implemented' % nm)
+        if renorm:
+            raise NotImplementedError('BatchNormalization: renorm is not implemented')
+        if virtual_batch_size is not None:
+            raise NotImplementedError('BatchNormalization: virtual_batch_size is not implemented')
+        if adjustment is not None:
+            raise NotImplementedError('BatchNormalization: adjustment is not implemented')
+        inits = {'beta_initializer': beta_initializer, 'gamma_initializer': gamma_initializer,
+                 'moving_mean_initializer': moving_mean_initializer,
+                 'moving_variance_initializer': moving_variance_initializer}
+        for nm, v in inits.items():
+            if v not in ('zeros', 'ones'):
+                raise NotImplementedError('BatchNormalization: %s=%r is not implemented (zeros, ones are)' % (nm, v))
+        self.axis = int(axis)
+        if self.axis not in (1, -3, -1):
+            raise NotImplementedError('BatchNormalization: axis=%r is not implemented (axis=1 on channels_first 4-D inputs)'
+                                      % (axis,))
+        self.momentum = float(momentum)
+        self.epsilon = float(epsilon)
+        self.center = bool(center)
+        self.scale = bool(scale)
+        self.initializers = inits
+        self.gamma = self.beta = self.moving_mean = self.moving_variance = None
+
+    def compute_output_shape(self, s):
+        if len(s) != 3:
+            raise NotImplementedError('BatchNormalization: only 4-D (N, C, H, W) inputs are implemented, got per-sample shape %r'
+                                      % (s,))
+        if self.axis == -1:
+            raise NotImplementedError("BatchNormalization: axis=-1 (Keras' default, channels_last) is not implemented; "
+                                      "pass axis=1 as the reference scripts do")
+        return tuple(s)
+
+    def build(self, input_shape, device, rng):
+        import torch
+        c = int(input_shape[0])
+        if self.built:
+            if self.moving_mean.shape[0] != c:
+                raise ValueError('%s was built for %d channels, now called with %d' % (self.name, self.moving_mean.shape[0], c))
+            return
+
+        def init(nm):
+            v = 1.0 if self.initializers[nm + '_initializer'] == 'ones' else 0.0
+            return torch.full((c,), v, dtype=torch.float32, device=device)
+        self._weights = []
+        if self.scale:
+            self.gamma = init('gamma')
+            self._weights.append(('gamma', self.gamma))
+        if self.center:
+            self.beta = init('beta')
+            self._weights.append(('beta', self.beta))
+        self.moving_mean = init('moving_mean')
+        self.moving_variance = init('moving_variance')
+        self._weights += [('moving_mean', self.moving_mean), ('moving_variance', self.moving_variance)]
+        self.built = True
+
+    def get_config(self):
+        cfg = super(BatchNormalization, self).get_config()
+        cfg.update({'axis': self.axis, 'momentum': self.momentum, 'epsilon': self.epsilon, 'center': self.center,
+                    'scale': self.scale})
+        cfg.update(self.initializers)
+        return cfg
+
+
 class _Pad3DBase(Layer):
     """ZeroPadding3D / PeriodicPadding3D argument handling (keras ZeroPadding3D forms).  On the HIP path these layers
     pad the recurrent (T, C, H, W) tensor in front of ConvLSTM2D (examples/train.py:144-147): channels_first makes T the

@@ -16,6 +16,17 @@ import numpy as np
 from .. import util
 
 
+def _refuse_parallel_batchnorm(model):
+    """keras.utils.multi_gpu_model gives every replica its own batch statistics and applies the moving-statistics update once
+    per replica; that is not implemented here (checked before any worker process is started)."""
+    from ..layers import BatchNormalization
+    bn = [lay.name for lay in model.layers if isinstance(lay, BatchNormalization)]
+    if bn:
+        raise NotImplementedError('build_model(gpus > 1) with BatchNormalization layers (%s) is not implemented: data-parallel '
+                                  'batch statistics (per replica in keras.utils.multi_gpu_model) need their own design'
+                                  % ', '.join(bn))
+
+
 class _Wrapper(object):
     """State and helpers shared by both wrappers."""
 
@@ -273,6 +284,8 @@ class DLWPNeuralNet(_Wrapper):
                 cls = util.get_from_class('dlwp_amd.custom', name)
             net.add(cls(*args, **kwargs))
         self.model = net
+        if gpus > 1:
+            _refuse_parallel_batchnorm(net)
         self.gpus = gpus
         if gpus > 1:
             from .. import parallel
@@ -457,6 +470,8 @@ class DLWPFunctional(_Wrapper):
     def build_model(self, model, gpus=1, **compile_kwargs):
         if type(gpus) is not int:
             raise TypeError("'gpus' argument must be an int")
+        if gpus > 1:
+            _refuse_parallel_batchnorm(model)
         self.base_model = model
         self.model = model
         self._n_steps = len(model.outputs)

@@ -957,3 +957,54 @@ def wgrad_config_forms():
 
 def force_wgrad_config(i):
     _lib.set_option(_lib.OPT_FORCE_WGRAD_CONFIG, int(i))
+
+
+# ------------------------------------------------------------------------------------------------------------------ #
+# BatchNormalization(axis=1) (csrc/batchnorm.hip)
+# ------------------------------------------------------------------------------------------------------------------ #
+
+def batchnorm_desc(x, momentum=0.99, epsilon=1e-3):
+    n, c = int(x.shape[0]), int(x.shape[1])
+    hw = 1
+    for d in x.shape[2:]:
+        hw *= int(d)
+    return _lib.BatchNorm(n, c, hw, float(momentum), float(epsilon))
+
+
+def batchnorm_workspace_bytes(d):
+    return int(_lib.lib.dlwp_batchnorm_workspace(d))
+
+
+def batchnorm_fwd_train(x, gamma, beta, moving_mean, moving_var, save_mean, save_invstd, ws, momentum=0.99, epsilon=1e-3,
+                        out=None):
+    """Training forward with the batch's statistics; updates moving_mean / moving_var in place and keeps the batch's mean and
+    1 / sqrt(var + eps) in save_mean / save_invstd for batchnorm_bwd.  ws: a uint8 device tensor of batchnorm_workspace_bytes."""
+    _check_f32(x, gamma, beta, moving_mean, moving_var, save_mean, save_invstd, out)
+    y = out if out is not None else torch.empty_like(x)
+    d = batchnorm_desc(x, momentum, epsilon)
+    _lib.check(_lib.lib.dlwp_batchnorm_fwd_train(_lib.handle(_dev(x)), _ptr(x), _ptr(y), _ptr(gamma), _ptr(beta),
+                                                 _ptr(moving_mean), _ptr(moving_var), _ptr(save_mean), _ptr(save_invstd),
+                                                 _ptr(ws), ws.numel() * ws.element_size(), d, _stream(x)))
+    return y
+
+
+def batchnorm_fwd_infer(x, gamma, beta, moving_mean, moving_var, epsilon=1e-3, out=None):
+    """Inference: the same affine map with the moving statistics."""
+    _check_f32(x, gamma, beta, moving_mean, moving_var, out)
+    y = out if out is not None else torch.empty_like(x)
+    d = batchnorm_desc(x, 0.0, epsilon)
+    _lib.check(_lib.lib.dlwp_batchnorm_fwd_infer(_lib.handle(_dev(x)), _ptr(x), _ptr(y), _ptr(gamma), _ptr(beta),
+                                                 _ptr(moving_mean), _ptr(moving_var), d, _stream(x)))
+    return y
+
+
+def batchnorm_bwd(x, dy, gamma, save_mean, save_invstd, ws, dgamma=None, dbeta=None, dx=None, want_dx=True):
+    """dx (None when want_dx is False), writing dgamma / dbeta (nullable) -- the backward of batchnorm_fwd_train."""
+    _check_f32(x, dy, gamma, save_mean, save_invstd, dgamma, dbeta, dx)
+    if want_dx and dx is None:
+        dx = torch.empty_like(x)
+    d = batchnorm_desc(x)
+    _lib.check(_lib.lib.dlwp_batchnorm_bwd(_lib.handle(_dev(x)), _ptr(x), _ptr(dy), _ptr(dx if want_dx else None), _ptr(gamma),
+                                           _ptr(save_mean), _ptr(save_invstd), _ptr(dgamma), _ptr(dbeta), _ptr(ws),
+                                           ws.numel() * ws.element_size(), d, _stream(x)))
+    return dx if want_dx else None

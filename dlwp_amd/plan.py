@@ -65,7 +65,7 @@ class View(object):
 
 
 class PlanOp(object):
-    """One launch.  kind in {'conv','rowconv','pad','maxpool','upsample','copy','lstm','phasew','d2s'}."""
+    """One launch.  kind in {'conv','rowconv','pad','maxpool','upsample','copy','lstm','phasew','d2s','bn'}."""
 
     def __init__(self, kind, src, dst, xs, **kw):
         self.kind, self.src, self.dst = kind, src, dst
@@ -130,6 +130,7 @@ class Plan(object):
         self.output_store = []   # per-sample stored (c, h, w) of each output slot
         self.conv_layers = []    # unique Conv2D layers in first-use order
         self.phase_params = []   # derived (phase-summed) kernels: dicts layer, w2_shape, b2 (bool), pad_top, pad_left
+        self.bn_layers = []      # BatchNormalization layers in plan order (one 'bn' op each)
 
     def new_buffer(self, c, h, w):
         self.buffers.append((int(c), int(h), int(w)))
@@ -706,6 +707,26 @@ def build_plan(inputs, outputs, inference=False, fuse_d2s=True, fuse_lstm=False,
                         act=ACT[lay.activation], in_c_off=v.c_off, in_c_total=v.c_total, out_c_off=0,
                         out_c_total=lay.filters, out_shape=(lay.filters, ho, wo)))
             views[t.uid] = View(dst, 0, lay.filters, lay.filters, ho, wo)
+        elif isinstance(lay, L.BatchNormalization):
+            # keras BatchNormalization(axis=1) (csrc/batchnorm.hip): its input is materialised as a whole buffer (the statistics
+            # pass reads it, and the training plan keeps it for the backward); its output is a new buffer, so nothing lazy and no
+            # epilogue of the convolution in front (pooled store, pooled weight gradient) carries a value across it
+            if lay in plan.bn_layers:
+                raise NotImplementedError('%s: a BatchNormalization layer applied more than once is not implemented' % lay.name)
+            v = ins[0]
+            if v.shape is not None and len(v.shape) != 3:
+                raise NotImplementedError('%s on a non-3D tensor %r' % (lay.name, v.shape))
+            v = materialize(v)
+            if not v.full:
+                v = materialize(v, dst=plan.new_buffer(*v.logical))
+            if outs:
+                dst = OUT(outs[0])
+                plan.output_store[outs[0]] = (v.c, v.h, v.w)
+            else:
+                dst = plan.new_buffer(v.c, v.h, v.w)
+            plan.bn_layers.append(lay)
+            emit(PlanOp('bn', v.buf, dst, (v.c, v.h, v.w), layer=lay, out_c_total=v.c, out_shape=(v.c, v.h, v.w)))
+            views[t.uid] = View(dst, 0, v.c, v.c, v.h, v.w)
         else:
             raise NotImplementedError('layer %s (%s) has no HIP lowering' % (lay.name, type(lay).__name__))
 

@@ -45,6 +45,8 @@ def _layer_config(lay):
                    data_format=lay.data_format, activation=lay.activation, use_bias=lay.use_bias)
         if isinstance(lay.kernel_regularizer, L1L2):
             cfg['kernel_regularizer'] = {'l2': lay.kernel_regularizer.l2}
+    elif isinstance(lay, L.BatchNormalization):
+        cfg.update(axis=lay.axis, momentum=lay.momentum, epsilon=lay.epsilon, center=lay.center, scale=lay.scale)
     elif isinstance(lay, (L.MaxPooling2D, L.UpSampling2D)):
         cfg.update(data_format=lay.data_format)
     elif isinstance(lay, L.Reshape):
@@ -153,6 +155,7 @@ def save_model_file(model, path, format=None):
 
 _GLOROT = {'class_name': 'VarianceScaling', 'config': {'scale': 1.0, 'mode': 'fan_avg', 'distribution': 'uniform', 'seed': None}}
 _ZEROS = {'class_name': 'Zeros', 'config': {}}
+_ONES = {'class_name': 'Ones', 'config': {}}
 _ORTHO = {'class_name': 'Orthogonal', 'config': {'gain': 1.0, 'seed': None}}
 
 
@@ -189,6 +192,11 @@ def _keras_layer_spec(lay):
         c.update(filters=lay.filters, kernel_size=list(lay.kernel_size), strides=list(lay.strides), padding=lay.padding,
                  data_format=lay.data_format, activation=lay.activation or 'linear', use_bias=lay.use_bias,
                  kernel_initializer=_GLOROT, bias_initializer=_ZEROS, kernel_regularizer=reg(lay.kernel_regularizer), **tail)
+    elif isinstance(lay, L.BatchNormalization):
+        init = {'zeros': _ZEROS, 'ones': _ONES}
+        c.update(axis=lay.axis, momentum=lay.momentum, epsilon=lay.epsilon, center=lay.center, scale=lay.scale,
+                 **{k: init[v] for k, v in lay.initializers.items()})
+        c.update(beta_regularizer=None, gamma_regularizer=None, beta_constraint=None, gamma_constraint=None)
     elif isinstance(lay, L.MaxPooling2D):
         c.update(pool_size=[2, 2], padding='valid', strides=[2, 2], data_format=lay.data_format)
     elif isinstance(lay, L.UpSampling2D):

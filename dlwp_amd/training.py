@@ -88,8 +88,9 @@ _METRIC_NAMES = {'mae': 'mean_absolute_error', 'mean_absolute_error': 'mean_abso
 # ------------------------------------------------------------------------------------------------------------------ #
 
 def flatten_parameters(model):
-    """Re-home every layer weight as a view into one contiguous fp32 buffer (values preserved).  Returns the buffer and
-    [(layer, name, offset, numel, shape)]."""
+    """Re-home every TRAINABLE layer weight as a view into one contiguous fp32 buffer (values preserved).  Returns the buffer
+    and [(layer, name, offset, numel, shape)].  Non-trainable weights (the moving statistics of BatchNormalization,
+    layer.non_trainable_names) stay where they are: Adam never updates them and the gradient exchange never carries them."""
     entries, total = [], 0
     seen = set()
     for lay in model.layers:
@@ -97,6 +98,8 @@ def flatten_parameters(model):
             continue
         seen.add(id(lay))
         for name, w in lay._weights:
+            if name in getattr(lay, 'non_trainable_names', ()):
+                continue
             entries.append((lay, name, total, w.numel(), tuple(w.shape)))
             total += w.numel()
     flat = torch.empty(max(total, 1), dtype=torch.float32, device=model.device)
@@ -194,6 +197,9 @@ class Trainer(object):
         self._loader_threads = 0      # > 0 while fit_generator feeds through a DeviceLoader (see _graph_ok)
         self._foreign = False         # set where a step launches through torch instead of the library (see _record_step)
         self._no_tape = set()         # step shapes whose recording was refused
+        # the moving statistics a training forward updates in place (BatchNormalization): part of the state a recorded step is
+        # validated on (see _validate_step)
+        self._bn_stats = [t for lay in self.plan.bn_layers for t in (lay.moving_mean, lay.moving_variance)]
         self.sync_parameters()
 
     # -- replicas ------------------------------------------------------------------------------------------------------ #
@@ -309,9 +315,9 @@ class Trainer(object):
         phase = self._phase_outputs()
         skip = tuple(k for k, _, _ in phase.values())
         if prep is not None:
-            outs = self.model.train_executor.run(x, prepared=prep['fwd'], skip_phasew=True, skip_ops=skip)
+            outs = self.model.train_executor.run(x, prepared=prep['fwd'], skip_phasew=True, skip_ops=skip, training=want_grad)
         else:
-            outs = self.model.train_executor.run(x, skip_ops=skip)
+            outs = self.model.train_executor.run(x, skip_ops=skip, training=want_grad)
         n_out = len(outs)
         if self._loss_out is None or self._loss_out.shape[0] != n_out:
             self._loss_out = torch.zeros((n_out, 7), dtype=torch.float32, device=self.device)
@@ -783,6 +789,16 @@ class Trainer(object):
                     dense = torch.empty((n, cin) + tuple(src.shape[2:]), dtype=torch.float32, device=self.device)
                     ops.rowconv2d_bwd_data(dz, lay.kernel, dd, xs, dense)
                 deposit(op.src, op.in_c_off, cin, dense)
+            elif op.kind == 'bn':              # BatchNormalization: dgamma, dbeta and dx from the batch statistics of the forward
+                lay = op.layer
+                st = self.model.train_executor.bn_state(k, int(n))
+                dx = ops.batchnorm_bwd(src, gD, lay.gamma, st['mean'], st['invstd'], st['ws'],
+                                       dgamma=self._grad_view(lay, 'gamma') if lay.gamma is not None else None,
+                                       dbeta=self._grad_view(lay, 'beta') if lay.beta is not None else None,
+                                       want_dx=op.src != P.STATE_IN)
+                touched_layers.add(id(lay))
+                if dx is not None:
+                    deposit(op.src, 0, src.shape[1], dx)
             elif op.kind == 'lstm':
                 zh_i, cp_i, co_i = op.aux
                 f = op.xs[0]
@@ -994,7 +1010,8 @@ class Trainer(object):
         pool = torch.cuda.MemPool()
         self._foreign = False
         validate = os.environ.get('DLWP_TAPE_VALIDATE', '1') != '0'
-        state0 = [t.clone() for t in [self.flat_params] + list(self.opt_state) + [self._iter_dev]] if validate else None
+        state0 = [t.clone() for t in [self.flat_params] + list(self.opt_state) + [self._iter_dev] + self._bn_stats] \
+            if validate else None
         def body(bx, bys):
             outs_, loss_, dys_ = self._forward_backward(bx, bys, scale)
             if dp is not None:       # the exchange and the update stay outside: a collective in between
@@ -1042,7 +1059,7 @@ class Trainer(object):
         """The freshly recorded step against the launch-by-launch step on a batch and weights neither has seen (see _record_step);
         returns None when they agree, else what differed.  Leaves the state the recorded step left."""
         from . import _lib
-        live = [self.flat_params] + list(self.opt_state) + [self._iter_dev]
+        live = [self.flat_params] + list(self.opt_state) + [self._iter_dev] + self._bn_stats
         # (the loss table rides behind the gradients only in a data-parallel step: the recorded launches write it there)
         gbuf = self._flat_exchange if data_parallel else self.flat_grads
         after = [t.clone() for t in live] + [gbuf.clone(), ent['loss'].clone()]
@@ -1070,8 +1087,8 @@ class Trainer(object):
                 why = 'replay failed: ' + _lib.lib.dlwp_last_error().decode('utf-8', 'replace')
             else:
                 torch.cuda.synchronize(self.device)
-                names = ['parameters'] + ['optimizer slot %d' % i for i in range(len(self.opt_state))] + \
-                    ['step counter', 'gradients', 'loss table']
+                names = ['parameters'] + ['optimizer slot %d' % i for i in range(len(self.opt_state))] + ['step counter'] + \
+                    ['moving statistics %d' % i for i in range(len(self._bn_stats))] + ['gradients', 'loss table']
                 for name, got, ref in zip(names, live + [gbuf, ent['loss']], want):
                     if got.dtype.is_floating_point:
                         if not bool(torch.isfinite(got).all()) and bool(torch.isfinite(ref).all()):

@@ -511,6 +511,31 @@ int dlwp_convlstm_gates_bwd(dlwp_handle_t, const void* zx, const void* zh, const
                             const void* dh, const void* dc_in, void* dz, void* dc_prev, int n, int f, int hw,
                             int h_c_off, int h_c_total, int act, int rec_act, int dtype, void* stream);
 
+/* ---- keras BatchNormalization(axis=1) on (n, c, hw) float32 tensors: the ('BatchNormalization', None, {'axis': 1}) entry
+ *      behind each Conv2D of examples/train.py:170-210, train_generator.py:172-212, Azure/train_tf.py:219-259 (csrc/batchnorm.hip).
+ *      Statistics per channel over (n, hw), deterministic (slabs merged with Chan's formula in a fixed order, no atomics).
+ *      fwd_train: y = gamma (x - mean_B) / sqrt(var_B + eps) + beta with the batch's biased variance; save_mean / save_invstd
+ *                 (c floats) keep mean_B and 1 / sqrt(var_B + eps) for the backward; moving_mean <- m moving_mean +
+ *                 (1 - m) mean_B, moving_var <- m moving_var + (1 - m) var_B M / (M - 1), M = n hw > 1, m = momentum.
+ *      fwd_infer: the same affine map with the moving statistics (y may alias x).
+ *      bwd      : dgamma = sum dy xhat, dbeta = sum dy (both nullable, overwritten), dx (nullable) = gamma invstd
+ *                 (dy - (sum dy + xhat sum dy xhat) / M), xhat = (x - save_mean) save_invstd.
+ *      gamma / beta nullable (scale=False / center=False: 1 / 0).  Any float alignment.  ws: caller-owned device memory of
+ *      dlwp_batchnorm_workspace() bytes, untouched between a call's kernels by anything else.                              */
+typedef struct {
+  int n, c, hw;                   /* samples, channels, pixels per plane                                  */
+  float momentum, epsilon;        /* Keras' momentum (the weight of the OLD moving value) and epsilon      */
+} dlwp_batchnorm;
+size_t dlwp_batchnorm_workspace(dlwp_batchnorm d);
+int dlwp_batchnorm_fwd_train(dlwp_handle_t, const void* x, void* y, const void* gamma, const void* beta, void* moving_mean,
+                             void* moving_var, void* save_mean, void* save_invstd, void* ws, size_t ws_bytes, dlwp_batchnorm d,
+                             void* stream);
+int dlwp_batchnorm_fwd_infer(dlwp_handle_t, const void* x, void* y, const void* gamma, const void* beta,
+                             const void* moving_mean, const void* moving_var, dlwp_batchnorm d, void* stream);
+int dlwp_batchnorm_bwd(dlwp_handle_t, const void* x, const void* dy, void* dx, const void* gamma, const void* save_mean,
+                       const void* save_invstd, void* dgamma, void* dbeta, void* ws, size_t ws_bytes, dlwp_batchnorm d,
+                       void* stream);
+
 /* ---- rollout: the N-step predict_timeseries loop (DLWP/model/models.py:277-293, 439-447) captured as ONE hipGraph.
  *      A plan is an array of dlwp_op describing one model call; buffer index >= 0 = caller scratch buffer,
  *      DLWP_BUF_STATE_IN = the call's input state, DLWP_BUF_OUT(o) = output o of the call.  Call t reads
@@ -529,6 +554,9 @@ int dlwp_convlstm_gates_bwd(dlwp_handle_t, const void* zx, const void* zh, const
 #define DLWP_OP_DEPTH2SPACE 7     /* src (n, 4F, h, w) -> dst window [conv.out_c_off, +F) of conv.out_c_total channels at
                                    * (2h, 2w); xs = (n, F, h, w) */
 #define DLWP_OP_ROWCONV2D  8      /* dlwp_rowconv2d_fwd: src, dst, w, b, xs, conv as for DLWP_OP_CONV2D (float32 buffers) */
+#define DLWP_OP_BATCHNORM  9      /* dlwp_batchnorm_fwd_infer: src, dst, xs = (n, c, h, w); w / b = gamma / beta buffer | -1,
+                                   * aux[0] / aux[1] = moving mean / variance buffer, aux[2] = the bits of epsilon (float).
+                                   * The moving statistics are read at every launch: a graph never holds stale ones.      */
 typedef struct {
   int kind;                 /* DLWP_OP_*                                                                  */
   int src, dst;             /* buffer indices                                                              */
