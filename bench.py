@@ -11,9 +11,12 @@ one hipGraph launch.  Members are sharded across ranks, no collective (weak scal
 
     python bench.py --gpus N --steps K --warmup W        (N > 1: launched by torch.distributed.run, one rank per GPU)
     --dump-outputs DIR   also writes what the last timed step returned as DIR/*.npy (dump_outputs: seeded sample, <= 64 MB)
+    --full               also measures forward, roofline, layers, sub_records and cpu_baseline (below)
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run does only what `value` needs: set-up, warm-up, the K timed steps, the dump.
   value      members x 56 x K x N / wall  [6-h forecast steps / s], state resident in HBM.
+With --full, after the timed steps (each takes runs of its own; --no-extras / --no-cpu-baseline drop the last two):
+  forward    the forward's executed and algorithmic rates over the timed wall (from the per-kernel timing of `layers`).
   roofline   the kernel with the largest share of the forward's time (all its launches), timed live with HIP events on the
              launch stream.  `achieved` / `frac` are the matrix-core FLOPs the kernel EXECUTES (dlwp_conv2d_launch_info:
              the padded GEMM volume of its MFMA instructions == SQ_INSTS_MFMA x 2048 of a rocprofv3 --pmc pass) over the
@@ -1078,8 +1081,10 @@ def main():
     ap.add_argument('--forwards', type=int, default=28, help='model applications per rollout (28 = 14 days)')
     ap.add_argument('--grid', default='88x180')
     ap.add_argument('--channels', type=int, default=4)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extras', action='store_true', help='skip the sub-records (members 1/8, host-visible, layer 1, '
+    ap.add_argument('--full', action='store_true', help='besides the headline, time every kernel of the forward (forward, '
+                                                        'roofline, layers), the sub-records and the CPU baseline')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
+    ap.add_argument('--no-extras', action='store_true', help='--full: skip the sub-records (members 1/8, host-visible, layer 1, '
                                                              'training, config 5)')
     ap.add_argument('--extras-timeout', type=float, default=240.0,
                     help='N > 1: seconds the collective sub-records may take before the line is printed without them')
@@ -1109,8 +1114,6 @@ def main():
     net = d.model
     net.set_activation_dtype(a.activation_dtype)
     flops_fwd = net.plan.conv_flops_per_sample()
-    bytes_fwd = net.infer_plan.algorithmic_bytes_per_sample()
-    weights_np = [(w, b) for w, b in zip(net.get_weights()[0::2], net.get_weights()[1::2])]
 
     # members: one base state + 0.01 * N(0,1) perturbations, different per rank
     if a.scaling == 'strong':          # --members in total: this rank's contiguous shard (no collective in a rollout)
@@ -1184,7 +1187,8 @@ def main():
                 sys.stdout.flush()
             state['printed'] = True
 
-    if rank == 0:
+    if a.full and rank == 0:
+        bytes_fwd = net.infer_plan.algorithmic_bytes_per_sample()
         rows = time_layers(net, m_local)
         executed_fwd = sum(r['executed_flops'] for r in rows) / m_local            # per member per forward
         per_gpu_fwd_per_s = fwd_per_s / world
@@ -1205,7 +1209,7 @@ def main():
             out['roofline']['pmc_crosscheck'] = cc
         out['layers'] = [{k: (round(v, 4) if isinstance(v, float) else v) for k, v in r.items()
                           if k not in ('flops', 'bytes', 'executed_flops', 'useful_flops', 'launch_flops', 'bf16_matrix')} for r in rows]
-    if not a.no_extras:
+    if a.full and not a.no_extras:
         sub = {}
         if rank == 0:
             try:
@@ -1260,8 +1264,9 @@ def main():
             sub['ensemble_cfg5'] = sub_cfg5(world, rank, barrier, dev)
         except Exception as e:  # noqa: BLE001
             sub['error_collective'] = repr(e)
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
-        out['cpu_baseline'] = cpu_baseline(grid, a.channels, a.forwards, weights_np)
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
+        ws = net.get_weights()
+        out['cpu_baseline'] = cpu_baseline(grid, a.channels, a.forwards, list(zip(ws[0::2], ws[1::2])))
     # what the stream probes of every rank found (util.distinct_streams: side streams of the training step, the loader's and the
     # rollout's copy streams): candidates passed over because they shared a hardware queue, streams that had to share one anyway
     from dlwp_amd import util as _util

@@ -176,15 +176,15 @@ def test_two_gpu_rccl_training_equals_the_single_process_run(mode, n_global):
 
 
 def test_bench_gpus_2_as_a_plain_script_prints_one_line_with_the_collective_sub_records():
-    """`python bench.py --gpus 2` the way the driver starts it (no torchrun environment): bench.py spawns its ranks, here two
-    on the one GPU over gloo, and rank 0 prints ONE JSON line whose sub-records include the data-parallel training step
+    """`python bench.py --gpus 2 --full` the way the driver starts it (no torchrun environment): bench.py spawns its ranks, here
+    two on the one GPU over gloo, and rank 0 prints ONE JSON line whose sub-records include the data-parallel training step
     (train_cfg3) and the sharded ensemble (ensemble_cfg5)."""
     import json
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_PORT')}
     env.update(DLWP_SHARE_GPUS='1', DLWP_DIST_BACKEND='gloo')
     p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1',
-                        '--members', '16', '--no-cpu-baseline'], env=env, capture_output=True, text=True, timeout=900)
+                        '--members', '16', '--full', '--no-cpu-baseline'], env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1, p.stdout[-2000:]
