@@ -25,6 +25,8 @@ F32, BF16, BF16_O8 = 0, 1, 2
 ROLLOUT_PREPARED = 0x100
 PAD_ZERO, PAD_WRAP, PAD_EDGE, PAD_REFLECT, PAD_SYMMETRIC = 0, 1, 2, 3, 4
 ACT_LINEAR, ACT_TANH, ACT_RELU = 0, 1, 2
+LOSS_MSE, LOSS_MAE, LOSS_MAPE, LOSS_MSLE, LOSS_LOGCOSH = 0, 1, 2, 3, 4      # dlwp_loss_elementwise kinds
+METRIC_ACC_SUMS = 0x20
 SRC_DIRECT, SRC_UPSAMPLE2, SRC_MAXPOOL2 = 0, 1, 2
 OP_CONV2D, OP_PAD2D, OP_MAXPOOL2, OP_UPSAMPLE2, OP_COPYCH, OP_LSTM_GATES, OP_PHASE_WEIGHTS, OP_DEPTH2SPACE = 0, 1, 2, 3, 4, 5, 6, 7
 OP_ROWCONV2D = 8
@@ -192,6 +194,12 @@ _sig('dlwp_mse_mae_phase_workspace', [_i], _sz)
 _sig('dlwp_mse_mae_phase', [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, ctypes.c_float, _vp, _sz, _i, _vp])
 _sig('dlwp_loss_workspace', [_vp, _i, _i], _sz)
 _sig('dlwp_loss_custom', [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, ctypes.c_float, _vp, _sz, _i, _vp])
+_sig('dlwp_loss_elementwise_workspace', [_vp], _sz)
+_sig('dlwp_loss_elementwise', [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, ctypes.c_float, _vp, _sz, _i, _vp])
+_sig('dlwp_loss_elementwise_phase_workspace', [_i], _sz)
+_sig('dlwp_loss_elementwise_phase', [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, ctypes.c_float, _vp, _sz, _i, _vp])
+_sig('dlwp_loss_metrics_workspace', [_vp], _sz)
+_sig('dlwp_loss_metrics', [_vp, _vp, _vp, _i, _i, _i, _i, _i, ctypes.c_uint, _vp, _vp, _sz, _i, _vp])
 _sig('dlwp_adam_keras', [_vp, _vp, _vp, _vp, _vp, _sz] + [ctypes.c_float] * 5 + [ctypes.c_longlong, ctypes.c_float, _vp])
 _sig('dlwp_copy_many', [_vp, _vp, _vp, _vp, _i, _vp])
 _sig('dlwp_adam_keras_dev', [_vp, _vp, _vp, _vp, _vp, _sz] + [ctypes.c_float] * 5 + [_vp, _vp, ctypes.c_float, _vp])

@@ -43,8 +43,15 @@ def install(force=False):
     keras.models = _module('keras.models', Model=engine.Model, Sequential=engine.Sequential)
     keras.callbacks = _module('keras.callbacks', Callback=custom.Callback, History=custom.History,
                               EarlyStopping=custom.EarlyStopping)
-    keras.losses = _module('keras.losses', mean_squared_error=training.mean_squared_error,
-                           mean_absolute_error=training.mean_absolute_error)
+    losses = dict(mean_squared_error=training.mean_squared_error, mean_absolute_error=training.mean_absolute_error,
+                  mean_absolute_percentage_error=training.mean_absolute_percentage_error,
+                  mean_squared_logarithmic_error=training.mean_squared_logarithmic_error, logcosh=training.logcosh)
+    losses.update(mse=losses['mean_squared_error'], MSE=losses['mean_squared_error'], mae=losses['mean_absolute_error'],
+                  MAE=losses['mean_absolute_error'], mape=losses['mean_absolute_percentage_error'],
+                  MAPE=losses['mean_absolute_percentage_error'], msle=losses['mean_squared_logarithmic_error'],
+                  MSLE=losses['mean_squared_logarithmic_error'])
+    keras.losses = _module('keras.losses', **losses)
+    keras.metrics = _module('keras.metrics', **losses)
     keras.regularizers = _module('keras.regularizers', l2=regularizers.l2, l1_l2=regularizers.l1_l2,
                                  L1L2=regularizers.L1L2)
     keras.optimizers = _module('keras.optimizers', Adam=training.Adam, SGD=training.SGD)

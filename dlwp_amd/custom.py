@@ -146,12 +146,34 @@ def row_conv2d(inputs, kernel, kernel_size, strides, output_shape, data_format=N
     return y if fmt == 'channels_first' else y.permute(0, 2, 3, 1).contiguous()
 
 
-class LossSpec(object):
-    """What `anomaly_correlation_loss(...)` / `latitude_weighted_loss(...)` return: a description the trainer lowers to
-    dlwp_loss_custom.  kind 0 = (latitude-weighted) mse, kind 1 = regularizer - anomaly correlation."""
+#: the Keras 2.2 regression losses by name and alias (keras/losses.py) -> dlwp_loss_elementwise kind (include/dlwp_hip.h)
+LOSS_KINDS = {'mse': 0, 'MSE': 0, 'mean_squared_error': 0,
+              'mae': 1, 'MAE': 1, 'mean_absolute_error': 1,
+              'mape': 2, 'MAPE': 2, 'mean_absolute_percentage_error': 2,
+              'msle': 3, 'MSLE': 3, 'mean_squared_logarithmic_error': 3,
+              'logcosh': 4}
+#: kind -> the Keras function's __name__ (the name Keras logs a metric under)
+KIND_NAMES = ('mean_squared_error', 'mean_absolute_error', 'mean_absolute_percentage_error', 'mean_squared_logarithmic_error',
+              'logcosh')
 
-    def __init__(self, kind, regularize=0, mean=None, row_weights=None, scale=1.0, name='loss'):
+
+def loss_kind(loss_function):
+    """The dlwp_loss_elementwise kind of a Keras loss given by name or as a function (its __name__); None: not one of them."""
+    name = loss_function if isinstance(loss_function, str) else getattr(loss_function, '__name__', None)
+    return LOSS_KINDS.get(name)
+
+
+class LossSpec(object):
+    """What `anomaly_correlation_loss(...)` / `latitude_weighted_loss(...)` / `LatitudeWeightedLoss(...)` return: a description
+    the trainer lowers to the HIP loss kernels.  kind 0 = (latitude-weighted) Keras loss `inner` (0 mse: dlwp_loss_custom, as
+    before; 1 mae, 2 mape, 3 msle, 4 logcosh: dlwp_loss_elementwise), kind 1 = regularizer - anomaly correlation
+    (dlwp_loss_custom)."""
+
+    def __init__(self, kind, regularize=0, mean=None, row_weights=None, scale=1.0, name='loss', inner=0):
         self.kind, self.regularize, self.scale = kind, regularize, scale
+        self.inner = int(inner)
+        if self.inner and kind != 0:
+            raise ValueError('an inner loss kind goes with kind 0 only')
         self.mean = None if mean is None else np.ascontiguousarray(mean, dtype=np.float32)
         self.row_weights = None if row_weights is None else np.ascontiguousarray(row_weights, dtype=np.float32)
         self.__name__ = name
@@ -185,9 +207,22 @@ def anomaly_correlation_loss(mean=None, regularize_mean='mse', reverse=True):
     return LossSpec(1, reg, None if mean is None else np.asarray(mean)[0], None, 1.0 if reverse else -1.0, 'acc_loss')
 
 
+def _weighted_spec(loss_function, w, name):
+    """A LossSpec applying `loss_function` to (w * y_true, w * y_pred), w per row (None: no weighting)."""
+    if isinstance(loss_function, LossSpec):
+        return LossSpec(loss_function.kind, loss_function.regularize, loss_function.mean, w, loss_function.scale, name,
+                        inner=loss_function.inner)
+    kind = 0 if loss_function is None else loss_kind(loss_function)
+    if kind is None:
+        raise NotImplementedError('a latitude-weighted %r is not implemented (mse, mae, mape, msle, logcosh and '
+                                  'anomaly_correlation_loss(...) are)' % (loss_function,))
+    return LossSpec(0, 0, None, w, 1.0, name, inner=kind)
+
+
 def latitude_weighted_loss(loss_function=None, lats=None, output_shape=(), axis=-2, weighting='cosine'):
     """Weight predictions and targets by a function of latitude before the loss (reference custom.py:956-991).
-    loss_function: mean_squared_error (default) or the result of anomaly_correlation_loss(...)."""
+    loss_function: mean_squared_error (default), any Keras regression loss of LOSS_KINDS (name or function), or the result of
+    anomaly_correlation_loss(...)."""
     if weighting not in ['cosine', 'midlatitude']:
         raise ValueError("'weighting' must be one of 'cosine' or 'midlatitude'")
     w = None
@@ -195,13 +230,63 @@ def latitude_weighted_loss(loss_function=None, lats=None, output_shape=(), axis=
         if axis != -2 and axis != len(output_shape) - 2:
             raise NotImplementedError('latitude_weighted_loss: the latitude axis must be the second to last (axis=-2)')
         w = latitude_weights(lats, weighting)
-    if isinstance(loss_function, LossSpec):
-        return LossSpec(loss_function.kind, loss_function.regularize, loss_function.mean, w, loss_function.scale,
-                        'lat_loss')
-    name = loss_function if isinstance(loss_function, str) else getattr(loss_function, '__name__', 'mean_squared_error')
-    if loss_function is not None and name not in ('mse', 'mean_squared_error'):
-        raise NotImplementedError('latitude_weighted_loss over %r is not implemented' % (loss_function,))
-    return LossSpec(0, 0, None, w, 1.0, 'lat_loss')
+    return _weighted_spec(loss_function, w, 'lat_loss')
+
+
+class LatitudeWeightedLoss(LossSpec):
+    """The class form of the latitude weighting (reference custom.py:899-953): loss_function(y_true * w, y_pred * w) with the
+    CLASS's weights -- cos(lat), or cos(lat) - 0.25 sin(2 lat) for 'midlatitude' (the function form adds 0.5 sin^2(2 lat)).
+    'channels_last' builds (h, w) weights: on this package's (n, c, h, w) outputs, a weight per row.  The 'channels_first' branch
+    builds an (h, h, w) tensor, which lines latitude up with the CHANNEL axis of an (n, c, h, w) output -- not a latitude
+    weighting -- and is refused."""
+
+    def __init__(self, loss_function, lats, data_format='channels_last', weighting='cosine'):
+        from .layers import normalize_data_format
+        self.data_format = normalize_data_format(data_format)
+        if weighting not in ['cosine', 'midlatitude']:
+            raise ValueError("'weighting' must be one of 'cosine' or 'midlatitude'")
+        if self.data_format == 'channels_first':
+            raise NotImplementedError("LatitudeWeightedLoss(data_format='channels_first') weights an (n, c, h, w) output by an "
+                                      "(h, h, w) tensor: latitude lines up with the channel axis, not the rows.  Use the default "
+                                      "'channels_last' (one weight per row) or latitude_weighted_loss(...)")
+        self.loss_function, self.weighting = loss_function, weighting
+        self.lats = np.asarray(lats)
+        self.weights = self.class_weights(self.lats, weighting)
+        spec = _weighted_spec(loss_function, self.weights, 'latitude_weighted_loss')
+        super(LatitudeWeightedLoss, self).__init__(spec.kind, spec.regularize, spec.mean, spec.row_weights, spec.scale,
+                                                   'latitude_weighted_loss', inner=spec.inner)
+
+    @staticmethod
+    def class_weights(lats, weighting='cosine'):
+        """cos(lat) [- 0.25 sin(2 lat) for 'midlatitude'] (reference custom.py:922-926), float32."""
+        lat = np.asarray(lats, dtype=np.float32) * np.float32(np.pi / 180.)
+        w = np.cos(lat)
+        if weighting == 'midlatitude':
+            w = w - np.float32(0.25) * np.sin(2 * lat)
+        return w.astype(np.float32)
+
+
+def anomaly_correlation(y_true, y_pred, mean=0., regularize_mean='mse', reverse=True):
+    """The anomaly-correlation METRIC (reference custom.py:994-1033): `mse - ACC` as Keras calls it (defaults), ACC =
+    mean(yp yt) / sqrt(mean(yp^2) mean(yt^2)); `mean` is ignored, as the reference's docstring says.  As metrics=[...] the
+    trainer takes it from the sums of its one metrics pass; called directly on device tensors it runs that pass
+    (dlwp_loss_metrics) and returns a 0-d device tensor."""
+    if regularize_mean not in (None, 'mse', 'mae'):
+        raise NotImplementedError("anomaly_correlation(regularize_mean=%r): only None, 'mse' and 'mae' are implemented"
+                                  % (regularize_mean,))
+    import torch
+    from . import _lib, ops
+    yp = y_pred.contiguous().float()
+    yt = y_true.contiguous().float()
+    if yp.dim() != 4:
+        yp, yt = yp.reshape(1, 1, 1, -1), yt.reshape(1, 1, 1, -1)
+    out = torch.zeros(5, dtype=torch.float32, device=yp.device)
+    ops.loss_metrics(yp, yt, out, (1 << _lib.LOSS_MSE) | (1 << _lib.LOSS_MAE) | _lib.METRIC_ACC_SUMS)
+    a = out[2] / torch.sqrt(out[3] * out[4])
+    m = {None: None, 'mse': out[0], 'mae': out[1]}[regularize_mean]
+    if reverse:
+        return -a if m is None else m - a
+    return a if m is None else a - m
 
 
 # compatibility names (reference custom.py:1091-1093): what load_model's custom_objects of older scripts look up

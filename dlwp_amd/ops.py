@@ -885,6 +885,63 @@ def loss_custom(y_pred, y_true, stats7, dy=None, loss_weight=1.0, mean=None, row
     return stats7
 
 
+def loss_elementwise(y_pred, y_true, out1, dy=None, loss_weight=1.0, kind=1, row_weights=None, ws_key=None):
+    """include/dlwp_hip.h: dlwp_loss_elementwise.  y: (n, c, h, w) device tensors; out1 (device, 1 float) <- the mean of kind
+    (_lib.LOSS_*) over w*y_pred, w*y_true (w = row_weights[h] or 1); dy <- loss_weight * dL/dy_pred."""
+    _check_f32(y_pred, y_true, out1, dy, row_weights)
+    n, c, hh, ww = y_pred.shape
+    if tuple(y_true.shape) != tuple(y_pred.shape):
+        raise ValueError('loss_elementwise: target %r does not match the prediction %r' % (tuple(y_true.shape), tuple(y_pred.shape)))
+    h = _lib.handle(_dev(y_pred))
+    ws = workspace2(y_pred.device, _lib.lib.dlwp_loss_elementwise_workspace(h), ('loss_ew', ws_key))
+    _lib.check(_lib.lib.dlwp_loss_elementwise(h, _ptr(y_pred), _ptr(y_true), n, c, hh, ww, _ptr(row_weights), int(kind),
+                                              _ptr(out1), _ptr(dy), float(loss_weight), _ptr(ws), ws.numel(), _lib.F32,
+                                              _stream(y_pred)))
+    return out1
+
+
+def loss_elementwise_phase(y_phase, y_true, out1, dz=None, db=None, loss_weight=1.0, kind=1, row_weights=None, ws_key=None):
+    """loss_elementwise on the phase channels (n, 4f, h, w) of a restated output layer against the target (n, f, 2h, 2w) (w
+    even); dz (phase layout) and db (4f: the sums of dz) are optional outputs, as for mse_mae_phase."""
+    _check_f32(y_phase, y_true, out1, dz, db, row_weights)
+    n, f4, hh, ww = y_phase.shape
+    f = f4 // 4
+    if f4 != 4 * f or tuple(y_true.shape) != (n, f, 2 * hh, 2 * ww):
+        raise ValueError('loss_elementwise_phase: phase tensor %r does not match the target %r'
+                         % (tuple(y_phase.shape), tuple(y_true.shape)))
+    h = _lib.handle(_dev(y_phase))
+    ws = workspace2(y_phase.device, _lib.lib.dlwp_loss_elementwise_phase_workspace(f), ('loss_ew_phase', ws_key))
+    _lib.check(_lib.lib.dlwp_loss_elementwise_phase(h, _ptr(y_phase), _ptr(y_true), n, f, hh, ww, _ptr(row_weights), int(kind),
+                                                    _ptr(out1), _ptr(dz), _ptr(db), float(loss_weight), _ptr(ws), ws.numel(),
+                                                    _lib.F32, _stream(y_phase)))
+    return out1
+
+
+def metric_columns(mask):
+    """Number of floats dlwp_loss_metrics writes for `mask`."""
+    return bin(int(mask) & 0x1f).count('1') + (3 if int(mask) & _lib.METRIC_ACC_SUMS else 0)
+
+
+def loss_metrics(y_pred, y_true, out, mask, phase=False, ws_key=None):
+    """include/dlwp_hip.h: dlwp_loss_metrics -- one pass over (y_pred, y_true) fills out[:metric_columns(mask)] with the selected
+    means (mse, mae, mape, msle, logcosh, then mean(p t), mean(p^2), mean(t^2)).  phase: y_pred is the phase form
+    (n, 4f, h, w) of the (n, f, 2h, 2w) target."""
+    _check_f32(y_pred, y_true, out)
+    n, c, hh, ww = y_true.shape
+    if phase:
+        if tuple(y_pred.shape) != (n, 4 * c, hh // 2, ww // 2):
+            raise ValueError('loss_metrics: phase tensor %r does not match the target %r' % (tuple(y_pred.shape), tuple(y_true.shape)))
+    elif tuple(y_pred.shape) != tuple(y_true.shape):
+        raise ValueError('loss_metrics: target %r does not match the prediction %r' % (tuple(y_true.shape), tuple(y_pred.shape)))
+    if out.numel() < metric_columns(mask):
+        raise ValueError('loss_metrics: %d output floats for %d metric columns' % (out.numel(), metric_columns(mask)))
+    h = _lib.handle(_dev(y_pred))
+    ws = workspace2(y_pred.device, _lib.lib.dlwp_loss_metrics_workspace(h), ('loss_metrics', ws_key))
+    _lib.check(_lib.lib.dlwp_loss_metrics(h, _ptr(y_pred), _ptr(y_true), n, c, hh, ww, 1 if phase else 0, int(mask), _ptr(out),
+                                          _ptr(ws), ws.numel(), _lib.F32, _stream(y_pred)))
+    return out
+
+
 def adam_keras(p, m, v, g, iteration, lr=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7, decay=0.0, grad_scale=1.0):
     _check_f32(p, m, v, g)
     _lib.check(_lib.lib.dlwp_adam_keras(_lib.handle(_dev(p)), _ptr(p), _ptr(m), _ptr(v), _ptr(g), p.numel(), lr, beta_1,

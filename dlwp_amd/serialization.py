@@ -65,8 +65,11 @@ def _layer_config(lay):
 def _loss_config(loss):
     from .custom import LossSpec
     if isinstance(loss, LossSpec):
-        return {'spec': {'kind': loss.kind, 'regularize': loss.regularize, 'scale': loss.scale, 'name': loss.__name__,
-                         'has_mean': loss.mean is not None, 'has_row_weights': loss.row_weights is not None}}
+        spec = {'kind': loss.kind, 'regularize': loss.regularize, 'scale': loss.scale, 'name': loss.__name__,
+                'has_mean': loss.mean is not None, 'has_row_weights': loss.row_weights is not None}
+        if loss.inner:            # (absent for mse: a spec of the earlier kinds is written as before)
+            spec['inner'] = loss.inner
+        return {'spec': spec}
     return loss if isinstance(loss, str) else getattr(loss, '__name__', None)
 
 
@@ -378,7 +381,28 @@ _KERAS_NEUTRAL = {'return_state': False, 'go_backwards': False, 'stateful': Fals
                   'use_bias': True, 'data_format': 'channels_first', 'padding': 'valid', 'dilation_rate': (1, 1)}
 
 
-def import_keras_hdf5(path, custom_objects=None, device=None, compile=True):
+def _resolve_metrics(names, custom_objects=None, package_objects=None):
+    """The metrics= of a stored training configuration that this package computes: Keras regression-loss names and
+    'anomaly_correlation' as they are, other names through custom_objects (first) or the package's own objects; the rest is
+    dropped, as before."""
+    from . import custom as C
+    out = []
+    for m in names or []:
+        if not isinstance(m, str):
+            continue
+        if m in (custom_objects or {}):
+            obj = custom_objects[m]
+        elif C.loss_kind(m) is not None or m == 'anomaly_correlation':
+            obj = m
+        else:
+            obj = (package_objects or {}).get(m)
+        if isinstance(obj, C.LossSpec) or obj is C.anomaly_correlation or (obj is not None and C.loss_kind(obj) is not None) \
+                or obj == 'anomaly_correlation':
+            out.append(obj)
+    return out
+
+
+def import_keras_hdf5(path, custom_objects=None, device=None, compile=True, package_objects=None):
     """Build a Model from a Keras 2.x HDF5 checkpoint (`keras.models.save_model` layout: root attribute `model_config` = JSON
     of the Sequential / functional graph, group `model_weights/<layer>/<weight names>`, optional `training_config`).  The
     container is read by dlwp_amd.hdf5_lite (no h5py for this interpreter).  Layers are looked up by class name in
@@ -489,12 +513,14 @@ def import_keras_hdf5(path, custom_objects=None, device=None, compile=True):
             priv = f['dlwp_amd']
             sp = json.loads(text(priv.attrs['loss_spec']))
             loss = C.LossSpec(sp['kind'], sp['regularize'], np.asarray(priv['loss_mean'][...]) if sp['has_mean'] else None,
-                              np.asarray(priv['loss_row_weights'][...]) if sp['has_row_weights'] else None, sp['scale'], sp['name'])
-        known = isinstance(loss, C.LossSpec) or (isinstance(loss, str) and
-                                                  loss in ('mse', 'mean_squared_error', 'mae', 'mean_absolute_error'))
+                              np.asarray(priv['loss_row_weights'][...]) if sp['has_row_weights'] else None, sp['scale'], sp['name'],
+                              inner=sp.get('inner', 0))
+        elif isinstance(loss, str) and isinstance((package_objects or {}).get(loss), C.LossSpec):
+            loss = package_objects[loss]
+        known = isinstance(loss, C.LossSpec) or ((isinstance(loss, str) or callable(loss)) and C.loss_kind(loss) is not None)
         if ocls is not None and known:
             ocfg = {k: v for k, v in oc.get('config', {}).items() if isinstance(v, (int, float))}
-            metrics = [m for m in (tc.get('metrics') or []) if m in ('mae', 'mse', 'mean_absolute_error', 'mean_squared_error')]
+            metrics = _resolve_metrics(tc.get('metrics'), custom_objects, package_objects)
             ocfg.pop('amsgrad', None)
             model.compile(optimizer=ocls(**ocfg), loss=loss, metrics=metrics, loss_weights=tc.get('loss_weights'))
             if 'optimizer_weights' in f:
@@ -523,13 +549,14 @@ def import_keras_hdf5(path, custom_objects=None, device=None, compile=True):
     return model
 
 
-def load_model_file(path, custom_objects=None, device=None):
+def load_model_file(path, custom_objects=None, device=None, package_objects=None):
+    """package_objects: names a stored loss / metric may resolve to after custom_objects (util.load_model: DLWP.custom)."""
     from . import custom as C
     from . import engine
     from . import layers as L
     from . import hdf5_lite
     if hdf5_lite.is_hdf5(path):          # a real Keras checkpoint (reference DLWP/util.py:141-144)
-        return import_keras_hdf5(path, custom_objects=custom_objects, device=device)
+        return import_keras_hdf5(path, custom_objects=custom_objects, device=device, package_objects=package_objects)
     with open(path, 'rb') as f:
         data = np.load(io.BytesIO(f.read()), allow_pickle=False)
     arch = json.loads(bytes(data['__arch__']).decode('utf-8'))
@@ -577,8 +604,10 @@ def load_model_file(path, custom_objects=None, device=None):
         if isinstance(loss, dict):
             sp = loss['spec']
             loss = C.LossSpec(sp['kind'], sp['regularize'], data['__loss_mean__'] if sp['has_mean'] else None,
-                              data['__loss_row_weights__'] if sp['has_row_weights'] else None, sp['scale'], sp['name'])
-        model.compile(optimizer=opt, loss=loss, metrics=comp['metrics'], loss_weights=comp['loss_weights'])
+                              data['__loss_row_weights__'] if sp['has_row_weights'] else None, sp['scale'], sp['name'],
+                              inner=sp.get('inner', 0))
+        model.compile(optimizer=opt, loss=loss, metrics=_resolve_metrics(comp['metrics'], custom_objects, package_objects),
+                      loss_weights=comp['loss_weights'])
         slots = []
         while '__opt_state_%d__' % len(slots) in data.files:
             slots.append(data['__opt_state_%d__' % len(slots)])

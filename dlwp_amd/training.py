@@ -67,20 +67,50 @@ def mean_absolute_error(y_true, y_pred):
     raise RuntimeError('marker only')
 
 
+def mean_absolute_percentage_error(y_true, y_pred):
+    raise RuntimeError('marker only')
+
+
+def mean_squared_logarithmic_error(y_true, y_pred):
+    raise RuntimeError('marker only')
+
+
+def logcosh(y_true, y_pred):
+    raise RuntimeError('marker only')
+
+
 def _loss_name(loss):
-    from .custom import LossSpec
+    """'mse' (dlwp_mse_mae), 'custom' (a LossSpec) or 'elementwise' (another Keras regression loss: dlwp_loss_elementwise)."""
+    from .custom import LossSpec, loss_kind
     if isinstance(loss, LossSpec):
         return 'custom'
-    name = loss if isinstance(loss, str) else getattr(loss, '__name__', None)
-    if name in ('mse', 'MSE', 'mean_squared_error'):
+    kind = loss_kind(loss)
+    if kind == 0:
         return 'mse'
-    raise NotImplementedError("loss %r is not implemented on the HIP path ('mse' / mean_squared_error, "
-                              "dlwp_amd.custom.anomaly_correlation_loss(...) and latitude_weighted_loss(...) are)"
-                              % (loss,))
+    if kind is not None:
+        return 'elementwise'
+    raise NotImplementedError("loss %r is not implemented on the HIP path ('mse', 'mae', 'mape', 'msle', 'logcosh' and their "
+                              "Keras names, dlwp_amd.custom.anomaly_correlation_loss(...), latitude_weighted_loss(...) and "
+                              "LatitudeWeightedLoss(...) are)" % (loss,))
 
 
 _METRIC_NAMES = {'mae': 'mean_absolute_error', 'mean_absolute_error': 'mean_absolute_error',
                  'mse': 'mean_squared_error', 'mean_squared_error': 'mean_squared_error'}
+
+
+def _metric_entry(m):
+    """(log name, what) of one metrics= entry: what = ('kind', k) for a Keras regression loss, ('acc',) for
+    custom.anomaly_correlation, ('spec', LossSpec) for a loss object of this package."""
+    from . import custom as C
+    if isinstance(m, C.LossSpec):
+        return m.__name__, ('spec', m)
+    if m is C.anomaly_correlation or m == 'anomaly_correlation':
+        return 'anomaly_correlation', ('acc',)
+    kind = C.loss_kind(m)
+    if kind is None:
+        raise NotImplementedError('metric %r is not implemented (mse, mae, mape, msle, logcosh, anomaly_correlation and the '
+                                  'loss objects of dlwp_amd.custom are)' % (m,))
+    return C.KIND_NAMES[kind], ('kind', kind)
 
 
 # ------------------------------------------------------------------------------------------------------------------ #
@@ -161,11 +191,12 @@ class Trainer(object):
             raise ValueError('loss_weights has %d entries for %d outputs' % (len(lw), n_out))
         self.loss_weights = [float(v) for v in lw]
         self.metric_keys = []
+        metrics = []
         for m in model.metrics:
-            key = m if isinstance(m, str) else getattr(m, '__name__', None)
-            if key not in _METRIC_NAMES:
-                raise NotImplementedError('metric %r is not implemented (mae, mse are)' % (m,))
-            self.metric_keys.append(_METRIC_NAMES[key])
+            key, what = _metric_entry(m)
+            self.metric_keys.append(key)
+            metrics.append(what)
+        self._plan_loss_table(metrics)
         out_names = [t.layer.name for t in model.outputs]
         if n_out == 1:
             self.metrics_names = ['loss'] + list(self.metric_keys)
@@ -175,10 +206,11 @@ class Trainer(object):
         self.flat_params, self.entries = flatten_parameters(model)
         # gradients + (behind them) the [n_out, 7] loss table of a data-parallel step: ONE buffer, ONE all-reduce
         n_par = self.flat_params.numel()
-        n_x = -(-(n_par + 7 * n_out) // 4) * 4        # (whole float4: the library's own exchange moves 16-byte units)
+        nc = self.n_cols
+        n_x = -(-(n_par + nc * n_out) // 4) * 4       # (whole float4: the library's own exchange moves 16-byte units)
         self._flat_exchange = torch.zeros(n_x, dtype=torch.float32, device=self.device)
         self.flat_grads = self._flat_exchange[:n_par]
-        self._loss_tail = self._flat_exchange[n_par:n_par + 7 * n_out].view(n_out, 7)
+        self._loss_tail = self._flat_exchange[n_par:n_par + nc * n_out].view(n_out, nc)
         self.opt_state = None
         self.dp = getattr(model, '_dp', None)
         self._grad_bufs = {}
@@ -201,6 +233,96 @@ class Trainer(object):
         # validated on (see _validate_step)
         self._bn_stats = [t for lay in self.plan.bn_layers for t in (lay.moving_mean, lay.moving_variance)]
         self.sync_parameters()
+
+    # -- the loss table ------------------------------------------------------------------------------------------------ #
+    def _plan_loss_table(self, metrics):
+        """Columns of the per-output loss table: 0 the loss value of a custom / elementwise loss, 1 mse, 2 mae, 3-6 the custom
+        loss's sums (as before); then the columns of ONE dlwp_loss_metrics pass (the kinds the loss kernel does not leave in 1 / 2,
+        in kind order, then mean(p t), mean(p^2), mean(t^2) for anomaly_correlation); then one column per elementwise LossSpec
+        metric and seven per dlwp_loss_custom LossSpec metric.  Only today's metrics: the table stays 7 columns wide."""
+        from . import _lib, ops
+        spec = self.model.loss if self.loss_kind == 'custom' else None
+        # (kind, row weights, scale) of a loss lowered to dlwp_loss_elementwise; None: dlwp_mse_mae / dlwp_loss_custom as before
+        if self.loss_kind == 'elementwise':
+            from .custom import loss_kind
+            self._ew = (loss_kind(self.model.loss), None, 1.0)
+        elif spec is not None and spec.kind == 0 and spec.inner:
+            self._ew = (spec.inner, spec.row_weights, spec.scale)
+        else:
+            self._ew = None
+        have = {0: 1, 1: 2} if self._ew is None else {}       # kinds the loss kernel already leaves in the table (mse, mae)
+        mask = 0
+        for what in metrics:
+            if what[0] == 'kind' and what[1] not in have:
+                mask |= 1 << what[1]
+            elif what[0] == 'acc':
+                mask |= _lib.METRIC_ACC_SUMS | (0 if 0 in have else 1 << _lib.LOSS_MSE)
+        col = dict(have)
+        c = 7
+        for k in range(5):
+            if mask & (1 << k):
+                col[k] = c
+                c += 1
+        acc_col = c if mask & _lib.METRIC_ACC_SUMS else None
+        c += ops.metric_columns(mask) - ops.metric_columns(mask & 0x1f)
+        self._metric_mask = mask
+        self._metric_cols = []          # per metric: ('col', c) | ('acc', mse column, first sum column) | ('spec', c, spec)
+        self._spec_metrics = []         # (first column, LossSpec)
+        self._batch_stat = False        # a metric that is a whole-batch statistic: epoch logs average per-batch values
+        for what in metrics:
+            if what[0] == 'kind':
+                self._metric_cols.append(('col', col[what[1]]))
+            elif what[0] == 'acc':
+                self._metric_cols.append(('acc', col[0], acc_col))
+                self._batch_stat = True
+            else:
+                ms = what[1]
+                self._spec_metrics.append((c, ms))
+                self._metric_cols.append(('spec', c, ms))
+                if ms.kind == 0 and ms.inner:
+                    c += 1
+                else:
+                    c += 7
+                    self._batch_stat = self._batch_stat or ms.kind == 1
+        self.n_cols = c
+        self._spec_consts = {}
+
+    def _device_consts(self, spec):
+        got = self._spec_consts.get(id(spec))
+        if got is None:
+            mean = None if spec.mean is None else torch.from_numpy(spec.mean).to(self.device).contiguous()
+            roww = None if spec.row_weights is None else torch.from_numpy(spec.row_weights).to(self.device).contiguous()
+            got = self._spec_consts[id(spec)] = (mean, roww, spec)
+        return got[0], got[1]
+
+    def _metric_passes(self, o, yp, yt, phase=False):
+        """The metric columns of output o that the loss kernel did not fill: one dlwp_loss_metrics pass, then the LossSpec
+        metrics (no gradient)."""
+        from . import ops
+        row = self._loss_out[o]
+        if self._metric_mask:
+            ops.loss_metrics(yp, yt, row[7:7 + ops.metric_columns(self._metric_mask)], self._metric_mask, phase=phase,
+                             ws_key=o)
+        for c, ms in self._spec_metrics:
+            mean, roww = self._device_consts(ms)
+            yp4, yt4 = self._as4(yp, roww), self._as4(yt, roww)
+            if roww is not None and roww.numel() != yp4.shape[2]:
+                raise ValueError('latitude weights have %d rows, the model output %d' % (roww.numel(), yp4.shape[2]))
+            if mean is not None and mean.numel() != yp4[0].numel():
+                raise ValueError('anomaly_correlation_loss mean has %d elements, the model output %d per sample'
+                                 % (mean.numel(), yp4[0].numel()))
+            if ms.kind == 0 and ms.inner:
+                ops.loss_elementwise(yp4, yt4, row[c:c + 1], None, 1.0, ms.inner, roww, ws_key=('metric', o, c))
+            else:
+                ops.loss_custom(yp4, yt4, row[c:c + 7], None, 1.0, mean, roww, ms.kind, ms.regularize)
+
+    @staticmethod
+    def _as4(y, roww=None):
+        if y.dim() == 4:
+            return y
+        if roww is not None:
+            raise NotImplementedError('latitude-weighted losses need (n, c, h, w) outputs')
+        return y.reshape(y.shape[0], -1, 1, 1)
 
     # -- replicas ------------------------------------------------------------------------------------------------------ #
     def sync_parameters(self):
@@ -310,7 +432,8 @@ class Trainer(object):
         return cache
 
     def _forward_loss(self, x, ys, want_grad, weight_scale=1.0, prep=None):
-        """Returns (outs, loss table [n_out, 7] on device: col 0 custom-loss value, 1 mse, 2 mae, dys or None)."""
+        """Returns (outs, loss table [n_out, n_cols] on device: col 0 custom / elementwise loss value, 1 mse, 2 mae, the metric
+        columns of _plan_loss_table, dys or None)."""
         from . import ops
         phase = self._phase_outputs()
         skip = tuple(k for k, _, _ in phase.values())
@@ -320,8 +443,12 @@ class Trainer(object):
             outs = self.model.train_executor.run(x, skip_ops=skip, training=want_grad)
         n_out = len(outs)
         if self._loss_out is None or self._loss_out.shape[0] != n_out:
-            self._loss_out = torch.zeros((n_out, 7), dtype=torch.float32, device=self.device)
+            self._loss_out = torch.zeros((n_out, self.n_cols), dtype=torch.float32, device=self.device)
         spec = self.model.loss if self.loss_kind == 'custom' else None
+        ew = self._ew
+        if ew is not None:
+            spec = None
+            ew_rows = None if ew[1] is None else self._device_consts(self.model.loss)[1]
         if spec is not None and self._loss_consts is None:
             mean = None if spec.mean is None else torch.from_numpy(spec.mean).to(self.device).contiguous()
             roww = None if spec.row_weights is None else torch.from_numpy(spec.row_weights).to(self.device).contiguous()
@@ -337,12 +464,23 @@ class Trainer(object):
                 db = None
                 if want_grad and lay.bias is not None and lay.activation == 'linear':     # db = the sums of dz: same pass
                     db = torch.empty(yph.shape[1], dtype=torch.float32, device=self.device)
-                ops.mse_mae_phase(yph, yt.reshape((yph.shape[0], yph.shape[1] // 4, 2 * yph.shape[2], 2 * yph.shape[3])),
-                                  self._loss_out[o, 1:3], dz, db, lw, ws_key=('mse', o) if prep is not None else None)
+                ytp = yt.reshape((yph.shape[0], yph.shape[1] // 4, 2 * yph.shape[2], 2 * yph.shape[3]))
+                if ew is None:
+                    ops.mse_mae_phase(yph, ytp, self._loss_out[o, 1:3], dz, db, lw, ws_key=('mse', o) if prep is not None else None)
+                else:
+                    if ew_rows is not None and ew_rows.numel() != ytp.shape[2]:
+                        raise ValueError('latitude weights have %d rows, the model output %d' % (ew_rows.numel(), ytp.shape[2]))
+                    ops.loss_elementwise_phase(yph, ytp, self._loss_out[o, 0:1], dz, db, lw * ew[2], ew[0], ew_rows, ws_key=o)
+                self._metric_passes(o, yph, ytp, phase=True)
                 dys.append(_PhaseGrad(d2s.src, conv_k, dz, db) if want_grad else None)
                 continue
             dy = torch.empty_like(yp) if want_grad else None
-            if spec is None:
+            if ew is not None:
+                if ew_rows is not None and ew_rows.numel() != self._as4(yp, ew_rows).shape[2]:
+                    raise ValueError('latitude weights have %d rows, the model output %d' % (ew_rows.numel(), yp.shape[2]))
+                ops.loss_elementwise(self._as4(yp, ew_rows), self._as4(yt, ew_rows), self._loss_out[o, 0:1],
+                                     None if dy is None else self._as4(dy, ew_rows), lw * ew[2], ew[0], ew_rows, ws_key=o)
+            elif spec is None:
                 ops.mse_mae(yp, yt, self._loss_out[o, 1:3], dy, lw, ws_key=('mse', o) if prep is not None else None)
             else:
                 mean, roww = self._loss_consts
@@ -353,7 +491,8 @@ class Trainer(object):
                                      % (mean.numel(), yp[0].numel()))
                 if roww is not None and roww.numel() != yp.shape[2]:
                     raise ValueError('latitude weights have %d rows, the model output %d' % (roww.numel(), yp.shape[2]))
-                ops.loss_custom(yp, yt, self._loss_out[o], dy, lw * spec.scale, mean, roww, spec.kind, spec.regularize)
+                ops.loss_custom(yp, yt, self._loss_out[o, 0:7], dy, lw * spec.scale, mean, roww, spec.kind, spec.regularize)
+            self._metric_passes(o, yp, yt)
             dys.append(dy)
         return outs, self._loss_out, dys
 
@@ -397,7 +536,10 @@ class Trainer(object):
         gradient and bias gradient on the phase channels (ops.mse_mae_phase).  DLWP_PHASE_LOSS=0 keeps the separate passes."""
         if self._phase_out is None:
             found = {}
-            if self.loss_kind != 'custom' and os.environ.get('DLWP_PHASE_LOSS', '1') != '0':
+            # the new loss kinds and the metrics pass read the phase channels in 8-byte pairs: an even phase width (target % 4)
+            extra = self._ew is not None or self._metric_mask
+            if ((self.loss_kind == 'mse' or self._ew is not None) and not self._spec_metrics and
+                    os.environ.get('DLWP_PHASE_LOSS', '1') != '0'):
                 ops_ = self.plan.ops
                 for k, op in enumerate(ops_):
                     if op.kind != 'd2s' or op.dst >= 0 or op.dst == P.STATE_IN or op.out_c_off != 0:
@@ -408,7 +550,7 @@ class Trainer(object):
                     store = self.plan.output_store[o] if 0 <= o < len(self.plan.output_store) else None
                     if (len(writers) == 1 and not readers and ops_[writers[0]].kind == 'conv' and
                             ops_[writers[0]].wparam is not None and store is not None and store[0] == op.xs[0] and
-                            sum(1 for w in ops_ if w.dst == op.dst) == 1):
+                            sum(1 for w in ops_ if w.dst == op.dst) == 1 and not (extra and store[2] % 4)):
                         found[o] = (k, op, writers[0])
             self._phase_out = found
         return self._phase_out
@@ -446,13 +588,22 @@ class Trainer(object):
         n_out = v.shape[0]
         if self.loss_kind == 'custom':
             per_out = [float(self.model.loss.scale * v[o, 0]) for o in range(n_out)]
+        elif self.loss_kind == 'elementwise':
+            per_out = [float(v[o, 0]) for o in range(n_out)]
         else:
             per_out = [float(v[o, 1]) for o in range(n_out)]
         total = float(sum(w * l for w, l in zip(self.loss_weights, per_out))) + (self._regularizer_loss() if reg is None else reg)
-        col = {'mean_squared_error': 1, 'mean_absolute_error': 2}
+
+        def metric(o, how):
+            if how[0] == 'col':
+                return float(v[o, how[1]])
+            if how[0] == 'acc':      # mse - mean(p t) / sqrt(mean(p^2) mean(t^2))
+                c = how[2]
+                return float(v[o, how[1]] - v[o, c] / np.sqrt(v[o, c + 1] * v[o, c + 2]))
+            return float(how[2].scale * v[o, how[1]])
         if n_out == 1:
-            return [total] + [float(v[0, col[k]]) for k in self.metric_keys]
-        return ([total] + per_out + [float(v[o, col[k]]) for o in range(n_out) for k in self.metric_keys])
+            return [total] + [metric(0, how) for how in self._metric_cols]
+        return ([total] + per_out + [metric(o, how) for o in range(n_out) for how in self._metric_cols])
 
     #: side streams of the weight gradients (DLWP_SIDE_STREAMS).  With the loader's copy stream and the main stream that is four -- the
     #: hardware queues a process has by default
@@ -1023,24 +1174,35 @@ class Trainer(object):
             else:
                 ops.sgd_keras(self.flat_params, self.opt_state[0], self.flat_grads, 0, opt.lr, opt.momentum, 0.0, 1.0)
             return outs_, loss_, dys_
-        with torch.cuda.use_mem_pool(pool, device=self.device):
-            _lib.check(_lib.lib.dlwp_train_step_record_begin(h, ctypes.c_void_p(main.cuda_stream)))
-            try:
-                outs, loss_vals, dys = body(gx, gys)
-            except BaseException:
-                _lib.lib.dlwp_train_step_record_abort(h)
-                raise
-            ins = [gx] + gys
-            if self._foreign or len(ins) > 8:
-                _lib.lib.dlwp_train_step_record_abort(h)
-                return {'refused': True, 'loss': loss_vals}
-            step = ctypes.c_void_p()
-            dst = (ctypes.c_void_p * len(ins))(*[t.data_ptr() for t in ins])
-            floats = (ctypes.c_size_t * len(ins))(*[t.numel() for t in ins])
-            rc = _lib.lib.dlwp_train_step_create(h, len(ins), dst, floats, ctypes.byref(step))
-            if rc == _lib.EUNSUPPORTED:          # an entry point without a tape record ran inside the step: the shape stays eager
-                return {'refused': True, 'loss': loss_vals, 'why': _lib.lib.dlwp_last_error().decode('utf-8', 'replace')}
-            _lib.check(rc)
+        # No garbage collection while recording (as in _capture_step): a cycle that finalises an OLD model's memory pool, graphs or
+        # streams inside this pool's use_mem_pool block aborts the process ('Fatal Python error: Aborted ... Garbage-collecting'
+        # under dlwp_stream_wait).
+        import gc
+        gc.collect()
+        gc_was_on = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.cuda.use_mem_pool(pool, device=self.device):
+                _lib.check(_lib.lib.dlwp_train_step_record_begin(h, ctypes.c_void_p(main.cuda_stream)))
+                try:
+                    outs, loss_vals, dys = body(gx, gys)
+                except BaseException:
+                    _lib.lib.dlwp_train_step_record_abort(h)
+                    raise
+                ins = [gx] + gys
+                if self._foreign or len(ins) > 8:
+                    _lib.lib.dlwp_train_step_record_abort(h)
+                    return {'refused': True, 'loss': loss_vals}
+                step = ctypes.c_void_p()
+                dst = (ctypes.c_void_p * len(ins))(*[t.data_ptr() for t in ins])
+                floats = (ctypes.c_size_t * len(ins))(*[t.numel() for t in ins])
+                rc = _lib.lib.dlwp_train_step_create(h, len(ins), dst, floats, ctypes.byref(step))
+                if rc == _lib.EUNSUPPORTED:          # an entry point without a tape record ran inside the step: the shape stays eager
+                    return {'refused': True, 'loss': loss_vals, 'why': _lib.lib.dlwp_last_error().decode('utf-8', 'replace')}
+                _lib.check(rc)
+        finally:
+            if gc_was_on:
+                gc.enable()
         keep = (outs, loss_vals, dys, dict(ops._workspaces), dict(ops._workspaces2),
                 self.model.train_executor.scratch(int(x.shape[0])), self.model.train_executor.phase_buffers(),
                 self._prep_cache.get(int(x.shape[0])), self._side, pool)
@@ -1311,7 +1473,8 @@ class Trainer(object):
             for bi, (X, y, n_glob) in enumerate(batches_fn(epoch)):      # X, y: this rank's rows of a batch of n_glob
                 self._call(cbs, 'on_batch_begin', bi, {'batch': bi, 'size': n_glob})
                 lv, reg = self.train_on_shard(X, y, n_glob, return_device=True)
-                if self.loss_kind != 'custom' and lv.is_cuda and lv.dtype == torch.float32 and lv.is_contiguous():
+                if (self.loss_kind != 'custom' and not self._batch_stat and lv.is_cuda and lv.dtype == torch.float32 and
+                        lv.is_contiguous()):
                     from . import ops
                     if acc is None:
                         acc = torch.zeros_like(lv)
@@ -1479,7 +1642,7 @@ class Trainer(object):
 
     def evaluate(self, x, y, batch_size=None, verbose=1, as_list=False):
         batch_size = int(batch_size or 32)
-        if self.loss_kind != 'custom':           # per-element means do not depend on it; larger chunks fill the GPU.
+        if self.loss_kind != 'custom' and not self._batch_stat:   # per-element means do not depend on it; larger chunks fill the GPU.
             batch_size = max(batch_size, 256)    # The anomaly-correlation loss is a whole-batch statistic: keep Keras' batches
         n = x.shape[0]
         ys = list(y) if isinstance(y, (list, tuple)) else [y]

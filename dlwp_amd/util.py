@@ -90,7 +90,10 @@ def load_model(file_name, history=False, custom_objects=None, gpus=1):
     from . import serialization
     with open('%s.pkl' % file_name, 'rb') as f:
         model = pickle.load(f)
-    net = serialization.load_model_file('%s.keras' % file_name, custom_objects=custom_objects)
+    # the reference registers every class and function of DLWP.custom (DLWP/util.py:171-174); the caller's objects come first
+    from . import custom
+    package = {k: v for k, v in vars(custom).items() if not k.startswith('_') and callable(v)}
+    net = serialization.load_model_file('%s.keras' % file_name, custom_objects=custom_objects, package_objects=package)
     model.base_model = net
     model.model = net
     model.gpus = gpus

@@ -371,6 +371,41 @@ size_t dlwp_loss_workspace(dlwp_handle_t, int n, int c);
 int    dlwp_loss_custom(dlwp_handle_t, const void* y_pred, const void* y_true, int n, int c, int h, int w,
                         const void* mean, const void* row_weights, int kind, int regularize, void* stats7, void* dy,
                         float loss_weight, void* ws, size_t ws_bytes, int dtype, void* stream);
+/* the remaining Keras 2.2 regression losses (keras/losses.py; csrc/losses.hip), x = yp - yt, eps = K.epsilon() = 1e-7, means over
+ * all N = n*c*h*w elements; g = d(element value)/d yp, the gradient is g / N:
+ *   DLWP_LOSS_MSE      x^2                                                        g = 2x
+ *   DLWP_LOSS_MAE      |x|                                                        g = sign(x) (0 at x = 0)
+ *   DLWP_LOSS_MAPE     100 |x| / max(|yt|, eps)                                   g = 100 sign(x) / max(|yt|, eps)
+ *   DLWP_LOSS_MSLE     (log1p(max(yp, eps)) - log1p(max(yt, eps)))^2             g = 2 (a - b) / (max(yp, eps) + 1), 0 where yp < eps
+ *   DLWP_LOSS_LOGCOSH  |x| + log1p(exp(-2|x|)) - log 2  (= x + softplus(-2x) - log 2)   g = tanh(x)
+ * dlwp_loss_elementwise: y (n, c, h, w); row_weights (h floats, nullable): the literal latitude weighting loss(w*yt, w*yp) of
+ *   DLWP.custom (custom.py:899-991) with w[row] on both operands; out1 (device, 1 float) <- the mean; dy (nullable) <- loss_weight
+ *   * dL/dyp = loss_weight * w * g(w yp, w yt) / N.  ws >= dlwp_loss_elementwise_workspace() bytes.
+ * dlwp_loss_elementwise_phase: the same on the PHASE channels of a restated output layer (y_phase (n, 4f, h, w) against y_true
+ *   (n, f, 2h, 2w), layout as dlwp_mse_mae_phase; w even, y_true 16-byte and the phase tensors 8-byte aligned); dz_phase / db4f (nullable) as there, row
+ *   weights indexed by the OUTPUT row.  The bias sums join dlwp_reductions_begin / _flush like dlwp_bias_grad's.
+ * dlwp_loss_metrics: one pass over (yp, yt) for the metrics of one output; mask = OR of (1 << DLWP_LOSS_*) and
+ *   DLWP_METRIC_ACC_SUMS; out <- the selected means in this order: mse, mae, mape, msle, logcosh, then (ACC sums) mean(yp yt),
+ *   mean(yp^2), mean(yt^2).  phase != 0: y_pred is in phase layout and (n, c, h, w) is the target's shape (w % 4 == 0).
+ *   ws >= dlwp_loss_metrics_workspace() bytes.
+ * Fixed reduction trees, no atomics: bit-reproducible.                                                                      */
+#define DLWP_LOSS_MSE     0
+#define DLWP_LOSS_MAE     1
+#define DLWP_LOSS_MAPE    2
+#define DLWP_LOSS_MSLE    3
+#define DLWP_LOSS_LOGCOSH 4
+#define DLWP_METRIC_ACC_SUMS 0x20u
+size_t dlwp_loss_elementwise_workspace(dlwp_handle_t);
+int    dlwp_loss_elementwise(dlwp_handle_t, const void* y_pred, const void* y_true, int n, int c, int h, int w,
+                             const void* row_weights, int kind, void* out1, void* dy, float loss_weight, void* ws,
+                             size_t ws_bytes, int dtype, void* stream);
+size_t dlwp_loss_elementwise_phase_workspace(int f);
+int    dlwp_loss_elementwise_phase(dlwp_handle_t, const void* y_phase, const void* y_true, int n, int f, int h, int w,
+                                   const void* row_weights, int kind, void* out1, void* dz_phase, void* db4f, float loss_weight,
+                                   void* ws, size_t ws_bytes, int dtype, void* stream);
+size_t dlwp_loss_metrics_workspace(dlwp_handle_t);
+int    dlwp_loss_metrics(dlwp_handle_t, const void* y_pred, const void* y_true, int n, int c, int h, int w, int phase,
+                         unsigned mask, void* out, void* ws, size_t ws_bytes, int dtype, void* stream);
 int    dlwp_adam_keras(dlwp_handle_t, void* p, void* m, void* v, const void* g, size_t n, float lr, float beta_1,
                        float beta_2, float epsilon, float decay, long long iteration, float grad_scale, void* stream);
 /* dlwp_adam_keras for a training step captured as a hipGraph: the step number is read from (and advanced in) device memory
