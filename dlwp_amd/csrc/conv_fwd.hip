@@ -794,6 +794,30 @@ int wino2s_grid(dlwp_handle_t h, const ConvArgs& a, const dlwp_conv2d* cd, const
   return (int)(items < slots ? items : slots);
 }
 
+// conv_fwd_wino_flat.hip instead of the chosen 8 x 32 Winograd instance?  Returns the runs of 64 tiles per image (0: no).  The flat
+// kernel multiplies no padded tile rectangles (22 x 45 source maps: 1024 tile slots per image for 990 tiles instead of 1152, 256 for
+// 253 instead of 288 as sample pairs) and gives the same bits, so the choice may depend on the batch: DLWP_OPT_WINO_FLAT 1 takes it
+// from one workgroup per CU on (below that a run's longer rows are not paid back by a full chip), 2 always.  Split-K launches, forced
+// configurations and pair-fused launches keep their instance.  *bnf: output-channel fragments per workgroup -- 4 (64 channels) on an
+// up-sampled source whenever Cout allows, whatever the rectangle instance had: the 32-channel form of that variant holds 56 KB of LDS
+// (two workgroups per CU, where the rectangle instance's source-resolution fetch fits three) and measured no faster than the
+// rectangle at 128 members (317 vs 313 us), while the 64-channel form fills the same two slots with twice the matrix work per
+// staged row.  The channel tiling does not change a bit: every (tile, channel) sum runs in the same order.
+int wino_flat_runs(dlwp_handle_t h, const ConvArgs& a, const dlwp_conv2d* cd, const LaunchPlan& lp, int* bnf) {
+  if (h->opt.wino_flat == 0 || h->opt.forced_cfg >= 0 || lp.primary < 0 || lp.narrow >= 0 || lp.ksplit > 1) return 0;
+  const ConvKernelEntry& e = registry().entries[lp.primary];
+  if (!is_wino(e) || e.split || e.dil != 1 || e.th != 8 || e.tw != 32 || e.waves != 4 || e.ck != 8 || cd->dil_h != 1 ||
+      cd->dil_w != 1 || cd->kh != 3 || cd->kw != 3)
+    return 0;
+  const int fb = (a.src_mode == DLWP_SRC_UPSAMPLE2 && a.Cout % 64 == 0) ? 4 : e.bnf;
+  const int runs = dlwp_conv_wino_flat_runs(a, fb);
+  if (runs <= 0) return 0;
+  const long long grid = (long long)a.N * runs * (a.Cout / (16 * fb));
+  if (grid >= (1ll << 31) || (h->opt.wino_flat == 1 && grid < h->cu_count)) return 0;
+  *bnf = fb;
+  return runs;
+}
+
 }  // namespace (second part)
 
 int dlwp_launch_conv2d(dlwp_handle_t h, const void* x, const void* w, const void* bias, void* y, dlwp_shape4 xs,
@@ -938,6 +962,19 @@ int dlwp_launch_conv2d(dlwp_handle_t h, const void* x, const void* w, const void
       a.ksplit <= 1 && !a.in_bf16 && !a.yact && !a.y2 && !lstm &&
       dlwp_pair_stash_fwd(h, a, wino_skips_row2(a) ? 1 : 0, (int)grid, e.launch, s))
     return DLWP_OK;
+  if (!lstm && !act_epi && !y_pool) {
+    int fb = 0;
+    if (const int runs = wino_flat_runs(h, a, cd, lp, &fb)) {   // runs of 64 consecutive tiles instead of 8 x 32 rectangles (same bits)
+      a.pair_vw = 0;
+      a.tiles_w = (a.Wo + 1) / 2;
+      a.tiles_h = runs;
+      a.cout_tiles = a.Cout / (16 * fb);
+      if (dlwp_conv_wino_flat_launch(a, fb, a.N * runs * a.cout_tiles, s) != 0)
+        DLWP_FAIL(DLWP_EHIP, "dlwp_conv2d_fwd: hipFuncSetAttribute failed");
+      DLWP_LAUNCH_CHECK("conv2d_fwd_wino_flat_f32");
+      return DLWP_OK;
+    }
+  }
   if (is_wino(e) && !e.split && lp.narrow < 0 && !lstm && wino_edge_pairs(a, e.dil, e.th, e.tw, e.waves, e.bnf)) {
     a.edge_pairs = 1;     // the last tile row's blocks take two column tiles each (WinoCfg::EP); a launch that was handed over to a
                           // pair (above) keeps the plain grid: the fused kernel runs the plain body
@@ -1443,6 +1480,14 @@ int dlwp_conv2d_launch_info(dlwp_handle_t h, dlwp_shape4 xs, const dlwp_conv2d* 
   if (const int sg = wino2s_grid(h, a, cd, lp)) {   // config -3: conv_fwd_wino2s.hip -- the instance's matrix work, 2 workgroups per CU
     const long long g832 = (long long)dlwp_ceil_div(a.Ho, 8) * dlwp_ceil_div(a.Wo, 32) * dlwp_ceil_div(a.Cout, 16) * a.N;
     out2[0] = dlwp_launch_info{-3, sg, 512, 2.0 * 64.0 * 16.0 * 16.0 * 8.0 * ((a.Cin + 7) / 8) * (double)g832, 0, 0};
+    *n_launches = 1;
+    return DLWP_OK;
+  }
+  int fb = 0;
+  if (const int runs = wino_flat_runs(h, a, cd, lp, &fb)) {   // config -4: conv_fwd_wino_flat.hip -- the same matrix work per tile slot
+    const long long g = (long long)a.N * runs * (a.Cout / (16 * fb));
+    const double mfmas = 4.0 * (wino_skips_row2(a) ? 9.0 : 16.0) * fb * (dlwp_ceil_div(a.Cin, 8) * 2.0) * (double)g;   // waves x
+    out2[0] = dlwp_launch_info{-4, (int)g, 256, 2048.0 * mfmas, 0, 0};          // positions x fragments x k steps x workgroups
     *n_launches = 1;
     return DLWP_OK;
   }

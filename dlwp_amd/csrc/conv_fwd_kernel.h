@@ -656,4 +656,7 @@ void dlwp_conv_few_launch(const ConvArgs& a, int dil, int grid, hipStream_t s);
 // conv_fwd_wino2s.hip: the streaming form of the position-split Winograd kernel for 16-output-channel blocks
 bool dlwp_conv_wino2s_covers(const ConvArgs& a);
 int dlwp_conv_wino2s_launch(const ConvArgs& a, int grid, hipStream_t s);
+// conv_fwd_wino_flat.hip: the 8 x 32 Winograd kernel on runs of 64 consecutive tiles (no padded tile rectangles; same bits)
+int dlwp_conv_wino_flat_runs(const ConvArgs& a, int bnf);
+int dlwp_conv_wino_flat_launch(const ConvArgs& a, int bnf, int grid, hipStream_t s);
 

@@ -52,6 +52,9 @@ struct WinoCfg {
   // and the store phase sends staged rows 4-7 to rows 0-3 of the second tile.  Same arithmetic on the same operands: the same bits.
   // The grid counts tiles_w (tiles_h - 1) + ceil(tiles_w / 2) blocks per image and channel tile (host: wino_edge_pairs).
   static constexpr bool EP = EP_;
+  // FLAT: a run of 64 consecutive 2x2 tiles in row-major order instead of an 8 x 32 rectangle (WinoFlatCfg, conv_fwd_wino_flat.hip;
+  // never set by this template)
+  static constexpr bool FLAT = false;
   static_assert(!EP_ || (DIL_ == 1 && TH_ == 8 && TW_ == 32 && WAVES_ == 4 && !IN16_ && !DACT_ && !POOL2_ && !SPLITK_ && !UPSQ_),
                 "edge pairs: the 8 x 32 four-wave float32 instances, plain / pooled epilogues, element-wise or column-pair loader");
   static constexpr int LRE = EP_ ? 2 * (TH_ / 2 + 2 * DIL_) : TH_ + 2 * DIL_;   // LDS rows of a channel's input tile
@@ -169,7 +172,16 @@ __device__ __forceinline__ void conv2d_fwd_wino_body(const ConvArgs& a, const in
   const int cin_l = C::SPLITK ? min(a.Cin - c_base, a.kchunks * C::CK) : a.Cin;                 // ... and how many it multiplies
   int tw, th;
   bool ep = false;      // (uniform) this block is an edge pair: the valid half of column tiles tw and tw + 1 of the last tile row
-  if constexpr (C::EP) {
+  // FLAT: run `run` of a.tiles_h per image; a.tiles_w 2x2 tiles per tile row, ftiles per image; ft0 = the run's first tile, fr0 its row
+  [[maybe_unused]] const int ftiles = ((a.Ho + 1) >> 1) * a.tiles_w;
+  [[maybe_unused]] int ft0 = 0, fr0 = 0;
+  if constexpr (C::FLAT) {
+    const int run = L % a.tiles_h;
+    L /= a.tiles_h;
+    ft0 = run * C::T;
+    fr0 = ft0 / a.tiles_w;
+    th = tw = 0;
+  } else if constexpr (C::EP) {
     const int full = a.tiles_w * (a.tiles_h - 1), per = full + ((a.tiles_w + 1) >> 1);
     const int t = L % per;
     L /= per;
@@ -215,6 +227,19 @@ __device__ __forceinline__ void conv2d_fwd_wino_body(const ConvArgs& a, const in
 #pragma unroll
   for (int q = 0; q < C::NPOS; ++q) {
     int s = tid + q * C::NT;
+    if constexpr (C::FLAT) {
+      // whole rows: LDS row lr, column lc = image row 2 fr0 - 1 + lr (up-sampled source: SOURCE row fr0 - 1 + lr) and column lc - 1
+      // (0 ... NCOL - 1: columns -1 ... NCOL - 2); a plain column sits in slot lc, a source column in slots 2 lc + 1 and 2 lc + 2
+      if (q == C::NPOS - 1 && s >= C::LR * C::NCOL) s = 0;
+      const int lr = s / C::NCOL, lc = s - lr * C::NCOL;
+      const int rs = C::UPS ? dlwp_map_coord_tile(fr0 - 1 + lr, a.Hs, a.mode_h) : dlwp_map_coord_tile(2 * fr0 - a.pad_top + lr, a.H, a.mode_h);
+      const int cs = C::UPS ? dlwp_map_coord_tile(lc - 1, a.Ws, a.mode_w) : dlwp_map_coord_tile(lc - a.pad_left, a.W, a.mode_w);
+      goff[q] = (rs >= 0 && cs >= 0) ? (unsigned)(rs * a.Ws + cs) * 4u : 0x7ffffff0u;
+      loff[q] = lr * C::LCP + (C::UPS ? 2 * lc + 1 : lc);
+      loff1[q] = loff[q] + 1;            // (UPS: the second slot; opaque for the reason given under PAIRX)
+      asm volatile("" : "+v"(loff1[q]));
+      continue;
+    }
     if constexpr (C::PAIRX) {
       if (q == C::NPOS - 1 && s >= (ep ? C::LRE : C::LR) * C::NPAIR) s = 0;
       int lr = s / C::NPAIR;
@@ -271,7 +296,15 @@ __device__ __forceinline__ void conv2d_fwd_wino_body(const ConvArgs& a, const in
 
   // ---- this lane's tile (= its MFMA A-operand row) and the LDS offset of the tile's 4x4 patch origin, channel l>>4
   int v_src;
-  {
+  if constexpr (C::FLAT) {
+    // tile g of the image: tile row g / tiles_w (LDS row 2 (row - fr0); up-sampled source: the patch's source rows are LDS rows
+    // row - fr0 + {0, 1, 1, 2}, see vt_read), tile column tc: LDS column 2 tc (up-sampled: up-sampled column 2 tc - 1 = slot 2 tc + 2).
+    // Tiles past the image compute tile ft0 again and are not stored.
+    int g = ft0 + wave * 16 + (lane & 15);
+    if (g >= ftiles) g = ft0;
+    const int tr = g / a.tiles_w, tc = g - tr * a.tiles_w;
+    v_src = (lane >> 4) * C::PS + (C::UPS ? (tr - fr0) : 2 * (tr - fr0)) * C::LCP + 2 * tc + (C::UPS ? 2 : 0);
+  } else {
     const int t = wave * 16 + (lane & 15);
     const int tt = t < C::T ? t : 0;
     const int pc = tt / (C::RTH * C::RTW), rem = tt - pc * (C::RTH * C::RTW);
@@ -339,7 +372,10 @@ __device__ __forceinline__ void conv2d_fwd_wino_body(const ConvArgs& a, const in
   };
   auto stage_x = [&](int xdst, int i) {
     const int ci = i / C::NPOS, q = i - ci * C::NPOS;
-    if constexpr (C::PAIRX) {   // (two 4-byte writes: the pair starts on an odd float)
+    if constexpr (C::FLAT && C::UPS) {   // a source element into the two column slots it replicates into
+      lds[xdst + ci * C::PS + loff[q]] = xr[ci][q];
+      lds[xdst + ci * C::PS + loff1[q]] = xr[ci][q];
+    } else if constexpr (C::PAIRX) {   // (two 4-byte writes: the pair starts on an odd float)
       lds[xdst + ci * C::PS + loff[q]] = xr[ci][2 * q];
       lds[xdst + ci * C::PS + loff1[q]] = xr[ci][2 * q + 1];
     } else
@@ -367,7 +403,8 @@ __device__ __forceinline__ void conv2d_fwd_wino_body(const ConvArgs& a, const in
   auto vt_read = [&](int xsrc, int c4, int part) {  // 8 parts: row part/2, columns 2*(part%2) and +1 (one ds_read_b64)
     const float* dp = lds + xsrc + v_src + c4 * 4 * C::PS;
     const int r = part >> 1, h = part & 1;
-    d2[r][h] = *(const f32x2*)(dp + r * C::LCP + 2 * h);
+    // (FLAT, up-sampled source: the LDS holds source rows -- patch rows 1 and 2 are the same one)
+    d2[r][h] = *(const f32x2*)(dp + (C::FLAT && C::UPS ? r - (r >> 1) : r) * C::LCP + 2 * h);
   };
   auto vt_rows = [&](int r) {  // d B, one patch row: (d0 - d2, d1 + d2 | d2 - d1, d1 - d3)
     t2[r][0] = pk_wino_t01(d2[r][0], d2[r][1]);
@@ -486,7 +523,7 @@ __device__ __forceinline__ void conv2d_fwd_wino_body(const ConvArgs& a, const in
       }
       if constexpr (C::UPSQ) {  // chunk k+2 -> registers: the NQ loads, one every second step (their registers are free from s = 24)
         if (s >= 24 && s < 24 + 2 * C::NQ && (s & 1) == 0) load_q(c0 + 2 * C::CK, (s - 24) >> 1);
-      } else if (s >= 24) {  // chunk k+2 -> registers (first third)
+      } else if (s >= 24 && (!C::FLAT || s < 32)) {  // chunk k+2 -> registers (first third; FLAT with BNF 4: in 8 steps as well)
 #pragma unroll
         for (int i = (s - 24) * C::NXI / 24; i < (s - 23) * C::NXI / 24; ++i) load_x(c0 + 2 * C::CK, i);
       }
@@ -629,7 +666,7 @@ __device__ __forceinline__ void conv2d_fwd_wino_body(const ConvArgs& a, const in
     auto y_odd = [&](const f32x2 (&s)[2][4], int aa) -> f32x2 {
       return C::UPS ? pk_sub(s[aa][1], s[aa][3]) : pk_sub(pk_sub(s[aa][1], s[aa][2]), s[aa][3]);
     };
-    if constexpr (C::DIL == 1) {
+    if constexpr (C::DIL == 1 && !C::FLAT) {   // (FLAT: no pooled epilogues -- host)
       if (pool_stage == 2) {  // 2x2 sum: 1^T A^T M A 1 with A 1 = (1, 2, 0, -1) -- row / column 2 of M drop out
         for_tiles([&](const f32x2 (&s)[2][4], int col, f32x2, int ti, int tj, int, int) {
           const f32x2 t0 = pk_add(s[0][0], s[1][0]), t1 = pk_add(s[0][1], s[1][1]), t3 = pk_add(s[0][3], s[1][3]);
@@ -649,7 +686,9 @@ __device__ __forceinline__ void conv2d_fwd_wino_body(const ConvArgs& a, const in
       }
     }
     for_tiles([&](const f32x2 (&s)[2][4], int col, f32x2 bv, int ti, int tj, int pi, int pj) {
-      float* op = lds + col * C::OPS + (ti * 2 * C::DIL + pi) * C::TW + tj * 2 * C::DIL + pj;
+      // (FLAT: staged as [co][row of the tile][tile t = ti RTW + tj of the run][column of the tile])
+      float* op = C::FLAT ? lds + col * C::OPS + 2 * (ti * C::RTW + tj)
+                          : lds + col * C::OPS + (ti * 2 * C::DIL + pi) * C::TW + tj * 2 * C::DIL + pj;
       f32x2 pmax = (f32x2){0.f, 0.f};
 #pragma unroll
       for (int aa = 0; aa < 2; ++aa) {
@@ -659,7 +698,7 @@ __device__ __forceinline__ void conv2d_fwd_wino_body(const ConvArgs& a, const in
           const f32x2 m = (f32x2){fmaxf(y0.x, y1.x), fmaxf(y0.y, y1.y)};
           pmax = aa == 0 ? m : (f32x2){fmaxf(pmax.x, m.x), fmaxf(pmax.y, m.y)};
         }
-        float* q = op + aa * C::DIL * C::TW;
+        float* q = op + aa * (C::FLAT ? 2 * C::T : C::DIL * C::TW);
         if constexpr (C::DIL == 1) {
           // the pair's four outputs of this row are adjacent: ONE 16-byte write (r3).  Four 4-byte writes put all 64 lanes of
           // an instruction on the 8 banks = 0 (mod 4) -- the plane stride OPS = 4 (mod 32) spreads the 16 channels of a lane
@@ -679,6 +718,37 @@ __device__ __forceinline__ void conv2d_fwd_wino_body(const ConvArgs& a, const in
   DLWP_STAMP(4);
   __syncthreads();
   DLWP_STAMP(5);
+  if constexpr (C::FLAT) {
+    // ---- stores of a run: thread = (channel parity cb, tile row aa, tile t); pass k = channels cb + 2 k (a scalar offset).  A wave
+    //      writes one output row's outputs of its 64 tiles: the run's row segments, in 8-byte pieces (even width) or elements (odd
+    //      width: the rows are not 8-byte aligned; the column past an odd width is dropped)
+    static_assert(C::NT == 4 * C::T, "one thread per (channel parity, tile row, tile)");
+    const int t = tid & (C::T - 1), aa = (tid / C::T) & 1, cb = tid / (2 * C::T);
+    const int g = ft0 + t, tr = g / a.tiles_w, tc = g - tr * a.tiles_w;
+    const int oh = 2 * tr + aa, ow = 2 * tc;
+    const unsigned plane_b = (unsigned)(a.Ho * a.Wo) * 4u;
+    float* yb = a.y + ((long long)n * a.out_c_total + a.out_c_off + n0) * a.Ho * a.Wo;
+    const __amdgpu_buffer_rsrc_t y_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)yb, 0, (unsigned)C::BN * plane_b, 0x00020000);
+    const bool ok = g < ftiles && oh < a.Ho;
+    const unsigned pix = (unsigned)(oh * a.Wo + ow) * 4u + (unsigned)cb * plane_b;
+    const unsigned v0 = ok ? pix : 0x7ffffff0u, v1 = (ok && ow + 1 < a.Wo) ? pix + 4u : 0x7ffffff0u;
+    const float* lp = lds + cb * C::OPS + aa * 2 * C::T + 2 * t;
+    if ((a.Wo & 1) == 0) {
+#pragma unroll
+      for (int k = 0; k < C::BN / 2; ++k)
+        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, *(const f32x2*)(lp + 2 * k * C::OPS)), y_rsrc, v0,
+                                              (unsigned)(2 * k) * plane_b, 0);
+    } else {
+#pragma unroll
+      for (int k = 0; k < C::BN / 2; ++k) {
+        const u32x2 o = __builtin_bit_cast(u32x2, *(const f32x2*)(lp + 2 * k * C::OPS));
+        __builtin_amdgcn_raw_buffer_store_b32(o[0], y_rsrc, v0, (unsigned)(2 * k) * plane_b, 0);
+        __builtin_amdgcn_raw_buffer_store_b32(o[1], y_rsrc, v1, (unsigned)(2 * k) * plane_b, 0);
+      }
+    }
+    DLWP_STAMP(6);
+    return;
+  }
   if constexpr (C::SPLITK) {
     // ---- the partial tile leaves as staged, [co][TH x TW] contiguous: slab (tile, split) of BN x TH x TW floats -- private memory,
     //      no bounds, 16-byte stores a wave writes as 1 KB runs.  Then the tile's arrival counter: one atomic per block; the LAST

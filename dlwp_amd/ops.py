@@ -457,6 +457,13 @@ def set_wino_xloader(mask):
     return int(_lib.set_option(_lib.OPT_WINO_XLOADER, int(mask)))
 
 
+def set_wino_flat(mode):
+    """DLWP_OPT_WINO_FLAT: 3x3 float32 Winograd layers of narrow maps run on runs of 64 consecutive tiles (csrc/conv_fwd_wino_flat.hip,
+    launch-info config -4): 0 never, 1 from one workgroup per CU on (default), 2 whenever the layer qualifies.  The same bits
+    whatever the setting.  Returns the previous setting."""
+    return int(_lib.set_option(_lib.OPT_WINO_FLAT, int(mode)))
+
+
 def set_splitk(mode):
     """DLWP_OPT_SPLITK: Winograd launches on small grids divide the input channels over several workgroups per output tile, the
     last arrival sums the partial tiles in index order (csrc/conv_fwd_k3d1s.hip): 0 never (default since r5), 1 by the library's rule,

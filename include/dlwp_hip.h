@@ -157,6 +157,13 @@ int         dlwp_device_info(dlwp_handle_t h, int* cu_count, int* lds_bytes, cha
                                         * valid rows of two neighbouring column tiles each: one block in eighteen less.  7
                                         * (default): all; 0: as before r5 (DLWP_WINO_XLOADER in the environment).  The same
                                         * values reach the same patch positions: identical bits whatever the setting            */
+#define DLWP_OPT_WINO_FLAT          9  /* 3x3 float32 Winograd layers of a narrow map (a plain source of at most 46 columns, an
+                                        * up-sampled one of at most 46 source columns; 'same' halo of zero / periodic / edge) run
+                                        * on runs of 64 consecutive 2x2 tiles instead of 8 x 32 rectangles: no padded tiles
+                                        * multiplied (csrc/conv_fwd_wino_flat.hip, launch-info config -4).  0: never; 1 (default):
+                                        * from one workgroup per CU on; 2: whenever the layer qualifies.  Not with a forced
+                                        * configuration or split-K.  Identical bits whatever the setting (DLWP_WINO_FLAT in the
+                                        * environment)                                                                          */
 int         dlwp_set_option(dlwp_handle_t h, int option, int value, int* previous);
 /* the defaults themselves: what handles created AFTERWARDS start from, and what the handle-less host logic (planner hints
  * called with a NULL handle, e.g. on a machine without a GPU) uses.  Existing handles are not touched.                 */
