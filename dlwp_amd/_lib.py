@@ -32,6 +32,7 @@ SRC_DIRECT, SRC_UPSAMPLE2, SRC_MAXPOOL2 = 0, 1, 2
 OP_CONV2D, OP_PAD2D, OP_MAXPOOL2, OP_UPSAMPLE2, OP_COPYCH, OP_LSTM_GATES, OP_PHASE_WEIGHTS, OP_DEPTH2SPACE = 0, 1, 2, 3, 4, 5, 6, 7
 OP_ROWCONV2D = 8
 OP_BATCHNORM = 9
+OP_DENSE = 10
 BUF_NONE = -1000
 STEP_LANES, STEP_GRAPH, STEP_GRAPH_BRANCHES, STEP_LANES_RECORDED = 0, 1, 2, 3
 
@@ -87,6 +88,17 @@ class BatchNorm(ctypes.Structure):
     """dlwp_batchnorm (include/dlwp_hip.h): shape and hyper-parameters of one BatchNormalization launch"""
     _fields_ = [('n', ctypes.c_int), ('c', ctypes.c_int), ('hw', ctypes.c_int), ('momentum', ctypes.c_float),
                 ('epsilon', ctypes.c_float)]
+
+
+class Dense(ctypes.Structure):
+    """dlwp_dense (include/dlwp_hip.h): samples, input features, units, activation of one Dense launch"""
+    _fields_ = [('m', ctypes.c_int), ('k', ctypes.c_int), ('n', ctypes.c_int), ('act', ctypes.c_int)]
+
+
+class Dropout(ctypes.Structure):
+    """dlwp_dropout (include/dlwp_hip.h): what names one mask -- seed, layer, step -- and how it is applied"""
+    _fields_ = [('seed', ctypes.c_ulonglong), ('layer', ctypes.c_uint), ('step', ctypes.c_uint), ('threshold', ctypes.c_uint),
+                ('scale', ctypes.c_float)]
 
 
 class LaunchInfo(ctypes.Structure):
@@ -232,6 +244,11 @@ _sig('dlwp_batchnorm_workspace', [BatchNorm], _sz)
 _sig('dlwp_batchnorm_fwd_train', [_vp] * 9 + [_vp, _sz, BatchNorm, _vp])
 _sig('dlwp_batchnorm_fwd_infer', [_vp] * 7 + [BatchNorm, _vp])
 _sig('dlwp_batchnorm_bwd', [_vp] * 9 + [_vp, _sz, BatchNorm, _vp])
+_sig('dlwp_dense_fwd', [_vp] * 5 + [Dense, _vp])
+_sig('dlwp_dense_bwd_data', [_vp] * 5 + [Dense, _vp])
+_sig('dlwp_dense_bwd_weight', [_vp] * 6 + [Dense, _vp])
+_sig('dlwp_dropout_fwd', [_vp, _vp, _vp, ctypes.c_longlong, Dropout, _vp])
+_sig('dlwp_dropout_bwd', [_vp, _vp, _vp, ctypes.c_longlong, Dropout, _vp])
 _sig('dlwp_copy_channels', [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp])
 _sig('dlwp_series_merge_time', [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp])
 _sig('dlwp_rollout_workspace_bytes', [_vp, _P(Op), _i, _i], _sz)

@@ -66,6 +66,10 @@ int enqueue_op(dlwp_handle_t h, const dlwp_op& op, const void* src, void* dst, c
       const dlwp_batchnorm d{op.xs.n, op.xs.c, op.xs.h * op.xs.w, 0.f, eps};
       return dlwp_batchnorm_fwd_infer(h, src, dst, w, b, aux[0], aux[1], d, (void*)s);
     }
+    case DLWP_OP_DENSE: {       // keras Dense: xs = (n, k, 1, 1), conv.cout = units, conv.act
+      const dlwp_dense d{op.xs.n, op.xs.c * op.xs.h * op.xs.w, op.conv.cout, op.conv.act};
+      return dlwp_dense_fwd(h, src, w, b, dst, d, (void*)s);
+    }
     case DLWP_OP_COPYCH:
       return dlwp_copy_channels(h, src, dst, op.xs.n, op.xs.c, op.xs.h * op.xs.w, op.conv.in_c_off,
                                 op.conv.in_c_total, op.conv.out_c_off, op.conv.out_c_total, dtype, (void*)s);
@@ -183,7 +187,7 @@ static int create_impl(dlwp_handle_t h, const dlwp_op* plan_in, int n_ops, void*
                    op.src);
     DLWP_CHECK_ARG(op.dst != DLWP_BUF_STATE_IN && op.dst >= DLWP_BUF_OUT(n_outputs - 1) && op.dst < n_buffers,
                    "rollout op %d: dst buffer %d out of range", i, op.dst);
-    if (op.kind == DLWP_OP_CONV2D || op.kind == DLWP_OP_ROWCONV2D)
+    if (op.kind == DLWP_OP_CONV2D || op.kind == DLWP_OP_ROWCONV2D || op.kind == DLWP_OP_DENSE)
       DLWP_CHECK_ARG(op.w >= 0 && op.w < n_buffers && op.b >= -1 && op.b < n_buffers,
                      "rollout op %d: weight/bias buffer out of range", i);
     if (op.kind == DLWP_OP_PHASE_WEIGHTS)
@@ -273,7 +277,7 @@ static int create_impl(dlwp_handle_t h, const dlwp_op* plan_in, int n_ops, void*
       for (int i = 0; i < n_ops && rc == DLWP_OK; ++i) {
         const dlwp_op& op = plan[i];
         if (op.kind == DLWP_OP_PHASE_WEIGHTS) continue;   // done once, at the head of the graph
-        const bool weighted = op.kind == DLWP_OP_CONV2D || op.kind == DLWP_OP_ROWCONV2D;
+        const bool weighted = op.kind == DLWP_OP_CONV2D || op.kind == DLWP_OP_ROWCONV2D || op.kind == DLWP_OP_DENSE;
         const bool bn = op.kind == DLWP_OP_BATCHNORM;
         const void* w = (weighted || (bn && op.w >= 0)) ? buffers[op.w] : nullptr;
         const void* b = ((weighted || bn) && op.b >= 0) ? buffers[op.b] : nullptr;

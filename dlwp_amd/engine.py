@@ -39,6 +39,7 @@ class Executor(object):
         self._phase = None       # derived (phase-summed) kernels of plan.phase_params: [(w2, b2 | None)]
         self._oct = self._octet_buffers() if self._bf16 and os.environ.get('DLWP_BF16_O8', '1') != '0' else set()
         self._bn = {}            # (op index, batch size) -> the batch statistics a training forward keeps for the backward
+        self.dropout_step = 0    # the training step whose masks a training forward draws (Trainer: the optimizer's iteration)
 
     # -- buffers ----------------------------------------------------------------------------------------------------- #
     def scratch(self, n):
@@ -287,7 +288,15 @@ class Executor(object):
             elif op.kind == 'upsample':
                 ops.upsample2(src, out=dst)
             elif op.kind == 'copy':
+                if tuple(dst.shape[2:]) != tuple(src.shape[2:]) and dst.numel() == src.numel():
+                    dst = dst.view(src.shape)          # a Reshape relabelled the target: the same contiguous block
                 ops.copy_channels(src, dst, op.xs[0], op.in_c_off, op.out_c_off)
+            elif op.kind == 'dense':
+                ops.dense_fwd(src, op.layer.kernel, op.layer.bias, op.act, out=dst)
+            elif op.kind == 'dropout':         # (training plans only; outside a training step: rate 0 = a copy)
+                lay = op.layer
+                ops.dropout_fwd(src, lay.rate if training else 0.0, lay.mask_seed, self.plan.dropout_layers.index(lay),
+                                self.dropout_step, out=dst)
             elif op.kind == 'bn':
                 lay = op.layer
                 if training:
@@ -431,6 +440,12 @@ class Executor(object):
             table.append(lay.kernel)
             if lay.bias is not None:
                 table.append(lay.bias)
+        didx = {}                                  # Dense: kernel, bias (index | -1)
+        for lay in self.plan.dense_layers:
+            didx[id(lay)] = (len(table), len(table) + 1 if lay.bias is not None else -1)
+            table.append(lay.kernel)
+            if lay.bias is not None:
+                table.append(lay.bias)
         bidx = {}                                  # BatchNormalization: gamma, beta, moving mean, moving variance (index | -1)
         for lay in self.plan.bn_layers:
             ent = []
@@ -448,7 +463,7 @@ class Executor(object):
         kind = {'conv': _lib.OP_CONV2D, 'pad': _lib.OP_PAD2D, 'maxpool': _lib.OP_MAXPOOL2,
                 'upsample': _lib.OP_UPSAMPLE2, 'copy': _lib.OP_COPYCH, 'lstm': _lib.OP_LSTM_GATES,
                 'phasew': _lib.OP_PHASE_WEIGHTS, 'd2s': _lib.OP_DEPTH2SPACE, 'rowconv': _lib.OP_ROWCONV2D,
-                'bn': _lib.OP_BATCHNORM}
+                'bn': _lib.OP_BATCHNORM, 'dense': _lib.OP_DENSE}
         arr = (_lib.Op * len(self.plan.ops))()
         for k, (op, d) in enumerate(zip(self.plan.ops, self._descriptors())):
             o = arr[k]
@@ -483,6 +498,9 @@ class Executor(object):
                 o.xs = _lib.Shape4(n, op.xs[0], 1, 1)
             elif op.kind == 'd2s':
                 o.conv.out_c_off, o.conv.out_c_total = op.out_c_off, op.out_c_total
+            elif op.kind == 'dense':
+                o.w, o.b = didx[id(op.layer)]
+                o.conv.cout, o.conv.act = op.layer.units, op.act
             elif op.kind == 'bn':                      # inference form: the moving statistics, read at every launch
                 g_i, b_i, o.aux[0], o.aux[1] = bidx[id(op.layer)]
                 o.w, o.b = g_i, b_i
@@ -719,6 +737,9 @@ class Model(object):
         if dtype == 'bfloat16' and self.plan.bn_layers:
             raise NotImplementedError('bfloat16 activation storage of a model with BatchNormalization layers is not implemented '
                                       '(the channel-octet layout would need an index map of its own)')
+        if dtype == 'bfloat16' and self.plan.dense_layers:
+            raise NotImplementedError('bfloat16 activation storage of a model with Dense layers is not implemented (the dense '
+                                      'kernels read and write float32)')
         if dtype != self.activation_dtype:
             self.activation_dtype = dtype
             # interleaved phase stores (dlwp_conv2d.out_d2s) belong to the float32 Winograd kernels; with bfloat16 storage
@@ -746,7 +767,7 @@ class Model(object):
         """Executor of the training plan: float32 activations, every pre-pooling tensor materialised."""
         if self._train_executor is None:
             same = self.activation_dtype == 'float32' and len(self.infer_plan.ops) == len(self.plan.ops) and \
-                not any(op.out_pool or op.out_d2s for op in self.infer_plan.ops)
+                not any(op.out_pool or op.out_d2s for op in self.infer_plan.ops) and not self.plan.dropout_layers
             self._train_executor = self.executor if same else Executor(self.plan, self.device, 'float32')
         return self._train_executor
 

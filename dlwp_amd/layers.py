@@ -441,6 +441,120 @@ class BatchNormalization(Layer):
         return cfg
 
 
+class Dense(Layer):
+    """keras.layers.Dense on per-sample rank-1 inputs -- the feed-forward model of the reference (examples/train_generator.py:224-233:
+    Dense(n_features // 2, tanh, l2) -> Dropout(0.25) -> Dense(n_features)) and the dense head behind Flatten (:138-140).
+    Weights in Keras layout: kernel (in, units) glorot_uniform (limit sqrt(6 / (in + units))), bias (units,) zeros.  Activations
+    None | 'linear' | 'tanh' | 'relu'.  Keras applies Dense to the last axis of a higher-rank input; no reference call site does,
+    and that raises NotImplementedError here."""
+
+    def __init__(self, units, activation=None, use_bias=True, kernel_initializer='glorot_uniform', bias_initializer='zeros',
+                 kernel_regularizer=None, bias_regularizer=None, activity_regularizer=None, kernel_constraint=None,
+                 bias_constraint=None, **kwargs):
+        if 'input_dim' in kwargs and 'input_shape' not in kwargs:
+            kwargs['input_shape'] = (int(kwargs.pop('input_dim')),)
+        super(Dense, self).__init__(**kwargs)
+        self.units = int(units)
+        if self.units <= 0:
+            raise ValueError('Dense: units must be positive, got %r' % (units,))
+        if callable(activation):
+            activation = getattr(activation, '__name__', None)
+        if activation not in (None, 'linear', 'tanh', 'relu'):
+            raise NotImplementedError('Dense activation %r is not implemented (linear, tanh, relu are)' % (activation,))
+        if kernel_initializer not in ('glorot_uniform', 'zeros') or bias_initializer not in ('zeros',):
+            raise NotImplementedError('initialisers: kernel glorot_uniform|zeros, bias zeros')
+        for nm, v in (('bias_regularizer', bias_regularizer), ('activity_regularizer', activity_regularizer),
+                      ('kernel_constraint', kernel_constraint), ('bias_constraint', bias_constraint)):
+            if v is not None:
+                raise NotImplementedError('Dense: %s is not implemented' % nm)
+        self.activation = activation or 'linear'
+        self.use_bias = bool(use_bias)
+        self.kernel_initializer = kernel_initializer
+        self.kernel_regularizer = kernel_regularizer   # l2 handled by the trainer when it is a dlwp_amd.regularizers.L2
+        self.kernel = None
+        self.bias = None
+
+    def compute_output_shape(self, s):
+        if len(s) != 1:
+            raise NotImplementedError('%s: Dense on a per-sample shape %r is not implemented (Keras would apply it to the last '
+                                      'axis; put a Flatten in front)' % (self.name, tuple(s)))
+        return (self.units,)
+
+    def build(self, input_shape, device, rng):
+        import torch
+        fin = int(input_shape[0])
+        if self.built:
+            if self.kernel.shape[0] != fin:
+                raise ValueError('%s was built for %d input features, now called with %d' % (self.name, self.kernel.shape[0], fin))
+            return
+        if self.kernel_initializer == 'glorot_uniform':
+            limit = math.sqrt(6.0 / (fin + self.units))
+            k = rng.uniform(-limit, limit, size=(fin, self.units)).astype(np.float32)
+        else:
+            k = np.zeros((fin, self.units), dtype=np.float32)
+        self.kernel = torch.from_numpy(k).to(device)
+        self._weights = [('kernel', self.kernel)]
+        if self.use_bias:
+            self.bias = torch.zeros(self.units, dtype=torch.float32, device=device)
+            self._weights.append(('bias', self.bias))
+        self.built = True
+
+    def get_config(self):
+        cfg = super(Dense, self).get_config()
+        cfg.update({'units': self.units, 'activation': self.activation, 'use_bias': self.use_bias})
+        return cfg
+
+
+class Flatten(Layer):
+    """keras.layers.Flatten.  data_format None / 'channels_last' (Keras' default configuration, what `('Flatten', None, None)`
+    builds): a relabelling of the contiguous per-sample block, like Reshape -- no launch.  Keras' data_format='channels_first'
+    permutes the tensor to channels-last order first; that permutation is not implemented and raises."""
+
+    def __init__(self, data_format=None, **kwargs):
+        super(Flatten, self).__init__(**kwargs)
+        self.data_format = normalize_data_format(data_format)
+        if self.data_format == 'channels_first':
+            raise NotImplementedError("Flatten(data_format='channels_first') permutes the tensor to channels-last order before "
+                                      "flattening in Keras; that permutation is not implemented (data_format=None keeps the "
+                                      "stored order, as Keras' default configuration does)")
+
+    def compute_output_shape(self, s):
+        return (int(np.prod(s)),)
+
+    def get_config(self):
+        cfg = super(Flatten, self).get_config()
+        cfg.update({'data_format': self.data_format})
+        return cfg
+
+
+class Dropout(Layer):
+    """keras.layers.Dropout(rate): the identity in predict / evaluate / rollouts (no launch there); in a training step the input times
+    mask / (1 - rate).  The mask comes from Philox-4x32-10 keyed by (seed, layer index among the model's Dropout layers, training
+    step, element index): no state, the same in the forward and the backward of a step, another one at the next step, reproducible
+    from the seed (seed=None draws one from the model's generator when the model is built)."""
+
+    def __init__(self, rate, noise_shape=None, seed=None, **kwargs):
+        super(Dropout, self).__init__(**kwargs)
+        self.rate = float(rate)
+        if not 0.0 <= self.rate < 1.0:
+            raise ValueError('Dropout: rate must be in [0, 1), got %r' % (rate,))
+        if noise_shape is not None:
+            raise NotImplementedError('Dropout: noise_shape is not implemented (one mask element per tensor element)')
+        self.noise_shape = None
+        self.seed = None if seed is None else int(seed)
+        self.mask_seed = self.seed       # what the kernels are keyed with (build() fills it when seed is None)
+
+    def build(self, input_shape, device, rng):
+        if self.mask_seed is None:
+            self.mask_seed = int(rng.randint(0, 2 ** 31 - 1))
+        self.built = True
+
+    def get_config(self):
+        cfg = super(Dropout, self).get_config()
+        cfg.update({'rate': self.rate, 'noise_shape': None, 'seed': self.seed})
+        return cfg
+
+
 class _Pad3DBase(Layer):
     """ZeroPadding3D / PeriodicPadding3D argument handling (keras ZeroPadding3D forms).  On the HIP path these layers
     pad the recurrent (T, C, H, W) tensor in front of ConvLSTM2D (examples/train.py:144-147): channels_first makes T the

@@ -27,6 +27,16 @@ def _refuse_parallel_batchnorm(model):
                                   % ', '.join(bn))
 
 
+def _refuse_parallel_dropout(model):
+    """Dropout masks are keyed by the element's position in the LOCAL batch: a data-parallel step on two shards would not draw the
+    masks of the single-process step on the whole batch.  Not implemented (checked before any worker process is started)."""
+    from ..layers import Dropout
+    dr = [lay.name for lay in model.layers if isinstance(lay, Dropout)]
+    if dr:
+        raise NotImplementedError('build_model(gpus > 1) with Dropout layers (%s) is not implemented: the masks would have to be '
+                                  'indexed by the global sample position' % ', '.join(dr))
+
+
 class _Wrapper(object):
     """State and helpers shared by both wrappers."""
 
@@ -69,6 +79,15 @@ class _Wrapper(object):
         from .. import ops
         series = self.model.rollout_on_device(x, calls)          # (calls*n_out, N) + state shape
         n_slots, n_sample = series.shape[0], series.shape[1]
+        if series.dim() == 3:            # a dense model: (slots, N, F) -> (slots, N, time_dim, F / time_dim) or time-major
+            if keep_time_dim:
+                out = series.reshape((n_slots, n_sample, self.time_dim, -1))
+                return out.clone() if fresh else out
+            if int(self.time_dim) == 1:
+                out = series.reshape((n_slots, n_sample, -1))
+                return out.clone() if fresh else out
+            out = ops.series_merge_time(series.reshape((n_slots, n_sample, -1, 1)).contiguous(), self.time_dim)
+            return out.reshape((n_slots * self.time_dim, n_sample, -1))
         fs = tuple(series.shape[3:]) if self.is_recurrent else tuple(series.shape[2:])
         if keep_time_dim:
             out = series.reshape((n_slots, n_sample, self.time_dim, -1) + fs[1:])
@@ -286,6 +305,7 @@ class DLWPNeuralNet(_Wrapper):
         self.model = net
         if gpus > 1:
             _refuse_parallel_batchnorm(net)
+            _refuse_parallel_dropout(net)
         self.gpus = gpus
         if gpus > 1:
             from .. import parallel
@@ -472,6 +492,7 @@ class DLWPFunctional(_Wrapper):
             raise TypeError("'gpus' argument must be an int")
         if gpus > 1:
             _refuse_parallel_batchnorm(model)
+            _refuse_parallel_dropout(model)
         self.base_model = model
         self.model = model
         self._n_steps = len(model.outputs)

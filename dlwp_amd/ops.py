@@ -1072,3 +1072,85 @@ def batchnorm_bwd(x, dy, gamma, save_mean, save_invstd, ws, dgamma=None, dbeta=N
                                            _ptr(save_mean), _ptr(save_invstd), _ptr(dgamma), _ptr(dbeta), _ptr(ws),
                                            ws.numel() * ws.element_size(), d, _stream(x)))
     return dx if want_dx else None
+
+
+# ------------------------------------------------------------------------------------------------------------------ #
+# Dense and Dropout (csrc/dense.hip)
+# ------------------------------------------------------------------------------------------------------------------ #
+
+def _dense_desc(m, kernel, act):
+    k, n = (int(v) for v in kernel.shape)
+    return _lib.Dense(int(m), k, n, ACTIVATIONS[act] if not isinstance(act, int) else int(act))
+
+
+def _rows(t):
+    """samples of a (n, ...) tensor whose per-sample block is read as one row"""
+    return int(t.shape[0])
+
+
+def dense_fwd(x, kernel, bias, act=None, out=None):
+    """y = act(x kernel + bias): x (m, ...) with prod(...) = k features per sample, kernel (k, units) in Keras layout, bias
+    (units,) or None.  out: any contiguous tensor of m * units floats (default (m, units))."""
+    _check_f32(x, kernel, bias, out)
+    d = _dense_desc(_rows(x), kernel, act)
+    if x.numel() != d.m * d.k:
+        raise ValueError('dense_fwd: input of %r does not hold %d features per sample' % (tuple(x.shape), d.k))
+    y = out if out is not None else torch.empty((d.m, d.n), dtype=torch.float32, device=x.device)
+    if y.numel() != d.m * d.n:
+        raise ValueError('dense_fwd: output of %r does not hold %d units per sample' % (tuple(y.shape), d.n))
+    _lib.check(_lib.lib.dlwp_dense_fwd(_lib.handle(_dev(x)), _ptr(x), _ptr(kernel), _ptr(bias), _ptr(y), d, _stream(x)))
+    return y
+
+
+def dense_bwd_data(dy, y, kernel, act=None, out=None):
+    """dx = (dy o act'(y)) kernel^T, (m, k) unless out is given; y: the forward's output (not read when act is linear)."""
+    _check_f32(dy, y, kernel, out)
+    d = _dense_desc(_rows(dy), kernel, act)
+    if dy.numel() != d.m * d.n or (y is not None and y.numel() != dy.numel()):
+        raise ValueError('dense_bwd_data: gradient of %r does not match %d units per sample' % (tuple(dy.shape), d.n))
+    dx = out if out is not None else torch.empty((d.m, d.k), dtype=torch.float32, device=dy.device)
+    if dx.numel() != d.m * d.k:
+        raise ValueError('dense_bwd_data: output of %r does not hold %d features per sample' % (tuple(dx.shape), d.k))
+    _lib.check(_lib.lib.dlwp_dense_bwd_data(_lib.handle(_dev(dy)), _ptr(dy), _ptr(y), _ptr(kernel), _ptr(dx), d, _stream(dy)))
+    return dx
+
+
+def dense_bwd_weight(x, dy, y, dkernel, dbias=None, act=None):
+    """dkernel (k, units) = x^T (dy o act'(y)), dbias (units,) = its column sums (None: not wanted); both overwritten."""
+    _check_f32(x, dy, y, dkernel, dbias)
+    d = _dense_desc(_rows(x), dkernel, act)
+    if x.numel() != d.m * d.k or dy.numel() != d.m * d.n or (y is not None and y.numel() != dy.numel()):
+        raise ValueError('dense_bwd_weight: x %r / dy %r do not match a (%d, %d) kernel' % (tuple(x.shape), tuple(dy.shape), d.k, d.n))
+    if dbias is not None and dbias.numel() != d.n:
+        raise ValueError('dense_bwd_weight: bias gradient of %d elements for %d units' % (dbias.numel(), d.n))
+    _lib.check(_lib.lib.dlwp_dense_bwd_weight(_lib.handle(_dev(x)), _ptr(x), _ptr(dy), _ptr(y), _ptr(dkernel), _ptr(dbias), d,
+                                              _stream(x)))
+    return dkernel
+
+
+def dropout_desc(rate, seed, layer, step):
+    """The launch descriptor of keras Dropout(rate): threshold = floor(rate 2^32) (an element is kept when its Philox word is >=
+    it), scale = float32(1 / (1 - rate)); seed a 64-bit integer, layer / step 32-bit."""
+    rate = float(rate)
+    if not 0.0 <= rate < 1.0:
+        raise ValueError('dropout rate must be in [0, 1), got %r' % (rate,))
+    thr = min(int(rate * 4294967296.0), 4294967295)
+    return _lib.Dropout(int(seed) & 0xffffffffffffffff, int(layer) & 0xffffffff, int(step) & 0xffffffff, thr, 1.0 / (1.0 - rate))
+
+
+def dropout_fwd(x, rate, seed, layer, step, out=None):
+    """y = x * mask / (1 - rate), the mask of (seed, layer, step); rate 0 copies."""
+    _check_f32(x, out)
+    y = out if out is not None else torch.empty_like(x)
+    _lib.check(_lib.lib.dlwp_dropout_fwd(_lib.handle(_dev(x)), _ptr(x), _ptr(y), x.numel(), dropout_desc(rate, seed, layer, step),
+                                         _stream(x)))
+    return y
+
+
+def dropout_bwd(dy, rate, seed, layer, step, out=None):
+    """dx = dy * mask / (1 - rate) with the mask the forward of (seed, layer, step) drew."""
+    _check_f32(dy, out)
+    dx = out if out is not None else torch.empty_like(dy)
+    _lib.check(_lib.lib.dlwp_dropout_bwd(_lib.handle(_dev(dy)), _ptr(dy), _ptr(dx), dy.numel(), dropout_desc(rate, seed, layer, step),
+                                         _stream(dy)))
+    return dx

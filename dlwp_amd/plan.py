@@ -65,7 +65,7 @@ class View(object):
 
 
 class PlanOp(object):
-    """One launch.  kind in {'conv','rowconv','pad','maxpool','upsample','copy','lstm','phasew','d2s','bn'}."""
+    """One launch.  kind in {'conv','rowconv','pad','maxpool','upsample','copy','lstm','phasew','d2s','bn','dense','dropout'}."""
 
     def __init__(self, kind, src, dst, xs, **kw):
         self.kind, self.src, self.dst = kind, src, dst
@@ -131,6 +131,8 @@ class Plan(object):
         self.conv_layers = []    # unique Conv2D layers in first-use order
         self.phase_params = []   # derived (phase-summed) kernels: dicts layer, w2_shape, b2 (bool), pad_top, pad_left
         self.bn_layers = []      # BatchNormalization layers in plan order (one 'bn' op each)
+        self.dense_layers = []   # Dense layers in plan order (one 'dense' op each)
+        self.dropout_layers = [] # Dropout layers in graph order (training plans: one 'dropout' op each; its index keys the mask)
 
     def new_buffer(self, c, h, w):
         self.buffers.append((int(c), int(h), int(w)))
@@ -342,7 +344,10 @@ def build_plan(inputs, outputs, inference=False, fuse_d2s=True, fuse_lstm=False,
 
     def store_of(shape):
         """stored 3-D (c, h, w) block of a logical per-sample shape: everything in front of the last two axes is
-        channels (the recurrent (T, C, H, W) layout is (T*C, H, W) in memory)."""
+        channels (the recurrent (T, C, H, W) layout is (T*C, H, W) in memory).  A rank-1 tensor of F features (Dense models) is
+        stored as (F, 1, 1)."""
+        if len(shape) == 1:
+            return (int(shape[0]), 1, 1)
         if len(shape) < 3:
             raise NotImplementedError('dense (non-convolutional) tensors of per-sample shape %r are not on the HIP path'
                                       % (shape,))
@@ -727,6 +732,51 @@ def build_plan(inputs, outputs, inference=False, fuse_d2s=True, fuse_lstm=False,
             plan.bn_layers.append(lay)
             emit(PlanOp('bn', v.buf, dst, (v.c, v.h, v.w), layer=lay, out_c_total=v.c, out_shape=(v.c, v.h, v.w)))
             views[t.uid] = View(dst, 0, v.c, v.c, v.h, v.w)
+        elif isinstance(lay, L.Flatten):
+            # keras Flatten (default data_format): the contiguous per-sample block read as one row -- a view, no launch.  The
+            # buffer keeps its stored shape (what its producer and that producer's backward know); only the logical shape changes.
+            v = materialize(ins[0])
+            if not v.full:
+                v = materialize(v, dst=plan.new_buffer(*v.logical))
+            views[t.uid] = v.copy(shape=tuple(t.shape))
+        elif isinstance(lay, L.Dense):
+            # keras Dense (csrc/dense.hip): reads a whole stored buffer as (n, k) rows, writes (n, units)
+            if lay in plan.dense_layers:
+                raise NotImplementedError('%s: a Dense layer applied more than once is not implemented' % lay.name)
+            v = materialize(ins[0])
+            if not v.full:
+                v = materialize(v, dst=plan.new_buffer(*v.logical))
+            if lay.kernel is not None and v.c * v.h * v.w != int(lay.kernel.shape[0]):
+                raise ValueError('%s: kernel for %d features on an input of %d' % (lay.name, lay.kernel.shape[0], v.c * v.h * v.w))
+            if outs:
+                dst = OUT(outs[0])
+                plan.output_store[outs[0]] = (lay.units, 1, 1)
+            else:
+                dst = plan.new_buffer(lay.units, 1, 1)
+            plan.dense_layers.append(lay)
+            emit(PlanOp('dense', v.buf, dst, (v.c, v.h, v.w), layer=lay, act=ACT[lay.activation], out_c_total=lay.units,
+                        out_shape=(lay.units, 1, 1)))
+            views[t.uid] = View(dst, 0, lay.units, lay.units, 1, 1, shape=tuple(t.shape))
+        elif isinstance(lay, L.Dropout):
+            # keras Dropout: the identity outside training -- an inference plan passes the view on.  The training plan gives it a
+            # launch and a buffer of its own (the executor runs it as a copy when the forward is not a training step's).
+            if lay in plan.dropout_layers:
+                raise NotImplementedError('%s: a Dropout layer applied more than once is not implemented' % lay.name)
+            plan.dropout_layers.append(lay)
+            if inference:
+                views[t.uid] = ins[0]
+            else:
+                shp = ins[0].shape
+                v = materialize(ins[0])
+                if not v.full:
+                    v = materialize(v, dst=plan.new_buffer(*v.logical))
+                if outs:
+                    dst = OUT(outs[0])
+                    plan.output_store[outs[0]] = (v.c, v.h, v.w)
+                else:
+                    dst = plan.new_buffer(v.c, v.h, v.w)
+                emit(PlanOp('dropout', v.buf, dst, (v.c, v.h, v.w), layer=lay, out_c_total=v.c, out_shape=(v.c, v.h, v.w)))
+                views[t.uid] = View(dst, 0, v.c, v.c, v.h, v.w, shape=shp)
         else:
             raise NotImplementedError('layer %s (%s) has no HIP lowering' % (lay.name, type(lay).__name__))
 
@@ -746,8 +796,9 @@ def build_plan(inputs, outputs, inference=False, fuse_d2s=True, fuse_lstm=False,
                     return op.src == v.buf or v.buf in extra
                 writers = [op for op in plan.ops if op.dst == v.buf]
                 w0 = writers[0] if len(writers) == 1 else None
-                if (w0 is not None and w0.kind in ('conv', 'd2s', 'rowconv') and not w0.lstm_f and not w0.out_pool and
-                        w0.out_c_off == 0 and w0.out_c_total in (0, lc[0]) and not any(reads(op) for op in plan.ops)):
+                if (w0 is not None and w0.kind in ('conv', 'd2s', 'rowconv', 'dense') and not w0.lstm_f and not w0.out_pool and
+                        (w0.kind == 'dense' or (w0.out_c_off == 0 and w0.out_c_total in (0, lc[0]))) and
+                        not any(reads(op) for op in plan.ops)):
                     # every view of the abandoned scratch buffer follows the launch into the output slot (the convolution's own
                     # tensor in front of the Reshape, slices of it): a consumer lowered LATER -- another branch of a
                     # multi-output model -- must not read a buffer nothing writes any more

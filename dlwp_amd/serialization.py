@@ -47,6 +47,15 @@ def _layer_config(lay):
             cfg['kernel_regularizer'] = {'l2': lay.kernel_regularizer.l2}
     elif isinstance(lay, L.BatchNormalization):
         cfg.update(axis=lay.axis, momentum=lay.momentum, epsilon=lay.epsilon, center=lay.center, scale=lay.scale)
+    elif isinstance(lay, L.Dense):
+        from .regularizers import L1L2
+        cfg.update(units=lay.units, activation=lay.activation, use_bias=lay.use_bias)
+        if isinstance(lay.kernel_regularizer, L1L2):
+            cfg['kernel_regularizer'] = {'l2': lay.kernel_regularizer.l2}
+    elif isinstance(lay, L.Flatten):
+        cfg.update(data_format=lay.data_format)
+    elif isinstance(lay, L.Dropout):       # (the seed the masks are keyed with: a loaded model continues the same sequence)
+        cfg.update(rate=lay.rate, seed=lay.mask_seed)
     elif isinstance(lay, (L.MaxPooling2D, L.UpSampling2D)):
         cfg.update(data_format=lay.data_format)
     elif isinstance(lay, L.Reshape):
@@ -200,6 +209,13 @@ def _keras_layer_spec(lay):
         c.update(axis=lay.axis, momentum=lay.momentum, epsilon=lay.epsilon, center=lay.center, scale=lay.scale,
                  **{k: init[v] for k, v in lay.initializers.items()})
         c.update(beta_regularizer=None, gamma_regularizer=None, beta_constraint=None, gamma_constraint=None)
+    elif isinstance(lay, L.Dense):
+        c.update(units=lay.units, activation=lay.activation or 'linear', use_bias=lay.use_bias, kernel_initializer=_GLOROT,
+                 bias_initializer=_ZEROS, kernel_regularizer=reg(lay.kernel_regularizer), **tail)
+    elif isinstance(lay, L.Flatten):
+        c.update(data_format=lay.data_format)
+    elif isinstance(lay, L.Dropout):       # (the seed the masks are keyed with: a loaded model continues the same sequence)
+        c.update(rate=lay.rate, noise_shape=None, seed=lay.mask_seed)
     elif isinstance(lay, L.MaxPooling2D):
         c.update(pool_size=[2, 2], padding='valid', strides=[2, 2], data_format=lay.data_format)
     elif isinstance(lay, L.UpSampling2D):

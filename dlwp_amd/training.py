@@ -437,6 +437,8 @@ class Trainer(object):
         from . import ops
         phase = self._phase_outputs()
         skip = tuple(k for k, _, _ in phase.values())
+        if want_grad and self.plan.dropout_layers:      # Dropout masks are keyed by the training step (the optimizer's count)
+            self.model.train_executor.dropout_step = int(self.model.optimizer.iterations)
         if prep is not None:
             outs = self.model.train_executor.run(x, prepared=prep['fwd'], skip_phasew=True, skip_ops=skip, training=want_grad)
         else:
@@ -940,6 +942,24 @@ class Trainer(object):
                     dense = torch.empty((n, cin) + tuple(src.shape[2:]), dtype=torch.float32, device=self.device)
                     ops.rowconv2d_bwd_data(dz, lay.kernel, dd, xs, dense)
                 deposit(op.src, op.in_c_off, cin, dense)
+            elif op.kind == 'dense':           # keras Dense: weight and bias gradient, then (not for the model input) dx
+                lay = op.layer
+                y = tensor(op.dst)
+                ops.dense_bwd_weight(src, gD, y, self._grad_view(lay, 'kernel'),
+                                     self._grad_view(lay, 'bias') if lay.bias is not None else None, op.act)
+                touched_layers.add(id(lay))
+                if op.src == P.STATE_IN:
+                    continue
+                dx = torch.empty_like(src)
+                ops.dense_bwd_data(gD, y, lay.kernel, op.act, out=dx)
+                deposit(op.src, 0, src.shape[1], dx)
+            elif op.kind == 'dropout':         # the mask of the forward: same (seed, layer, step)
+                if op.src == P.STATE_IN:
+                    continue
+                lay = op.layer
+                dx = ops.dropout_bwd(gD, lay.rate, lay.mask_seed, plan.dropout_layers.index(lay),
+                                     self.model.train_executor.dropout_step)
+                deposit(op.src, 0, src.shape[1], dx.view(src.shape))
             elif op.kind == 'bn':              # BatchNormalization: dgamma, dbeta and dx from the batch statistics of the forward
                 lay = op.layer
                 st = self.model.train_executor.bn_state(k, int(n))
@@ -1112,12 +1132,13 @@ class Trainer(object):
         DLWP_TRAIN_GRAPH: '0' never replay; '1' always; unset: folded plans replay -- small steps (at most graph_below samples x
         grid points) as 'graph', larger ones as 'lanes' (their weight gradients gain from the side streams: batch 64 1.78 ->
         1.68 ms in r3).  DLWP_TRAIN_STEP=graph|lanes|branches|torch picks the form.  Never replayed: kernel regularisers (their
-        penalty is read back to the host every step), SGD with decay (its rate is a launch argument), steps on the CPU device."""
+        penalty is read back to the host every step), SGD with decay (its rate is a launch argument), models with Dropout layers
+        (the step number that keys their masks is a launch argument), steps on the CPU device."""
         opt = self.model.optimizer
         mode = os.environ.get('DLWP_TRAIN_GRAPH', 'auto')
         if self.device.type != 'cuda' or mode == '0' or n_local is None:
             return False
-        if any(True for _ in self._regularized()):
+        if any(True for _ in self._regularized()) or self.plan.dropout_layers:
             return False
         if not (isinstance(opt, Adam) or (isinstance(opt, SGD) and opt.decay == 0.0)):
             return False

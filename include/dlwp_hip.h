@@ -578,6 +578,35 @@ int dlwp_batchnorm_bwd(dlwp_handle_t, const void* x, const void* dy, void* dx, c
                        const void* save_invstd, void* dgamma, void* dbeta, void* ws, size_t ws_bytes, dlwp_batchnorm d,
                        void* stream);
 
+/* ---- keras Dense and Dropout on float32 row-major matrices: the feed-forward model of examples/train_generator.py:224-233
+ *      (Dense(n_features // 2, tanh, l2) -> Dropout(0.25) -> Dense(n_features)) and the dense head of :138-140 (csrc/dense.hip).
+ *      x (m, k), w (k, n) = the Keras kernel, b (n) nullable, y / dy (m, n), dx (m, k), dw (k, n), db (n) nullable.
+ *      fwd       : y = act(x w + b)
+ *      bwd_data  : dx = (dy o act'(y)) w^T                  (y: the forward's output; unused with DLWP_ACT_LINEAR)
+ *      bwd_weight: dw = x^T (dy o act'(y)), db = its column sums; both OVERWRITTEN
+ *      All products on the float32 matrix instruction, sums in a fixed order, no atomics: two runs give the same bits, and row i
+ *      of y / dx does not depend on m or on the other rows.  Any float alignment; no workspace.                              */
+typedef struct {
+  int m, k, n;                    /* samples, input features, units                                        */
+  int act;                        /* DLWP_ACT_*                                                            */
+} dlwp_dense;
+int dlwp_dense_fwd(dlwp_handle_t, const void* x, const void* w, const void* b, void* y, dlwp_dense d, void* stream);
+int dlwp_dense_bwd_data(dlwp_handle_t, const void* dy, const void* y, const void* w, void* dx, dlwp_dense d, void* stream);
+int dlwp_dense_bwd_weight(dlwp_handle_t, const void* x, const void* dy, const void* y, void* dw, void* db, dlwp_dense d,
+                          void* stream);
+/*      Dropout: y[i] = keep(i) ? x[i] * scale : 0 on n contiguous floats (y may alias x).  keep(i) = word (i mod 4) of
+ *      Philox-4x32-10 with counter (i / 4 low word, i / 4 high word, step, layer) and key (seed low word, seed high word) is
+ *      >= threshold; the caller passes threshold = floor(rate 2^32) and scale = 1 / (1 - rate).  No state: the backward names the
+ *      same (seed, layer, step) and multiplies dy by the same mask.  threshold 0, scale 1 is a copy.                          */
+typedef struct {
+  unsigned long long seed;
+  unsigned layer, step;           /* which Dropout layer of the model, which training step                 */
+  unsigned threshold;
+  float scale;
+} dlwp_dropout;
+int dlwp_dropout_fwd(dlwp_handle_t, const void* x, void* y, long long n, dlwp_dropout d, void* stream);
+int dlwp_dropout_bwd(dlwp_handle_t, const void* dy, void* dx, long long n, dlwp_dropout d, void* stream);
+
 /* ---- rollout: the N-step predict_timeseries loop (DLWP/model/models.py:277-293, 439-447) captured as ONE hipGraph.
  *      A plan is an array of dlwp_op describing one model call; buffer index >= 0 = caller scratch buffer,
  *      DLWP_BUF_STATE_IN = the call's input state, DLWP_BUF_OUT(o) = output o of the call.  Call t reads
@@ -599,8 +628,9 @@ int dlwp_batchnorm_bwd(dlwp_handle_t, const void* x, const void* dy, void* dx, c
 #define DLWP_OP_BATCHNORM  9      /* dlwp_batchnorm_fwd_infer: src, dst, xs = (n, c, h, w); w / b = gamma / beta buffer | -1,
                                    * aux[0] / aux[1] = moving mean / variance buffer, aux[2] = the bits of epsilon (float).
                                    * The moving statistics are read at every launch: a graph never holds stale ones.      */
+#define DLWP_OP_DENSE     10      /* dlwp_dense_fwd: src, dst, w, b (| -1); xs = (n, k, 1, 1), conv.cout = units, conv.act       */
 typedef struct {
-  int kind;                 /* DLWP_OP_*                                                                  */
+  int kind;                 /* DLWP_OP_*                                                                */
   int src, dst;             /* buffer indices                                                              */
   int w, b;                 /* weight / bias buffer indices (conv only)                                    */
   dlwp_shape4 xs;           /* stored input shape of this op                                               */
