@@ -951,6 +951,8 @@ def loss_metrics(y_pred, y_true, out, mask, phase=False, ws_key=None):
 
 def adam_keras(p, m, v, g, iteration, lr=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7, decay=0.0, grad_scale=1.0):
     _check_f32(p, m, v, g)
+    if p.numel() == 0:      # (an empty tensor has no address for the C ABI to check)
+        return
     _lib.check(_lib.lib.dlwp_adam_keras(_lib.handle(_dev(p)), _ptr(p), _ptr(m), _ptr(v), _ptr(g), p.numel(), lr, beta_1,
                                         beta_2, epsilon, decay, int(iteration), grad_scale, _stream(p)))
 
@@ -962,6 +964,8 @@ def adam_keras_dev(p, m, v, g, iteration_dev, lr_t_scratch, lr=1e-3, beta_1=0.9,
     _check_f32(p, m, v, g, lr_t_scratch)
     if iteration_dev.dtype != torch.int64 or iteration_dev.numel() != 1:
         raise ValueError('iteration_dev must be one int64 on the device')
+    if p.numel() == 0:      # nothing is touched, the step number included (as dlwp_adam_keras_dev itself has it)
+        return
     _lib.check(_lib.lib.dlwp_adam_keras_dev(_lib.handle(_dev(p)), _ptr(p), _ptr(m), _ptr(v), _ptr(g), p.numel(), lr, beta_1,
                                             beta_2, epsilon, decay, _ptr(iteration_dev), _ptr(lr_t_scratch), grad_scale,
                                             _stream(p)))
@@ -969,6 +973,8 @@ def adam_keras_dev(p, m, v, g, iteration_dev, lr_t_scratch, lr=1e-3, beta_1=0.9,
 
 def sgd_keras(p, vel, g, iteration, lr=0.01, momentum=0.0, decay=0.0, grad_scale=1.0):
     _check_f32(p, vel, g)
+    if p.numel() == 0:
+        return
     _lib.check(_lib.lib.dlwp_sgd_keras(_lib.handle(_dev(p)), _ptr(p), _ptr(vel), _ptr(g), p.numel(), lr, momentum, decay,
                                        int(iteration), grad_scale, _stream(p)))
 
@@ -993,6 +999,8 @@ def copy_many(pairs):
 def axpby(x, y, a=1.0, b=1.0):
     """y <- a*x + b*y"""
     _check_f32(x, y)
+    if x.numel() == 0:
+        return y
     _lib.check(_lib.lib.dlwp_axpby(_lib.handle(_dev(x)), _ptr(x), _ptr(y), x.numel(), float(a), float(b), _stream(x)))
     return y
 

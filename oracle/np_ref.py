@@ -320,6 +320,14 @@ def adam_keras_step(p, m, v, g, iteration, lr=1e-3, beta_1=0.9, beta_2=0.999, ep
     return p, m, v
 
 
+def sgd_keras_step(p, vel, g, iteration, lr=0.01, momentum=0., decay=0.):
+    """One keras.optimizers.SGD update (nesterov off): lr' = lr/(1+decay*it); vel = momentum*vel - lr'*g; p += vel."""
+    lr_ = lr / (1. + decay * iteration)
+    vel = momentum * vel - lr_ * g
+    p = p + vel
+    return p, vel
+
+
 # ------------------------------------------------------------------------------------------------------------------ #
 # ConvLSTM2D  (PARITY UNPINNED: the arithmetic lives in Keras 2.2.x, keras/layers/convolutional_recurrent.py
 # ConvLSTM2DCell.call, absent here; restated from its published algorithm.  Call sites: examples/train.py:148-155,

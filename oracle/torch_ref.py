@@ -112,21 +112,31 @@ def run_layers(layers, x, tweights, record=None):
     return x
 
 
-def conv_lstm2d(x, k_oihw, r_oihw, b, dilation=1, activation='tanh', return_sequences=True):
+def convlstm_gates(zx, zh, c_prev, act='tanh', rec_act='hard_sigmoid'):
+    """The cell update of Keras' ConvLSTM2DCell.call as a differentiable function: zx, zh (n, 4F, h, w) gate pre-activations
+    (gate order i, f, c, o as in np_ref.conv_lstm2d; zh and c_prev None on the first step), c_prev (n, F, h, w):
+        z = zx + zh;  c = rec(z_f) c_prev + rec(z_i) act(z_c);  h = rec(z_o) act(c)
+    hard_sigmoid(z) = clamp(0.2 z + 0.5, 0, 1).  Returns (c, h) in the dtype of zx."""
+    a = {'tanh': torch.tanh, 'relu': torch.relu, 'linear': lambda v: v, None: lambda v: v}[act]
+    rec = {'hard_sigmoid': lambda v: torch.clamp(0.2 * v + 0.5, 0.0, 1.0), 'sigmoid': torch.sigmoid}[rec_act]
+    z = zx if zh is None else zx + zh
+    f = z.shape[1] // 4
+    c = rec(z[:, :f]) * a(z[:, 2 * f:3 * f])
+    if c_prev is not None:
+        c = rec(z[:, f:2 * f]) * c_prev + c
+    return c, rec(z[:, 3 * f:]) * a(c)
+
+
+def conv_lstm2d(x, k_oihw, r_oihw, b, dilation=1, activation='tanh', return_sequences=True,
+                recurrent_activation='hard_sigmoid'):
     """Independent restatement of Keras' ConvLSTM2DCell on torch-CPU convolutions ('valid' input conv, 'same'
     recurrent conv, hard_sigmoid gates); weights OIHW as to_torch_weights produces them."""
-    act = torch.tanh if activation == 'tanh' else (lambda v: v)
-    hs = lambda v: torch.clamp(0.2 * v + 0.5, 0.0, 1.0)  # noqa: E731
-    f = k_oihw.shape[0] // 4
     h = c = None
     outs = []
     for t in range(x.shape[1]):
-        z = F.conv2d(x[:, t], k_oihw, b, dilation=dilation)
-        if h is not None:
-            z = z + F.conv2d(h, r_oihw, None, padding=(r_oihw.shape[2] // 2, r_oihw.shape[3] // 2))
-        i, fg, g, o = hs(z[:, :f]), hs(z[:, f:2 * f]), act(z[:, 2 * f:3 * f]), hs(z[:, 3 * f:])
-        c = i * g if c is None else fg * c + i * g
-        h = o * act(c)
+        zx = F.conv2d(x[:, t], k_oihw, b, dilation=dilation)
+        zh = None if h is None else F.conv2d(h, r_oihw, None, padding=(r_oihw.shape[2] // 2, r_oihw.shape[3] // 2))
+        c, h = convlstm_gates(zx, zh, c, activation, recurrent_activation)
         outs.append(h)
     return torch.stack(outs, dim=1) if return_sequences else h
 
@@ -151,3 +161,10 @@ def adam_keras_step(p, m, v, g, iteration, lr=1e-3, beta_1=0.9, beta_2=0.999, ep
     m.mul_(beta_1).add_(g, alpha=1. - beta_1)
     v.mul_(beta_2).addcmul_(g, g, value=1. - beta_2)
     p.sub_(lr_t * m / (v.sqrt() + epsilon))
+
+
+def sgd_keras_step(p, vel, g, iteration, lr=0.01, momentum=0., decay=0.):
+    """float32 torch form of np_ref.sgd_keras_step (in place)."""
+    lr_ = lr / (1. + decay * iteration)
+    vel.mul_(momentum).sub_(g, alpha=lr_)
+    p.add_(vel)

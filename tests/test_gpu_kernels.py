@@ -873,34 +873,46 @@ def test_conv2d_with_prepared_weights_is_bit_identical(ops):
 # ConvLSTM2D cell update
 # ----------------------------------------------------------------------------------------------------------------- #
 
-@pytest.mark.parametrize('n,f,h,w,first,rec', [(2, 3, 5, 8, True, 'hard_sigmoid'), (3, 4, 6, 7, False, 'hard_sigmoid'),
-                                                (1, 8, 16, 24, False, 'sigmoid'), (0, 2, 4, 4, False, 'hard_sigmoid')])
-def test_convlstm_gates_match_oracle(ops, n, f, h, w, first, rec):
-    """c = rec(z_f) c' + rec(z_i) tanh(z_c), h = rec(z_o) tanh(c) (keras ConvLSTM2DCell.call); h lands in a channel
-    window of the return_sequences buffer.  Vector (hw % 4 == 0) and scalar paths, first step (no zh / c')."""
+GATE_CASES = [(2, 3, 5, 8, True, 'hard_sigmoid'), (3, 4, 6, 7, False, 'hard_sigmoid'), (1, 8, 16, 24, False, 'sigmoid'),
+              (0, 2, 4, 4, False, 'hard_sigmoid')]
+
+
+@pytest.mark.parametrize('n,f,h,w,first,rec,act',
+                         [pytest.param(*(c + ('tanh',)), id='-'.join(str(v) for v in c)) for c in GATE_CASES] +
+                         [pytest.param(*(c + (a,)), id='-'.join(str(v) for v in c + (a,))) for a in ('relu', 'linear')
+                          for c in GATE_CASES])
+def test_convlstm_gates_match_oracle(ops, n, f, h, w, first, rec, act):
+    """c = rec(z_f) c' + rec(z_i) act(z_c), h = rec(z_o) act(c) (keras ConvLSTM2DCell.call), act = tanh, relu or linear; h lands in
+    a channel window of the return_sequences buffer.  Vector (hw % 4 == 0) and scalar paths, first step (no zh / c').
+    tanh: 2e-6 absolute.  relu / linear outputs are not bounded by 1 (|z| reaches 10 here, where one float32 ulp is 1e-6 by
+    itself), so their 2e-6 is relative to the output scale, max(1, max|want|) -- the form of every forward bar of the project
+    (FWD_TOL); a wrong activation branch is an error of order 1."""
+    a_np = lambda v: np_ref.activate(v, act)  # noqa: E731
+    act_code = ops.ACTIVATIONS[act]
+    tol = (lambda want: 2e-6) if act == 'tanh' else (lambda want: 2e-6 * max(1.0, float(np.abs(want).max())))
     rng = np.random.default_rng(n * 100 + f)
     zx = (2 * rng.standard_normal((n, 4 * f, h, w))).astype(np.float32)
     zh = None if first else (2 * rng.standard_normal((n, 4 * f, h, w))).astype(np.float32)
     cp = None if first else rng.standard_normal((n, f, h, w)).astype(np.float32)
     z = zx.astype(np.float64) + (0 if zh is None else zh)
     r = np_ref.hard_sigmoid if rec == 'hard_sigmoid' else (lambda v: 1 / (1 + np.exp(-v)))
-    c_want = r(z[:, :f]) * np.tanh(z[:, 2 * f:3 * f]) + (0 if cp is None else r(z[:, f:2 * f]) * cp)
-    h_want = r(z[:, 3 * f:]) * np.tanh(c_want)
+    c_want = r(z[:, :f]) * a_np(z[:, 2 * f:3 * f]) + (0 if cp is None else r(z[:, f:2 * f]) * cp)
+    h_want = r(z[:, 3 * f:]) * a_np(c_want)
     c_out = torch.empty((n, f, h, w), device='cuda')
     h_out = torch.full((n, 3 * f, h, w), 7.0, device='cuda')
     ops.convlstm_gates(dev(zx), None if zh is None else dev(zh), None if cp is None else dev(cp), c_out, h_out, f,
-                       h_c_off=f, act=ops.ACT_TANH, rec_act=ops.REC_HARD_SIGMOID if rec == 'hard_sigmoid' else ops.REC_SIGMOID)
+                       h_c_off=f, act=act_code, rec_act=ops.REC_HARD_SIGMOID if rec == 'hard_sigmoid' else ops.REC_SIGMOID)
     if n == 0:
         return
-    assert np.abs(host(c_out) - c_want).max() < 2e-6
+    assert np.abs(host(c_out) - c_want).max() < tol(c_want)
     got = host(h_out)
-    assert np.abs(got[:, f:2 * f] - h_want).max() < 2e-6
+    assert np.abs(got[:, f:2 * f] - h_want).max() < tol(h_want)
     assert np.all(got[:, :f] == 7.0) and np.all(got[:, 2 * f:] == 7.0)
     # h stored as bfloat16 (config 4): the same values rounded once; c is float32 and unchanged
     c16 = torch.empty((n, f, h, w), device='cuda')
     h16 = torch.full((n, 3 * f, h, w), 7.0, device='cuda', dtype=torch.bfloat16)
     ops.convlstm_gates(dev(zx), None if zh is None else dev(zh), None if cp is None else dev(cp), c16, h16, f,
-                       h_c_off=f, act=ops.ACT_TANH, rec_act=ops.REC_HARD_SIGMOID if rec == 'hard_sigmoid' else ops.REC_SIGMOID)
+                       h_c_off=f, act=act_code, rec_act=ops.REC_HARD_SIGMOID if rec == 'hard_sigmoid' else ops.REC_SIGMOID)
     assert torch.equal(c16, c_out)
     assert torch.equal(h16, h_out.to(torch.bfloat16))
     # gate pre-activations stored as bfloat16 too: the float32 arithmetic on the rounded values
@@ -908,14 +920,14 @@ def test_convlstm_gates_match_oracle(ops, n, f, h, w, first, rec):
     zh16 = None if zh is None else dev(zh).to(torch.bfloat16)
     cz = torch.empty((n, f, h, w), device='cuda')
     hz = torch.full((n, 3 * f, h, w), 7.0, device='cuda', dtype=torch.bfloat16)
-    ops.convlstm_gates(zx16, zh16, None if cp is None else dev(cp), cz, hz, f, h_c_off=f, act=ops.ACT_TANH,
+    ops.convlstm_gates(zx16, zh16, None if cp is None else dev(cp), cz, hz, f, h_c_off=f, act=act_code,
                        rec_act=ops.REC_HARD_SIGMOID if rec == 'hard_sigmoid' else ops.REC_SIGMOID)
     z = np_ref.round_bf16(zx) + (0 if zh is None else np_ref.round_bf16(zh))
-    c_want = r(z[:, :f]) * np.tanh(z[:, 2 * f:3 * f]) + (0 if cp is None else r(z[:, f:2 * f]) * cp)
-    h_want = r(z[:, 3 * f:]) * np.tanh(c_want)
-    assert np.abs(host(cz) - c_want).max() < 2e-6
+    c_want = r(z[:, :f]) * a_np(z[:, 2 * f:3 * f]) + (0 if cp is None else r(z[:, f:2 * f]) * cp)
+    h_want = r(z[:, 3 * f:]) * a_np(c_want)
+    assert np.abs(host(cz) - c_want).max() < tol(c_want)
     hg = hz.to(torch.float32).cpu().numpy()[:, f:2 * f]
-    assert np.all(np.abs(hg - h_want) <= 2.0 ** -8 * np.abs(h_want) + 2e-6)
+    assert np.all(np.abs(hg - h_want) <= 2.0 ** -8 * np.abs(h_want) + tol(h_want))
 
 
 # ----------------------------------------------------------------------------------------------------------------- #

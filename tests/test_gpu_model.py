@@ -609,6 +609,55 @@ def test_train_step_gradients_loss_and_adam_match_autograd_oracle():
     assert ev[0] == pytest.approx(np_ref.mse(y, out1), rel=1e-3) and ev[1] == pytest.approx(np_ref.mae(y, out1), rel=1e-3)
 
 
+def test_train_step_weights_and_velocity_follow_the_autograd_oracle_sgd(monkeypatch):
+    """SGD(lr=0.01, momentum=0.9, decay=1e-2) on the small U-Net, five eager steps on five batches.  After every step the weights
+    are compared with np_ref.sgd_keras_step applied to the ORACLE'S OWN float64 gradient at the product's current weights (the
+    oracle is re-seeded from get_weights() and the velocity slot each step, so the bar is a single-step bar).  Bar: the gradient
+    bar of the Adam test above, 2e-4 max|g_ref|, times the step's rate lr' = lr / (1 + decay it), plus one float32 ulp of the
+    weight; the velocity: the same gradient term plus its float32 roundings, 3u (|mom vel| + |lr' g|).  The rate really decays:
+    at step 5 the oracle with the UNDECAYED rate is outside the bar."""
+    from dlwp_amd.training import SGD
+    monkeypatch.setenv('DLWP_TRAIN_GRAPH', '0')
+    rng = np.random.default_rng(18)
+    cs = (4, 16, 24)
+    layers = unet_layers(cs)
+    f32 = lambda v: float(np.float32(v))  # noqa: E731  (the C ABI receives floats)
+    lr, mom, decay = f32(0.01), f32(0.9), f32(1e-2)
+    d = _build(layers, time_dim=2, optimizer=SGD(lr=0.01, momentum=0.9, decay=1e-2))
+    _weights_of(d.model, rng)
+    tr = d.model._trainer
+    undecayed_outside = False
+    for k in range(5):
+        x = rng.standard_normal((6,) + cs).astype(np.float32)
+        y = rng.standard_normal((6,) + cs).astype(np.float32)
+        ws = d.model.get_weights()
+        assert len(ws) == len(tr.entries)
+        torch.cuda.synchronize()
+        vel = np.zeros(tr.flat_params.numel(), np.float32) if tr.opt_state is None else tr.opt_state[0].cpu().numpy().copy()
+        loss_ref, mae_ref, grads_ref, _ = _torch_step(layers, [(ws[i], ws[i + 1]) for i in range(0, len(ws), 2)], x, y)
+        vals = d.model.train_on_batch(x, y)
+        assert vals[0] == pytest.approx(loss_ref, rel=2e-5) and vals[1] == pytest.approx(mae_ref, rel=2e-5)
+        assert d.model.optimizer.iterations == k + 1
+        torch.cuda.synchronize()
+        vel_new = tr.opt_state[0].cpu().numpy()
+        lr_k = lr / (1. + decay * k)
+        for w0, w1, g_ref, (_, _, off, numel, shape) in zip(ws, d.model.get_weights(), grads_ref, tr.entries):
+            assert tuple(shape) == w0.shape == g_ref.shape
+            v0 = vel[off:off + numel].reshape(shape).astype(np.float64)
+            p_ref, v_ref = np_ref.sgd_keras_step(w0.astype(np.float64), v0, g_ref, k, lr=lr, momentum=mom, decay=decay)
+            g_bar = 2e-4 * max(np.abs(g_ref).max(), 1e-6) * lr_k
+            bar = g_bar + np.spacing(np.abs(p_ref).astype(np.float32)).astype(np.float64)
+            assert np.all(np.abs(w1 - p_ref) <= bar), (k, shape, float((np.abs(w1 - p_ref) / bar).max()))
+            v_bar = g_bar + 3 * 2.0 ** -24 * (np.abs(mom * v0) + np.abs(lr_k * g_ref))
+            v1 = vel_new[off:off + numel].reshape(shape)
+            assert np.all(np.abs(v1 - v_ref) <= v_bar), (k, shape, float((np.abs(v1 - v_ref) / v_bar).max()))
+            if k == 4:          # lr / (1 + 4 decay), not lr
+                p_flat, _ = np_ref.sgd_keras_step(w0.astype(np.float64), v0, g_ref, k, lr=lr, momentum=mom, decay=0.)
+                undecayed_outside = undecayed_outside or bool(np.any(np.abs(w1 - p_flat) > bar))
+    assert undecayed_outside
+    assert d.model.optimizer.iterations == 5 and d.model.optimizer.decay == pytest.approx(1e-2)
+
+
 def test_full_size_training_batch_of_520_equals_its_eight_distinct_samples():
     """A batch of 520 at 88 x 180 (65 copies of 8 samples; 1 GB per activation, 4 160 weight-gradient tiles per layer-2
     channel block, the partial-sum workspaces at their large-batch sizes) has the loss and the mean gradient of the 8
@@ -633,16 +682,17 @@ def test_captured_training_step_equals_the_eager_step(monkeypatch):
     """A batch shape seen more than twice runs as one captured hipGraph (Trainer._graph_step: forward, loss, backward and the
     Adam update with the step number in device memory).  Same kernels, same order: weights, reported loss and the step
     counter follow the eager run (the only arithmetic difference is lr_t, evaluated in double on the device instead of on
-    the host); a second batch shape gets its own graph; set_weights / evaluate in between do not disturb it."""
+    the host); a second batch shape gets its own graph; set_weights / evaluate in between do not disturb it.  SGD with momentum
+    replays as well (bit-equal weights and velocity: no device-side rate); SGD with decay never does and stays the eager run."""
     rng = np.random.default_rng(12)
     cs = (4, 16, 24)
     layers = unet_layers(cs, widths=(8, 16, 16, 16, 8))
     xs = [rng.standard_normal((n,) + cs).astype(np.float32) for n in (6, 6, 6, 4, 6, 4, 4, 6, 4, 6)]
     ys = [rng.standard_normal(x.shape).astype(np.float32) for x in xs]
 
-    def run(graph):
+    def run(graph, optimizer='adam'):
         monkeypatch.setenv('DLWP_TRAIN_GRAPH', '1' if graph else '0')
-        d = _build(layers, time_dim=2, seed=3)
+        d = _build(layers, time_dim=2, seed=3, optimizer=optimizer)
         tr = d.model._trainer
         logs = [d.model.train_on_batch(x, y) for x, y in zip(xs, ys)]
         ev = d.evaluate(xs[0], ys[0], verbose=0)
@@ -667,6 +717,30 @@ def test_captured_training_step_equals_the_eager_step(monkeypatch):
     assert np.allclose(lg, le, rtol=1e-5) and dg.model.optimizer.iterations == 1001
     for a, b in zip(dg.model.get_weights(), de.model.get_weights()):
         assert np.abs(a - b).max() <= 2e-7 * (len(xs) + 2)
+    # SGD with momentum replays too (decay 0: its rate is a launch argument).  No device-side lr_t here -- the launches and
+    # their arguments are those of the eager step: weights and velocity slot equal the eager run's bit for bit.
+    from dlwp_amd.training import SGD
+    de, tre, logs_e, ev_e = run(False, SGD(lr=0.01, momentum=0.9))
+    dg, trg, logs_g, ev_g = run(True, SGD(lr=0.01, momentum=0.9))
+    assert not tre._graphs and sorted(k[0] for k in trg._graphs) == [4, 6]
+    assert dg.model.optimizer.iterations == de.model.optimizer.iterations == len(xs) + 1
+    for a, b in zip(logs_g, logs_e):
+        assert np.allclose(a, b, rtol=1e-5, atol=1e-7), (a, b)
+    assert np.allclose(ev_g, ev_e, rtol=1e-5)
+    for a, b in zip(dg.model.get_weights(), de.model.get_weights()):
+        assert np.array_equal(a, b)
+    assert len(trg.opt_state) == 1 and torch.equal(trg.opt_state[0], tre.opt_state[0]) and trg.opt_state[0].abs().max() > 0
+    # with decay the rate changes every step: never replayed, and still the eager run
+    dd, trd, logs_d, ev_d = run(True, SGD(lr=0.01, momentum=0.9, decay=1e-2))
+    de, tre, logs_e, ev_e = run(False, SGD(lr=0.01, momentum=0.9, decay=1e-2))
+    assert not trd._graphs and not tre._graphs
+    assert dd.model.optimizer.iterations == de.model.optimizer.iterations == len(xs) + 1
+    for a, b in zip(logs_d, logs_e):
+        assert np.allclose(a, b, rtol=1e-5, atol=1e-7), (a, b)
+    for a, b in zip(dd.model.get_weights(), de.model.get_weights()):
+        assert np.array_equal(a, b)
+    assert torch.equal(trd.opt_state[0], tre.opt_state[0])
+    assert not all(np.array_equal(a, b) for a, b in zip(dd.model.get_weights(), dg.model.get_weights()))     # decay changed the run
 
 
 def test_fit_and_fit_generator_reduce_the_loss():
@@ -1526,6 +1600,52 @@ def test_keras_hdf5_checkpoint_written_here_resumes_training_where_it_stopped(tm
     for k in range(3, 6):
         la, lb = d.model.train_on_batch(x[k], x[k]), d2.model.train_on_batch(x[k], x[k])
         assert np.allclose(la, lb, rtol=1e-6, atol=1e-7)
+    for a, b in zip(d.model.get_weights(), d2.model.get_weights()):
+        assert np.abs(a - b).max() <= 1e-7
+    assert not all(np.array_equal(a, b) for a, b in zip(w_start, d2.model.get_weights()))
+
+
+def test_keras_hdf5_checkpoint_of_an_sgd_run_resumes_training_where_it_stopped(tmp_path):
+    """The same round trip for SGD(lr=0.01, momentum=0.9, decay=1e-2) with the plain 'mse' loss: the file's optimizer_weights
+    list SGD/iterations:0 and one moment per weight (Keras' order), the loaded model has the weights, the velocity slot, the
+    step count and the hyper-parameters of the saved one, and continues like the uninterrupted run (the decayed rate depends
+    on the restored count)."""
+    from dlwp_amd import hdf5_lite, util
+    from dlwp_amd.training import SGD
+    rng = np.random.default_rng(28)
+    cs = (4, 16, 24)
+    x = [rng.standard_normal((6,) + cs).astype(np.float32) for _ in range(6)]
+    d = _build(unet_layers(cs, widths=(8, 16, 16, 16, 8)), time_dim=2, seed=4, loss='mse',
+               optimizer=SGD(lr=0.01, momentum=0.9, decay=1e-2))
+    _weights_of(d.model, rng)
+    w_start = d.model.get_weights()
+    for k in range(3):
+        d.model.train_on_batch(x[k], x[k])
+    base = str(tmp_path / 'ckpt_sgd')
+    util.save_model(d, base)
+    assert hdf5_lite.is_hdf5(base + '.keras')
+    f = hdf5_lite.File(base + '.keras')
+    names = [n.decode() for n in np.asarray(f['optimizer_weights'].attrs['weight_names']).reshape(-1)]
+    n_par = len(d.model._trainer.entries)
+    assert names[0] == 'SGD/iterations:0' and len(names) == 1 + n_par
+    assert int(np.asarray(f['optimizer_weights'][names[0]][...]).reshape(-1)[0]) == 3
+    for nm, (_, _, off, numel, shape) in zip(names[1:], d.model._trainer.entries):      # one moment per weight, in its shape
+        stored = np.asarray(f['optimizer_weights'][nm][...])
+        assert stored.shape == tuple(shape)
+        assert np.array_equal(stored.reshape(-1), d.model._trainer.opt_state[0][off:off + numel].cpu().numpy())
+    d2 = util.load_model(base)
+    opt2 = d2.model.optimizer
+    assert isinstance(opt2, SGD) and d2.model.loss == 'mse'
+    assert opt2.iterations == 3 and opt2.lr == pytest.approx(0.01) and opt2.momentum == pytest.approx(0.9) \
+        and opt2.decay == pytest.approx(1e-2)
+    assert all(np.array_equal(a, b) for a, b in zip(d.model.get_weights(), d2.model.get_weights()))
+    assert len(d2.model._trainer.opt_state) == 1 and d.model._trainer.opt_state[0].abs().max() > 0
+    for a, b in zip(d.model._trainer.opt_state, d2.model._trainer.opt_state):
+        assert torch.equal(a, b)
+    for k in range(3, 6):
+        la, lb = d.model.train_on_batch(x[k], x[k]), d2.model.train_on_batch(x[k], x[k])
+        assert np.allclose(la, lb, rtol=1e-6, atol=1e-7)
+    assert d.model.optimizer.iterations == d2.model.optimizer.iterations == 6
     for a, b in zip(d.model.get_weights(), d2.model.get_weights()):
         assert np.abs(a - b).max() <= 1e-7
     assert not all(np.array_equal(a, b) for a, b in zip(w_start, d2.model.get_weights()))

@@ -109,6 +109,69 @@ def test_adam_keras_form():
     assert np.allclose(p1, -1e-3, rtol=5e-3)      # eps=1e-7 shows at |g|=1e-3
 
 
+def test_sgd_keras_form():
+    """np_ref.sgd_keras_step (float64) against torch_ref's float32 in-place form over five decayed momentum steps, and the
+    update written out by hand: the first step from zero velocity is p - lr g, the second uses lr / (1 + decay)."""
+    rng = np.random.default_rng(17)
+    p = rng.standard_normal(50)
+    vel = np.zeros(50)
+    pt, vt = (torch.tensor(a, dtype=torch.float32) for a in (p, vel))
+    for it in range(5):
+        g = rng.standard_normal(50)
+        p, vel = np_ref.sgd_keras_step(p, vel, g, it, lr=0.01, momentum=0.9, decay=1e-2)
+        torch_ref.sgd_keras_step(pt, vt, torch.tensor(g, dtype=torch.float32), it, lr=0.01, momentum=0.9, decay=1e-2)
+    assert np.abs(p - pt.numpy()).max() < 1e-6 and np.abs(vel - vt.numpy()).max() < 1e-6
+    g = np.array([1e-3, 1., -1e3])
+    p1, v1 = np_ref.sgd_keras_step(np.ones(3), np.zeros(3), g, 0, lr=0.5, momentum=0.9, decay=1.)
+    assert np.array_equal(v1, -0.5 * g) and np.array_equal(p1, 1. - 0.5 * g)
+    p2, v2 = np_ref.sgd_keras_step(p1, v1, g, 1, lr=0.5, momentum=0.9, decay=1.)
+    assert np.allclose(v2, 0.9 * v1 - 0.25 * g, rtol=1e-15) and np.allclose(p2, p1 + v2, rtol=1e-15)
+    p3, v3 = np_ref.sgd_keras_step(p1, v1, g, 1, lr=0.5)            # momentum 0: the velocity is forgotten
+    assert np.array_equal(v3, -0.5 * g)
+
+
+def kink_free_gate_inputs(rng, shape, first):
+    """Gate pre-activations whose float32 sum zx + zh is exact and at least 2^-7 away from every kink of hard_sigmoid
+    (|z| = 2.5) and relu (0): zx multiples of 2^-6 and zh odd multiples of 2^-7, both in [-2, 2]; on the first step (no zh) zx
+    odd multiples of 2^-7 in [-4, 4].  Returns float64 (zx, zh | None)."""
+    if first:
+        return (2 * rng.integers(-256, 256, size=shape) + 1) * 2.0 ** -7, None
+    return rng.integers(-128, 129, size=shape) * 2.0 ** -6, (2 * rng.integers(-128, 128, size=shape) + 1) * 2.0 ** -7
+
+
+@pytest.mark.parametrize('rec_act', ['hard_sigmoid', 'sigmoid'])
+@pytest.mark.parametrize('act', ['linear', 'tanh', 'relu'])
+def test_convlstm_gate_function_gradcheck(act, rec_act):
+    """torch_ref.convlstm_gates is the autograd source the backward kernel is compared with: its analytic gradient against
+    finite differences in float64, first and later step, at points away from the kinks; and the function itself against the
+    cell update inside np_ref.conv_lstm2d (1x1 identity kernels turn the convolutions into the pre-activations)."""
+    rng = np.random.default_rng(23)
+    n, f, h, w = 2, 3, 2, 3
+    for first in (True, False):
+        zx, zh = kink_free_gate_inputs(rng, (n, 4 * f, h, w), first)
+        z = zx + (0 if zh is None else zh)
+        assert np.abs(np.abs(z) - 2.5).min() >= 2.0 ** -7 and np.abs(z).min() >= 2.0 ** -7
+        cp = None if first else rng.standard_normal((n, f, h, w))
+        if cp is not None:      # c = f c' + i act(z_c) stays off relu's kink as well: away from 0, or exactly 0 where the gates
+            # that feed it are saturated (c is constant around such a point, and relu has gradient 0 on both sides of it)
+            c0, _ = torch_ref.convlstm_gates(torch.tensor(zx), torch.tensor(zh), torch.tensor(cp), act, rec_act)
+            assert c0[c0 != 0].abs().min() > 1e-4
+        ins = [torch.tensor(a, dtype=torch.float64, requires_grad=True) for a in (zx, zh, cp) if a is not None]
+        if first:
+            fn = lambda a: torch_ref.convlstm_gates(a, None, None, act, rec_act)           # noqa: E731
+        else:
+            fn = lambda a, b, c: torch_ref.convlstm_gates(a, b, c, act, rec_act)          # noqa: E731
+        assert torch.autograd.gradcheck(fn, ins, eps=1e-6, atol=1e-7, rtol=1e-6)
+    # two steps of np_ref.conv_lstm2d with identity 1x1 kernels: step 0 sees zx = x_0, step 1 sees x_1 + (h_0, h_0, h_0, h_0)
+    x = rng.standard_normal((n, 2, 4 * f, h, w))
+    k = np.eye(4 * f).reshape(1, 1, 4 * f, 4 * f)
+    r = np.tile(np.eye(f), (1, 4)).reshape(1, 1, f, 4 * f)
+    want = np_ref.conv_lstm2d(x, k, r, np.zeros(4 * f), activation=act, recurrent_activation=rec_act)
+    c0, h0 = torch_ref.convlstm_gates(torch.tensor(x[:, 0]), None, None, act, rec_act)
+    c1, h1 = torch_ref.convlstm_gates(torch.tensor(x[:, 1]), h0.repeat(1, 4, 1, 1), c0, act, rec_act)
+    assert np.abs(want[:, 0] - h0.numpy()).max() < 1e-14 and np.abs(want[:, 1] - h1.numpy()).max() < 1e-14
+
+
 def test_conv_lstm2d_numpy_and_torch_restatements_agree():
     """ConvLSTM2D parity is unpinned (Keras is absent): the two independent restatements -- numpy direct sums and
     torch-CPU F.conv2d -- must at least agree with each other, through the reference's recurrent front end
