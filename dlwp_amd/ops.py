@@ -812,6 +812,8 @@ def conv2d_bwd_weight_pooled(x, y, dpool, dw, db, cd, xs, act, accumulate=False,
 def act_bwd(y, dy, act, out=None):
     _check_f32(y, dy)
     dz = out if out is not None else torch.empty_like(dy)
+    if dy.numel() == 0:     # (an empty tensor has no address for the C ABI to check)
+        return dz
     _lib.check(_lib.lib.dlwp_act_bwd(_lib.handle(_dev(dy)), _ptr(y), _ptr(dy), _ptr(dz), dy.numel(), int(act), _lib.F32,
                                      _stream(dy)))
     return dz
@@ -820,6 +822,8 @@ def act_bwd(y, dy, act, out=None):
 def bias_grad(dz, db, c, c_off=0, ws_key=None):
     _check_f32(dz, db)
     n, c_total, h, w = dz.shape
+    if dz.numel() == 0:     # the sum of nothing
+        return db.zero_()
     ws = workspace2(dz.device, _lib.lib.dlwp_bias_grad_workspace(int(c)), ws_key)
     _lib.check(_lib.lib.dlwp_bias_grad(_lib.handle(_dev(dz)), _ptr(dz), _ptr(db), n, int(c), int(c_off), c_total, h * w,
                                        _ptr(ws), ws.numel(), _lib.F32, _stream(dz)))
@@ -831,6 +835,9 @@ def act_bwd_bias_grad(y, dy, act, db, c, c_off=0, out=None, ws_key=None):
     _check_f32(y, dy, db)
     dz = out if out is not None else torch.empty_like(dy)
     n, c_total, h, w = dy.shape
+    if dy.numel() == 0:     # nothing to write but the sum of nothing
+        db.zero_()
+        return dz
     ws = workspace2(dy.device, _lib.lib.dlwp_bias_grad_workspace(int(c)), ws_key)
     _lib.check(_lib.lib.dlwp_act_bwd_bias_grad(_lib.handle(_dev(dy)), _ptr(y), _ptr(dy), _ptr(dz), _ptr(db), n, int(c),
                                                int(c_off), c_total, h * w, int(act), _ptr(ws), ws.numel(), _lib.F32,
@@ -838,13 +845,19 @@ def act_bwd_bias_grad(y, dy, act, db, c, c_off=0, out=None, ws_key=None):
     return dz
 
 
-def pool_act_bwd_bias_grad(y, dp, act, db=None, ws_key=None):
+def pool_act_bwd_bias_grad(y, dp, act, db=None, ws_key=None, out=None):
     """Backward of MaxPooling2D(2) + activation (+ bias gradient) of the convolution that produced y, in one pass:
-    returns dz (shape of y) from the pooled tensor's gradient dp."""
-    _check_f32(y, dp, db)
+    returns dz (shape of y; `out`, which must not be y, or a new tensor) from the pooled tensor's gradient dp."""
+    _check_f32(y, dp, db, out)
     n, c, h, w = y.shape
     assert tuple(dp.shape) == (n, c, h // 2, w // 2) and y.is_contiguous() and dp.is_contiguous()
-    dz = torch.empty_like(y)
+    if out is not None and tuple(out.shape) != tuple(y.shape):
+        raise ValueError('pool_act_bwd_bias_grad: out %r does not have the shape of y %r' % (tuple(out.shape), tuple(y.shape)))
+    dz = out if out is not None else torch.empty_like(y)
+    if y.numel() == 0:      # (dlwp_pool_act_bwd_bias_grad returns before it writes db)
+        if db is not None:
+            db.zero_()
+        return dz
     ws = workspace2(y.device, _lib.lib.dlwp_bias_grad_workspace(int(c)), ws_key)
     _lib.check(_lib.lib.dlwp_pool_act_bwd_bias_grad(_lib.handle(_dev(y)), _ptr(y), _ptr(dp), _ptr(dz),
                                                     _ptr(db), _lib.Shape4(n, c, h, w), int(act),
@@ -855,6 +868,8 @@ def pool_act_bwd_bias_grad(y, dp, act, db=None, ws_key=None):
 def mse_mae(y_pred, y_true, out2, dy=None, loss_weight=1.0, ws_key=None):
     """out2 (device, 2 floats) <- [mse, mae]; dy <- loss_weight * 2 (y_pred - y_true) / numel."""
     _check_f32(y_pred, y_true, out2, dy)
+    if y_pred.numel() == 0:
+        raise ValueError('mse_mae: the loss of an empty batch is undefined')
     d = _dev(y_pred)
     h = _lib.handle(d)
     need = _lib.lib.dlwp_mse_mae_workspace(h)
@@ -872,6 +887,8 @@ def mse_mae_phase(y_phase, y_true, out2, dz=None, db=None, loss_weight=1.0, ws_k
     f = f4 // 4
     if f4 != 4 * f or tuple(y_true.shape) != (n, f, 2 * hh, 2 * ww):
         raise ValueError('mse_mae_phase: phase tensor %r does not match the target %r' % (tuple(y_phase.shape), tuple(y_true.shape)))
+    if y_phase.numel() == 0:
+        raise ValueError('mse_mae_phase: the loss of an empty batch is undefined')
     h = _lib.handle(_dev(y_phase))
     ws = workspace(y_phase.device, _lib.lib.dlwp_mse_mae_phase_workspace(f), ws_key)
     _lib.check(_lib.lib.dlwp_mse_mae_phase(h, _ptr(y_phase), _ptr(y_true), n, f, hh, ww, _ptr(out2), _ptr(dz), _ptr(db),
@@ -883,6 +900,8 @@ def loss_custom(y_pred, y_true, stats7, dy=None, loss_weight=1.0, mean=None, row
     """The reference's custom losses (include/dlwp_hip.h: dlwp_loss_custom).  y: (n, c, h, w) device tensors."""
     _check_f32(y_pred, y_true, stats7, dy, mean, row_weights)
     n, c, hh, ww = y_pred.shape
+    if y_pred.numel() == 0:
+        raise ValueError('loss_custom: the loss of an empty batch is undefined')
     d = _dev(y_pred)
     h = _lib.handle(d)
     ws = workspace(y_pred.device, _lib.lib.dlwp_loss_workspace(h, n, c))

@@ -793,3 +793,119 @@ def latitude_weights(lats, weighting='cosine'):
     if weighting == 'midlatitude':
         w = w + 0.5 * np.sin(2 * lat) ** 2
     return w
+
+
+# ------------------------------------------------------------------------------------------------------------------ #
+# the helper kernels of the training step (csrc/train_ops.hip), float64  (tests/test_train_ops_cpu.py, test_gpu_train_ops.py)
+# ------------------------------------------------------------------------------------------------------------------ #
+
+def act_bwd(y, dy, activation):
+    """dlwp_act_bwd: dz = dy * act'(y) from the layer OUTPUT y (tanh: 1 - y^2; relu: y > 0; linear: dy), float64."""
+    dy = np.asarray(dy, np.float64)
+    if activation in (None, 'linear'):
+        return dy.copy()
+    y = np.asarray(y, np.float64)
+    if activation == 'relu':
+        return np.where(y > 0, dy, 0.0)
+    return activation_grad(y, dy, activation)
+
+
+def channel_sum(dz, c_off=0, c=None):
+    """dlwp_bias_grad: the sum over (n, h, w) of channels [c_off, c_off + c) of an (n, c_total, h, w) tensor."""
+    dz = np.asarray(dz, np.float64)
+    c = dz.shape[1] - c_off if c is None else c
+    return dz[:, c_off:c_off + c].sum(axis=(0, 2, 3))
+
+
+def pool_act_bwd(y, dp, activation):
+    """dlwp_pool_act_bwd_bias_grad without the sum: the pooled tensor's gradient dp (n, c, h // 2, w // 2) goes to the first maximum
+    of each 2x2 window of y in row-major order, times act'(y) there; an odd last row or column gets zero."""
+    y = np.asarray(y, np.float64)
+    routed = maxpool2_grad(y, dp)
+    if activation in (None, 'linear'):
+        return routed
+    slope = (1. - y * y) if activation == 'tanh' else (y > 0).astype(np.float64)
+    return np.where(routed != 0, routed * slope, 0.0)
+
+
+def mse_mae(y_pred, y_true, loss_weight=1.0):
+    """dlwp_mse_mae: (sum d^2, sum |d|, mse, mae, dy = loss_weight * 2 d / numel) with d = y_pred - y_true."""
+    d = np.asarray(y_pred, np.float64) - np.asarray(y_true, np.float64)
+    s2, s1 = float(np.sum(d * d)), float(np.sum(np.abs(d)))
+    return s2, s1, s2 / d.size, s1 / d.size, loss_weight * 2.0 * d / d.size
+
+
+def space_to_depth2(y):
+    """(N, F, 2H, 2W) -> (N, 4F, H, W), channel (2a + b) F + co holding pixel (2i + a, 2j + b): the inverse of depth_to_space2."""
+    return np.concatenate([y[:, :, a::2, b::2] for a in (0, 1) for b in (0, 1)], axis=1)
+
+
+def mse_mae_phase(y_phase, y_true, loss_weight=1.0):
+    """dlwp_mse_mae_phase: mse_mae of the interleaved phase tensor against the target, the gradient in PHASE layout, and its
+    per-phase-channel sums (the bias gradient of a linear output layer)."""
+    f = y_true.shape[1]
+    s2, s1, v2, v1, dy = mse_mae(depth_to_space2(np.asarray(y_phase, np.float64), f), y_true, loss_weight)
+    dz = space_to_depth2(dy)
+    return s2, s1, v2, v1, dz, channel_sum(dz)
+
+
+def custom_loss(yp, yt, mean, row_w, kind, regularize, loss_weight, sums=None):
+    """dlwp_loss_custom (its header comment in csrc/train_ops.hip) on (n, c, h, w) fields, float64.
+        y' = w[h] y;  P = yp' - M, T = yt' - M;  S_pt, S_pp, S_tt = sum P T, sum P^2, sum T^2;  a = S_pt / sqrt(S_pp S_tt)
+        reg: 0 none, 1 mse(y'), 2 mae(y'), 3 |(St - Sp) / St| over everything, 4 the mean over (n, c) planes of that per plane,
+             Sp, St the sums of yp', yt'
+        kind 0: loss = mse(y');  kind 1: loss = reg - a
+    Returns (stats, dy, aux): stats = [loss, mse(y), mae(y), S_pt, S_pp, S_tt, reg] and dy = loss_weight * dloss / dyp in closed
+    form: with g = dloss / dyp',
+        kind 0: g = 2 (yp' - yt') / numel
+        kind 1: g = -(T - (S_pt / S_pp) P) / sqrt(S_pp S_tt)  +  2 (yp' - yt') / numel | sign(yp' - yt') / numel |
+                    -sign(q) / St | -sign(q_plane) / (St_plane planes),   q = (St - Sp) / St
+    and dy = loss_weight w g.  aux holds the sums behind reg 3 / 4: 'extra' = (Sp, St), 'plane' = (planes, 2) of (Sp, St).
+    sums: {'spt', 'spp', 'stt', 'extra', 'plane'} to evaluate the GRADIENT from (a kernel's own float32 sums); the stats are
+    always this function's own."""
+    yp, yt = np.asarray(yp, np.float64), np.asarray(yt, np.float64)
+    n, c, h, w_ = yp.shape
+    numel = yp.size
+    w = np.ones((1, 1, 1, 1)) if row_w is None else np.asarray(row_w, np.float64).reshape(1, 1, h, 1)
+    m = 0.0 if mean is None else np.asarray(mean, np.float64).reshape(1, c, h, w_)
+    d = yp - yt
+    pw, tw = w * yp, w * yt
+    dw = pw - tw
+    P, T = pw - m, tw - m
+    spt, spp, stt = float(np.sum(P * T)), float(np.sum(P * P)), float(np.sum(T * T))
+    plane = np.stack([pw.sum(axis=(2, 3)).reshape(-1), tw.sum(axis=(2, 3)).reshape(-1)], axis=1)
+    extra = np.array([pw.sum(), tw.sum()])
+    aux = {'extra': extra, 'plane': plane}
+    mse_w = float(np.sum(dw * dw)) / numel
+    reg = 0.0
+    if kind == 0:
+        loss = mse_w
+    else:
+        if regularize == 1:
+            reg = mse_w
+        elif regularize == 2:
+            reg = float(np.sum(np.abs(dw))) / numel
+        elif regularize == 3:
+            reg = abs((extra[1] - extra[0]) / extra[1])
+        elif regularize == 4:
+            reg = float(np.mean(np.abs((plane[:, 1] - plane[:, 0]) / plane[:, 1])))
+        loss = reg - spt / math.sqrt(spp * stt)
+    stats = np.array([loss, float(np.sum(d * d)) / numel, float(np.sum(np.abs(d))) / numel, spt, spp, stt, reg])
+    if sums is not None:
+        spt, spp, stt = (float(sums[k]) for k in ('spt', 'spp', 'stt'))
+        extra = np.asarray(sums.get('extra', extra), np.float64)
+        plane = np.asarray(sums.get('plane', plane), np.float64)
+    if kind == 0:
+        g = 2.0 * dw / numel
+    else:
+        g = -(T - (spt / spp) * P) / math.sqrt(spp * stt)
+        if regularize == 1:
+            g = g + 2.0 * dw / numel
+        elif regularize == 2:
+            g = g + np.sign(dw) / numel
+        elif regularize == 3:
+            g = g - np.sign((extra[1] - extra[0]) / extra[1]) / extra[1]
+        elif regularize == 4:
+            t2 = -np.sign((plane[:, 1] - plane[:, 0]) / plane[:, 1]) / (plane[:, 1] * (n * c))
+            g = g + t2.reshape(n, c, 1, 1)
+    return stats, loss_weight * w * g, aux
