@@ -909,3 +909,83 @@ def custom_loss(yp, yt, mean, row_w, kind, regularize, loss_weight, sums=None):
             t2 = -np.sign((plane[:, 1] - plane[:, 0]) / plane[:, 1]) / (plane[:, 1] * (n * c))
             g = g + t2.reshape(n, c, 1, 1)
     return stats, loss_weight * w * g, aux
+
+
+# ------------------------------------------------------------------------------------------------------------------ #
+# one convolution layer's gradients as the C ABI's entry points write them (tests/test_conv_grads_cpu.py, test_gpu_conv_grads.py)
+# ------------------------------------------------------------------------------------------------------------------ #
+
+SRC_DIRECT, SRC_UPSAMPLE2, SRC_MAXPOOL2 = 0, 1, 2
+
+
+def conv_layer(k, dil=1, pads=None, mode_h=PAD_ZERO, mode_w=PAD_WRAP, src=SRC_DIRECT, in_c_off=0, in_c=None, out_c_off=0, out_c=None):
+    """A layer descriptor for conv_layer_grads: kernel size, dilation, halo (top, bottom, left, right; default 'same') and its modes,
+    source mode, and the channel windows [in_c_off, +in_c) of the stored input / [out_c_off, +out_c) of the output gradient that the
+    layer reads (None: all channels)."""
+    p = dil * (k - 1) // 2
+    return dict(k=int(k), dil=int(dil), pads=tuple(pads) if pads is not None else (p, p, p, p), mode_h=mode_h, mode_w=mode_w, src=src,
+                in_c_off=in_c_off, in_c=in_c, out_c_off=out_c_off, out_c=out_c)
+
+
+def _valid_conv_grads(xp, w, dz, d, want_dw, want_dx, use_torch):
+    """dw, dxp of the valid cross-correlation of conv2d above in float64: the einsum sums, or torch's CPU float64 convolution
+    gradients of the same operands (tests/test_conv_grads_cpu.py holds the two within 1e-12 of each other)."""
+    kh, kw = w.shape[:2]
+    ho, wo = dz.shape[-2:]
+    if use_torch:
+        import torch
+        from torch.nn import grad as tgrad
+        xt, zt = torch.from_numpy(np.ascontiguousarray(xp)), torch.from_numpy(np.ascontiguousarray(dz))
+        wt = torch.from_numpy(np.ascontiguousarray(w.transpose(3, 2, 0, 1)))
+        dw = tgrad.conv2d_weight(xt, wt.shape, zt, dilation=d).numpy().transpose(2, 3, 1, 0) if want_dw else None
+        dxp = tgrad.conv2d_input(xt.shape, wt, zt, dilation=d).numpy() if want_dx else None
+        return dw, dxp
+    dw = np.zeros(w.shape) if want_dw else None
+    dxp = np.zeros(xp.shape) if want_dx else None
+    for u in range(kh):
+        for v in range(kw):
+            sl = (slice(None), slice(None), slice(u * d, u * d + ho), slice(v * d, v * d + wo))
+            if want_dw:
+                dw[u, v] = np.einsum('nchw,nohw->co', xp[sl], dz, optimize=True)
+            if want_dx:
+                dxp[sl] += np.einsum('nohw,co->nchw', dz, w[u, v], optimize=True)
+    return dw, dxp
+
+
+def conv_layer_grads(x, w_hwio, dz, layer, stored=False, act_in=None, want=('dw', 'dx'), absolute=False, use_torch=False):
+    """What dlwp_conv2d_bwd_weight and the dlwp_conv2d_bwd_data family write for one layer, float64.
+        x: the STORED input (n, c_total, hs, ws), channels [in_c_off, +in_c) read; dz: (n, oc_total, ho, wo), channels
+        [out_c_off, +out_c) read; w_hwio (k, k, in_c, out_c).
+    Returns a dict: 'dw' (k, k, in_c, out_c); 'dx' with respect to the tensor the entry point writes -- the convolution's input after
+    the source transform, (n, in_c, hin, win) (the caller applies maxpool2_grad / upsample2_grad), or with stored=True the stored tensor of
+    an up-sampled source (2 x 2 sums); act_in 'tanh' / 'relu': 'dx' times act'(x) (x is that activation's output) and 'db' its channel
+    sums (dlwp_conv2d_bwd_data_act).
+    absolute=True: the same sums over absolute values -- sum |x| |dz| per weight, sum |dz| |w| per dx element (before the act' factor,
+    which is at most 1), 'db' the sum of those -- the scale of every rounding-error bound and of the exactness condition."""
+    x, w, dz = (np.asarray(a, np.float64) for a in (x, w_hwio, dz))
+    kh, kw, cin, cout = w.shape
+    assert kh == kw == layer['k'] and (layer['in_c'] or x.shape[1]) == cin and (layer['out_c'] or dz.shape[1]) == cout
+    xw = x[:, layer['in_c_off']:layer['in_c_off'] + cin]
+    dzw = dz[:, layer['out_c_off']:layer['out_c_off'] + cout]
+    xt = {SRC_DIRECT: xw, SRC_UPSAMPLE2: upsample2(xw), SRC_MAXPOOL2: maxpool2(xw)}[layer['src']]
+    if absolute:
+        xt, w, dzw = np.abs(xt), np.abs(w), np.abs(dzw)
+    xp = pad2d_modes(xt, layer['pads'], layer['mode_h'], layer['mode_w'])
+    d = layer['dil']
+    assert dzw.shape[2:] == (xp.shape[2] - d * (kh - 1), xp.shape[3] - d * (kw - 1)), (dzw.shape, xp.shape)
+    dw, dxp = _valid_conv_grads(xp, w, dzw, d, 'dw' in want, 'dx' in want, use_torch)
+    out = {}
+    if dw is not None:
+        out['dw'] = dw
+    if dxp is not None:
+        dx = pad2d_modes_grad(dxp, xt.shape, layer['pads'], layer['mode_h'], layer['mode_w'])
+        if stored:
+            assert layer['src'] == SRC_UPSAMPLE2
+            dx = upsample2_grad(dx)
+        if act_in is not None:
+            assert layer['src'] == SRC_DIRECT
+            if not absolute:
+                dx = act_bwd(xw, dx, act_in)
+            out['db'] = dx.sum(axis=(0, 2, 3))
+        out['dx'] = dx
+    return out

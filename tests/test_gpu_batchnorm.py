@@ -206,7 +206,10 @@ def _check_step(d, specs, x, y, p, tol=3e-4, first_kernel_tol=None):
     """one train_on_batch against float64 autograd: loss, every gradient, the moving statistics.  first_kernel_tol: the bound of
     the first layer's kernel gradient.  That layer reads the 4-channel model input; its weight gradient is a sum over every
     position of the batch, and at 64 samples of the 88 x 180 grid the library's 4-channel weight-gradient kernel misses the
-    float64 sum by ~4e-5 of its size already without normalisation (2e-7 on every other layer).  Behind a normalisation the
+    float64 sum by ~4e-5 of its size already without normalisation (2e-7 on every other layer).  That is round-off, not a wrong
+    term: tests/test_gpu_conv_grads.py holds this kernel bit-equal to float64 on integer inputs at this size and measures its error on
+    random reals at 0.04 u A (A = sum |x| |dz|, u = 2^-24; 4e-7 of max |dw| where max |dw| is 5e-3 of A); here x is the independent
+    model input, the sum cancels to ~1e-4 of A, and the same 0.04 u A is 4e-5 of what is left.  Behind a normalisation the
     gradient of that layer's output has the batch mean and the correlation with the normalised tensor projected out: the sum
     cancels ~20x more, the same absolute error is ~1e-3 of it."""
     logs = d.model.train_on_batch(x, y)
