@@ -7,7 +7,9 @@ all-reduce of ONE flat gradient buffer per step (RCCL over xGMI on the GPU box, 
 Reference: keras Model.fit / fit_generator / evaluate as driven by DLWP/model/models.py:188-228, 303-316 and
 examples/train.py:240,258-263,274; loss / metric / optimizer strings of examples/train.py:240.
 """
+import contextlib
 import ctypes
+import gc
 import os
 import time
 
@@ -165,6 +167,23 @@ class _StepHandle(object):
             self.h = None
         except Exception:  # noqa: BLE001
             pass
+
+
+@contextlib.contextmanager
+def _no_gc():
+    """No garbage collection while a step is recorded or captured: a collection cycle that finalises an OLD model's memory pool,
+    graphs, streams, events or device memory (hipGraphExecDestroy, hipStreamDestroy, hipFree ...) inside the recording's
+    use_mem_pool block or in the middle of a capture aborts the process or leaves a graph that crashes at launch (r3: seen as
+    'Fatal Python error: Aborted ... Garbage-collecting' inside _capture_step and under dlwp_stream_wait, and as segmentation
+    faults in replay, 3 of 7 full test runs, once small steps were captured by default).  Collects first."""
+    gc.collect()
+    was_on = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was_on:
+            gc.enable()
 
 
 class _PhaseGrad(object):
@@ -622,414 +641,12 @@ class Trainer(object):
 
     # -- backward ------------------------------------------------------------------------------------------------------ #
     def _backward(self, x, outs, dys, prep=None):
-        """prep (the folded step, _fold_ok): prepared data-gradient operands, a workspace per deferred final sum, the weight
-        gradients on the side stream; the caller brackets forward + backward with ops.reductions_begin / _flush and runs
-        the returned callables (work that needs the final sums) after the flush."""
-        from . import _lib, ops
-        plan = self.plan
-        n = x.shape[0]
-        post = []
-        main = torch.cuda.current_stream(self.device) if prep is not None else None
-        if prep is not None and self._side is None:
-            self._ensure_side_streams()
-        sides = self._side if prep is not None else None
-        if sides is not None and torch.cuda.is_current_stream_capturing():
-            # inside a captured step everything stays on ONE stream: replaying graphs with forked branches crashed inside
-            # hipGraphLaunch now and then (r3: 2 of 3 full test runs), and the forks bought little there (0.49 vs ~0.47 ms at 8
-            # samples: a fork / join costs ~10 us in a graph).  The eager step keeps the side streams (batch 64: 1.78 -> 1.68 ms).
-            sides = None
-        # Weight gradients leave the critical path (activation backward -> data gradient -> ...): they are queued and launched
-        # on side streams in TWO batches with one fork each -- a fork / join costs ~10 us inside a captured graph
-        # (profiles/r3_train_b8_timeline.txt): the first half, one after the other, beside the second half of the chain; the
-        # rest in parallel behind it.
-        wq, used = [], []
-        n_wgrad = sum(1 for op in plan.ops if op.kind == 'conv')
-        queued = [0]
-
-        def launch_queued(parallel):
-            started = set()
-            for i, fn in enumerate(wq):
-                st = sides[i % len(sides)] if parallel else sides[0]
-                if id(st) not in started:
-                    ops.stream_wait(st, main)    # behind everything issued on the main stream so far
-                    started.add(id(st))
-                    if st not in used:
-                        used.append(st)
-                with torch.cuda.stream(st):
-                    fn()
-            del wq[:]
-
-        # (r3, eager steps: every weight gradient forks as soon as its operands exist -- the two-batch rule above was made for
-        #  forks inside a captured graph, which is single-stream now; batch 64: the last layers' weight gradients no longer pile
-        #  up behind the end of the chain.  DLWP_WGRAD_FORKS=batch keeps the two batches)
-        each = os.environ.get('DLWP_WGRAD_FORKS', 'each') != 'batch'
-
-        def on_side(fn):
-            if sides is None:
-                return fn()
-            if each:
-                st = sides[queued[0] % len(sides)]
-                queued[0] += 1
-                ops.stream_wait(st, main)
-                if st not in used:
-                    used.append(st)
-                with torch.cuda.stream(st):
-                    fn()
-                return None
-            wq.append(fn)
-            queued[0] += 1
-            if queued[0] == (n_wgrad + 1) // 2:
-                launch_queued(False)
-        # r4: where the step replays as ONE hipGraph on one stream (small batches: every launch under a round of workgroups), a
-        # layer's weight gradient and its data gradient -- both read dz, neither the other's output -- leave in one launch
-        # (ops.pair_begin / pair_end, csrc/conv_pair.hip).  The pair opens in front of the weight gradient and closes behind the data
-        # gradient's convolution; what is issued in between (bias gradient) depends on neither.
-        can_pair = (prep is not None and os.environ.get('DLWP_TRAIN_PAIR', '1') != '0' and self._graph_ok(int(n)) == 'graph')
-        pair_open = [False]
-
-        def pair_begin():
-            if can_pair and not pair_open[0]:
-                ops.pair_begin(self.device)
-                pair_open[0] = True
-
-        def pair_end():
-            if pair_open[0]:
-                pair_open[0] = False
-                ops.pair_end(self.device)
-        bufs = self.model.train_executor.scratch(n)
-        x = x.reshape((n,) + plan._in_store)
-
-        def tensor(i):
-            if i >= 0:
-                return bufs[i]
-            return x if i == P.STATE_IN else outs[-2 - i]
-
-        grads = {}          # buffer id -> gradient tensor
-        written = {}        # buffer id -> list of (c_off, c) windows already holding a gradient
-
-        def overlaps(buf, c_off, c):
-            return any(not (c_off + c <= o or o + k <= c_off) for o, k in written.get(buf, []))
-
-        # buffer id -> gradient of its MaxPooling2D(2) image, when that is the only gradient so far: the producing
-        # convolution then takes pooling + activation backward (+ bias gradient) in one pass
-        pending_pool = {}
-
-        def materialise(buf):
-            gp = pending_pool.pop(buf, None)
-            if gp is not None:
-                deposit(buf, 0, gp.shape[1], ops.maxpool2_bwd(tensor(buf), gp))
-
-        def grad_of(buf):
-            materialise(buf)
-            g = grads.get(buf)
-            if g is None:
-                g = torch.empty_like(tensor(buf))
-                grads[buf] = g
-            return g
-
-        preact = set()       # buffers whose gradient is already a PRE-activation gradient (dlwp_conv2d_bwd_data_act)
-        phase_db = {}        # convolution op index -> bias gradient of its phase channels, already summed with the loss
-        for o, dy in enumerate(dys):
-            if isinstance(dy, _PhaseGrad):     # the gradient arrives on the phase channels: the 'd2s' op has no adjoint to run
-                grads[dy.buf] = dy.dz
-                written[dy.buf] = [(0, dy.dz.shape[1])]
-                if dy.db is not None:
-                    phase_db[dy.conv_k] = dy.db
-                continue
-            grads[P.OUT(o)] = dy
-            written[P.OUT(o)] = [(0, dy.shape[1])]
-
-        def deposit(buf, c_off, c, dense):
-            """Put `dense` (n, c, h, w) into window [c_off, +c) of grad[buf]: overwrite on first touch, add after."""
-            materialise(buf)
-            if grads.get(buf) is None and c_off == 0 and tuple(dense.shape) == tuple(tensor(buf).shape) and \
-                    dense.is_contiguous():
-                grads[buf] = dense            # first gradient of the whole tensor: adopt it, no copy
-                written[buf] = [(0, c)]
-                return
-            g = grad_of(buf)
-            full = c_off == 0 and c == g.shape[1]
-            if not overlaps(buf, c_off, c):
-                if full:
-                    if dense.data_ptr() != g.data_ptr():
-                        self._foreign = True
-                        g.view(-1).copy_(dense.reshape(-1))
-                else:
-                    ops.copy_channels(dense.reshape((n, c) + tuple(g.shape[2:])), g, c, 0, c_off)
-                written.setdefault(buf, []).append((c_off, c))
-            elif full and written[buf] == [(0, g.shape[1])]:
-                ops.axpby(dense.reshape(-1), g.view(-1), 1.0, 1.0)
-            elif all(any(o <= ch < o + k for o, k in written[buf]) for ch in range(c_off, c_off + c)):
-                # the window already holds a gradient everywhere (e.g. h_{t-1}: read by the next layer as part of the
-                # whole sequence AND by the recurrent convolution of step t): extract, add, put back
-                cur = torch.empty((n, c) + tuple(g.shape[2:]), dtype=torch.float32, device=self.device)
-                ops.copy_channels(g, cur, c, c_off, 0)
-                ops.axpby(dense.reshape(-1), cur.view(-1), 1.0, 1.0)
-                ops.copy_channels(cur, g, c, 0, c_off)
-            else:
-                raise NotImplementedError('partially overlapping channel windows in the backward pass')
-
-        touched_layers = set()
-        descs = self.model.train_executor._descriptors()
-        for k, (op, d) in reversed(list(enumerate(zip(plan.ops, descs)))):
-            key = (lambda what, k=k: (what, k)) if prep is not None else (lambda what: None)   # a scratch per deferred sum
-            pooled_grad = None
-            if op.dst in pending_pool:
-                lay = op.layer if op.kind == 'conv' else None
-                if (lay is not None and op.wparam is None and op.out_c_off == 0 and
-                        op.conv_geometry[0] == tensor(op.dst).shape[1] and
-                        (lay.bias is None or id(lay) not in touched_layers)):
-                    pooled_grad = pending_pool.pop(op.dst)
-                else:
-                    materialise(op.dst)
-            if op.dst not in grads and pooled_grad is None:
-                continue                      # nothing downstream of this op contributes to the loss
-            gD = grads.get(op.dst)
-            src = tensor(op.src)
-            if op.kind == 'd2s':               # adjoint of the depth-to-space interleave of a restated decoder layer
-                grads[op.src] = ops.space_to_depth2(gD, op.xs[0], c_off=op.out_c_off)
-                written[op.src] = [(0, 4 * op.xs[0])]
-                continue
-            if op.kind == 'conv':
-                lay = op.layer
-                y = tensor(op.dst)
-                acc = id(lay) in touched_layers
-                derived = op.wparam is not None        # the layer runs with phase-summed kernels (plan.phase_params)
-                kern = self.model.train_executor.conv_weights(op)[0]
-                n_out = op.conv_geometry[0]
-                fused_bias = (pooled_grad is None and lay.activation != 'linear' and lay.bias is not None and not acc and
-                              not derived and gD.shape[1] == lay.filters and tuple(y.shape) == tuple(gD.shape))
-                if (pooled_grad is not None and op.src == P.STATE_IN and not acc and pooled_grad.is_contiguous() and
-                        os.environ.get('DLWP_WGRAD_POOLED', '1') != '0' and
-                        ops.conv2d_bwd_weight_pooled_supported(_lib.Shape4(n, op.xs[0], op.xs[1], op.xs[2]), d)):
-                    # the first layer under MaxPooling2D(2): nobody needs its data gradient, so the pooling + activation
-                    # backward is formed inside the weight gradient's loader and the gradient tensor is never stored
-                    gb = self._grad_view(lay, 'bias') if lay.bias is not None else None
-                    on_side(lambda src=src, y=y, pg=pooled_grad, lay=lay, gb=gb, d=d, act=op.act, key=key,
-                            xs=_lib.Shape4(n, op.xs[0], op.xs[1], op.xs[2]):
-                            ops.conv2d_bwd_weight_pooled(src, y, pg, self._grad_view(lay, 'kernel'), gb, d, xs, act,
-                                                         ws_key=key('wgrad')))
-                    touched_layers.add(id(lay))
-                    if isinstance(lay, L._ConvPart):
-                        touched_layers.add(id(lay.parent))
-                    continue
-                if op.dst in preact:           # the reader's data gradient left dz and this layer's bias gradient already
-                    fused_bias = True
-                elif pooled_grad is not None:  # the layer's only reader is MaxPooling2D(2): its backward rides along
-                    fused_bias = lay.bias is not None
-                    gD = ops.pool_act_bwd_bias_grad(y, pooled_grad, op.act,
-                                                    self._grad_view(lay, 'bias') if fused_bias else None, ws_key=key('bias'))
-                elif fused_bias:       # dz in place of dy and the bias gradient from the same pass
-                    ops.act_bwd_bias_grad(y, gD, op.act, self._grad_view(lay, 'bias'), lay.filters, out=gD,
-                                          ws_key=key('bias'))
-                elif lay.activation != 'linear':
-                    ops.act_bwd(y, gD, op.act, out=gD)          # dz in place of dy
-                dz = gD
-                xs = _lib.Shape4(n, op.xs[0], op.xs[1], op.xs[2])
-                if op.src != P.STATE_IN:
-                    pair_begin()           # (closed behind the data gradient's convolution, below)
-                if derived:                # gradients of the derived kernels, folded back onto the layer's own
-                    pp = plan.phase_params[op.wparam]
-                    dw2 = torch.empty(tuple(kern.shape), dtype=torch.float32, device=self.device)
-                    have_db = k in phase_db
-                    db2 = phase_db[k] if have_db else (
-                        torch.empty(n_out, dtype=torch.float32, device=self.device) if lay.bias is not None else None)
-
-                    def derived_grads(src=src, dz=dz, dw2=dw2, db2=db2, d=d, xs=xs, n_out=n_out, key=key, have_db=have_db):
-                        ops.conv2d_bwd_weight(src, dz, dw2, d, xs, ws_key=key('wgrad'))
-                        if db2 is not None and not have_db:
-                            ops.bias_grad(dz, db2, n_out, ws_key=key('bias'))
-                    on_side(derived_grads)
-
-                    def fold_back(dw2=dw2, db2=db2, lay=lay, pp=pp, acc=acc):
-                        ops.phase_weights_bwd(dw2, db2, self._grad_view(lay, 'kernel'),
-                                              self._grad_view(lay, 'bias') if lay.bias is not None else None,
-                                              pp['pad_top'], pp['pad_left'], accumulate=acc)
-                    if prep is not None:
-                        post.append(fold_back)          # dw2 / db2 are final only behind the deferred sums
-                    else:
-                        fold_back()
-                else:
-                    on_side(lambda src=src, dz=dz, lay=lay, d=d, xs=xs, acc=acc, key=key: ops.conv2d_bwd_weight(
-                        src, dz, self._grad_view(lay, 'kernel'), d, xs, accumulate=acc, ws_key=key('wgrad')))
-                if lay.bias is not None and not fused_bias and not derived:
-                    gb = self._grad_view(lay, 'bias')
-                    if acc:
-                        tmp = torch.empty_like(gb)
-                        ops.bias_grad(dz, tmp, lay.filters)
-                        ops.axpby(tmp, gb, 1.0, 1.0)
-                    else:
-                        on_side(lambda dz=dz, gb=gb, lay=lay, key=key: ops.bias_grad(dz, gb, lay.filters, ws_key=key('bias')))
-                touched_layers.add(id(lay))
-                if isinstance(lay, L._ConvPart):
-                    touched_layers.add(id(lay.parent))
-                if op.src == P.STATE_IN:
-                    continue                  # no gradient w.r.t. the model input is needed
-                cin = op.xs[0]
-                c_total = src.shape[1]
-                pb = prep['bwd'].get(k) if prep is not None else None     # (prepared operand, for the stored tensor?)
-                if op.src_mode == P.SRC_DIRECT:
-                    g = grad_of(op.src)
-                    if not overlaps(op.src, op.in_c_off, cin):
-                        # writes its channel window in place -- where this layer is the only reader of another Conv2D's
-                        # activation output, already times act'(that output), with that layer's bias gradient from the same pass
-                        done = False
-                        kp = self._dgrad_act_ops().get(k)
-                        if kp is not None:
-                            pop = plan.ops[kp]
-                            done = ops.conv2d_bwd_data_act(dz, kern, d, xs, g, src, pop.act, self._grad_view(pop.layer, 'bias'),
-                                                           prepared=pb[0] if pb else None, ws_key=key('dact'))
-                            if done:
-                                preact.add(op.src)
-                        if not done:
-                            ops.conv2d_bwd_data(dz, kern, d, xs, g, prepared=pb[0] if pb else None)
-                        pair_end()
-                        written.setdefault(op.src, []).append((op.in_c_off, cin))
-                    else:
-                        dd = ops.make_conv(d.cout, d.kh, d.kw, (d.dil_h, d.dil_w), d.halo, d.act, 0, 0, d.out_c_off,
-                                           d.out_c_total, d.src_mode)
-                        tmp = torch.empty((n, cin) + tuple(src.shape[2:]), dtype=torch.float32, device=self.device)
-                        ops.conv2d_bwd_data(dz, kern, dd, xs, tmp)
-                        pair_end()
-                        deposit(op.src, op.in_c_off, cin, tmp)
-                else:
-                    hin = 2 * op.xs[1] if op.src_mode == P.SRC_UPSAMPLE2 else op.xs[1] // 2
-                    win = 2 * op.xs[2] if op.src_mode == P.SRC_UPSAMPLE2 else op.xs[2] // 2
-                    if op.src_mode == P.SRC_UPSAMPLE2:    # 2x2 sum fused into the data-gradient kernel where it can be
-                        dense = torch.empty((n, cin, op.xs[1], op.xs[2]), dtype=torch.float32, device=self.device)
-                        if pb is not None and pb[1]:
-                            ops.conv2d_bwd_data(dz, kern, d, xs, dense, prepared=pb[0], stored=True)
-                            pair_end()
-                        elif pb is not None or not ops.conv2d_bwd_data_stored(dz, kern, d, xs, dense):
-                            tmp = torch.empty((n, cin, hin, win), dtype=torch.float32, device=self.device)
-                            ops.conv2d_bwd_data(dz, kern, d, xs, tmp, prepared=pb[0] if pb else None)
-                            pair_end()
-                            dense = ops.upsample2_bwd(tmp)
-                        pair_end()
-                    else:
-                        tmp = torch.empty((n, cin, hin, win), dtype=torch.float32, device=self.device)
-                        ops.conv2d_bwd_data(dz, kern, d, xs, tmp, prepared=pb[0] if pb else None)
-                        pair_end()
-                        if op.in_c_off == 0 and cin == c_total:
-                            xw = src
-                        else:
-                            xw = torch.empty((n, cin) + tuple(src.shape[2:]), dtype=torch.float32, device=self.device)
-                            ops.copy_channels(src, xw, cin, op.in_c_off, 0)
-                        dense = ops.maxpool2_bwd(xw, tmp)
-                    deposit(op.src, op.in_c_off, cin, dense)
-            elif op.kind == 'rowconv':         # RowConnected2D (reference custom.py:695-837): per-row filters
-                lay = op.layer
-                y = tensor(op.dst)
-                acc = id(lay) in touched_layers
-                if lay.activation != 'linear':
-                    ops.act_bwd(y, gD, op.act, out=gD)          # dz in place of dy
-                dz = gD
-                xs = _lib.Shape4(n, op.xs[0], op.xs[1], op.xs[2])
-                ops.rowconv2d_bwd_weight(src, dz, self._grad_view(lay, 'kernel'),
-                                         self._grad_view(lay, 'bias') if lay.bias is not None else None, d, xs,
-                                         accumulate=acc)
-                touched_layers.add(id(lay))
-                if op.src == P.STATE_IN:
-                    continue
-                cin = op.xs[0]
-                if op.src_mode == P.SRC_UPSAMPLE2:     # gradient of the up-sampled tensor, then the 2x2 sums of its adjoint
-                    dd = ops.make_conv(d.cout, d.kh, d.kw, 1, d.halo, d.act, 0, 0, d.out_c_off, d.out_c_total)
-                    up = torch.empty((n, cin, 2 * op.xs[1], 2 * op.xs[2]), dtype=torch.float32, device=self.device)
-                    ops.rowconv2d_bwd_data(dz, lay.kernel, dd, _lib.Shape4(n, cin, 2 * op.xs[1], 2 * op.xs[2]), up)
-                    dense = ops.upsample2_bwd(up)
-                else:
-                    dd = ops.make_conv(d.cout, d.kh, d.kw, 1, d.halo, d.act, 0, 0, d.out_c_off, d.out_c_total)
-                    dense = torch.empty((n, cin) + tuple(src.shape[2:]), dtype=torch.float32, device=self.device)
-                    ops.rowconv2d_bwd_data(dz, lay.kernel, dd, xs, dense)
-                deposit(op.src, op.in_c_off, cin, dense)
-            elif op.kind == 'dense':           # keras Dense: weight and bias gradient, then (not for the model input) dx
-                lay = op.layer
-                y = tensor(op.dst)
-                ops.dense_bwd_weight(src, gD, y, self._grad_view(lay, 'kernel'),
-                                     self._grad_view(lay, 'bias') if lay.bias is not None else None, op.act)
-                touched_layers.add(id(lay))
-                if op.src == P.STATE_IN:
-                    continue
-                dx = torch.empty_like(src)
-                ops.dense_bwd_data(gD, y, lay.kernel, op.act, out=dx)
-                deposit(op.src, 0, src.shape[1], dx)
-            elif op.kind == 'dropout':         # the mask of the forward: same (seed, layer, step)
-                if op.src == P.STATE_IN:
-                    continue
-                lay = op.layer
-                dx = ops.dropout_bwd(gD, lay.rate, lay.mask_seed, plan.dropout_layers.index(lay),
-                                     self.model.train_executor.dropout_step)
-                deposit(op.src, 0, src.shape[1], dx.view(src.shape))
-            elif op.kind == 'bn':              # BatchNormalization: dgamma, dbeta and dx from the batch statistics of the forward
-                lay = op.layer
-                st = self.model.train_executor.bn_state(k, int(n))
-                dx = ops.batchnorm_bwd(src, gD, lay.gamma, st['mean'], st['invstd'], st['ws'],
-                                       dgamma=self._grad_view(lay, 'gamma') if lay.gamma is not None else None,
-                                       dbeta=self._grad_view(lay, 'beta') if lay.beta is not None else None,
-                                       want_dx=op.src != P.STATE_IN)
-                touched_layers.add(id(lay))
-                if dx is not None:
-                    deposit(op.src, 0, src.shape[1], dx)
-            elif op.kind == 'lstm':
-                zh_i, cp_i, co_i = op.aux
-                f = op.xs[0]
-                win = (op.out_c_off, f)
-                if not all(any(o <= ch < o + k for o, k in written.get(op.dst, [])) for ch in range(win[0], win[0] + f)):
-                    if overlaps(op.dst, *win):
-                        raise NotImplementedError('ConvLSTM2D output used through partially overlapping channel windows')
-                    deposit(op.dst, win[0], f, torch.zeros((n, f) + tuple(gD.shape[2:]), dtype=torch.float32,
-                                                           device=self.device))   # this h_t feeds nothing downstream
-                dz, dcp = ops.convlstm_gates_bwd(src, tensor(zh_i) if zh_i is not None else None,
-                                                 tensor(cp_i) if cp_i is not None else None, tensor(co_i), gD,
-                                                 grads.get(co_i), f, h_c_off=op.out_c_off, act=op.act, rec_act=op.rec_act)
-                grads[op.src] = dz
-                written[op.src] = [(0, 4 * f)]
-                if zh_i is not None:
-                    grads[zh_i] = dz                 # z = zx + zh: the same gradient flows into both convolutions
-                    written[zh_i] = [(0, 4 * f)]
-                if cp_i is not None:
-                    grads[cp_i] = dcp
-                    written[cp_i] = [(0, f)]
-            elif op.kind == 'copy':
-                if op.src == P.STATE_IN:
-                    continue
-                c = op.xs[0]
-                gw = torch.empty((n, c) + tuple(gD.shape[2:]), dtype=torch.float32, device=self.device)
-                ops.copy_channels(gD, gw, c, op.out_c_off, 0)
-                deposit(op.src, op.in_c_off, c, gw)
-            elif op.kind == 'pad':
-                if op.src == P.STATE_IN:
-                    continue
-                if op.inner > 1:
-                    dense = ops.pad2d_bwd(gD.reshape((n, gD.shape[1], gD.shape[2], -1)) if gD.dim() == 4 else gD,
-                                          (n, op.xs[1], op.xs[2], op.inner), d, channels_last=True)
-                else:
-                    dense = ops.pad2d_bwd(gD, (n,) + tuple(op.xs), d)
-                deposit(op.src, 0, src.shape[1], dense)
-            elif op.kind == 'maxpool':
-                if op.src == P.STATE_IN:
-                    continue
-                if op.src >= 0 and op.src not in grads and op.src not in pending_pool:
-                    pending_pool[op.src] = gD
-                else:
-                    deposit(op.src, 0, src.shape[1], ops.maxpool2_bwd(src, gD))
-            elif op.kind == 'upsample':
-                if op.src == P.STATE_IN:
-                    continue
-                deposit(op.src, 0, src.shape[1], ops.upsample2_bwd(gD))
-            else:
-                raise RuntimeError(op.kind)
-        pair_end()          # (a layer whose data gradient took no convolution)
-        # layers that received no gradient this step (unused by any output) must not keep a stale one
-        for lay, nm, off, numel, shape in self.entries:
-            if id(lay) not in touched_layers:
-                self._foreign = True          # (torch's own launch: a recorded step would miss it)
-                self.flat_grads[off:off + numel].zero_()
-        if sides is not None:
-            launch_queued(True)
-            for st in used:
-                ops.stream_wait(main, st)     # the weight gradients join before anything reads them
-        return post
+        """The plan's ops in reverse (backward.py); gradients in flat_grads.  prep (the folded step, _fold_ok): prepared
+        data-gradient operands, a workspace per deferred final sum, the weight gradients on the side streams; the caller brackets
+        forward + backward with ops.reductions_begin / _flush and runs the returned callables (work that needs the final sums)
+        after the flush."""
+        from .backward import BackwardPass
+        return BackwardPass(self, x, outs, dys, prep).run()
 
     def _forward_backward(self, x, ys, scale):
         """Forward + loss + backward of one step; gradients in flat_grads.  Returns (outs, loss table, dys)."""
@@ -1152,6 +769,21 @@ class Trainer(object):
         store = self.plan._in_store
         return 'graph' if (mode == '1' or n_local * int(store[-1]) * int(store[-2]) <= self.graph_below) else 'lanes'
 
+    def _step_tail(self, loss_vals, scale, dp):
+        """What follows forward + backward inside a recorded or captured step: the update with the step number on the device --
+        or, data parallel, the loss table moved behind the gradients (the exchange and the update stay outside: a collective in
+        between)."""
+        from . import ops
+        opt = self.model.optimizer
+        if dp is not None:
+            ops.axpby(loss_vals.view(-1), self._loss_tail.view(-1), scale, 0.0)
+        elif isinstance(opt, Adam):
+            m, v = self.opt_state
+            ops.adam_keras_dev(self.flat_params, m, v, self.flat_grads, self._iter_dev, self._lr_t, opt.lr, opt.beta_1,
+                               opt.beta_2, opt.epsilon, opt.decay, 1.0)
+        else:
+            ops.sgd_keras(self.flat_params, self.opt_state[0], self.flat_grads, 0, opt.lr, opt.momentum, 0.0, 1.0)
+
     # -- the step as a library object (dlwp_train_step_*) ------------------------------------------------------------------ #
     def _record_step(self, x, ys, n_global, scale, dp, form='graph'):
         """Runs ONE real step on (x, ys) while the library records its launches; returns the step entry, or {'refused': True} when
@@ -1184,25 +816,12 @@ class Trainer(object):
         validate = os.environ.get('DLWP_TAPE_VALIDATE', '1') != '0'
         state0 = [t.clone() for t in [self.flat_params] + list(self.opt_state) + [self._iter_dev] + self._bn_stats] \
             if validate else None
+
         def body(bx, bys):
             outs_, loss_, dys_ = self._forward_backward(bx, bys, scale)
-            if dp is not None:       # the exchange and the update stay outside: a collective in between
-                ops.axpby(loss_.view(-1), self._loss_tail.view(-1), scale, 0.0)
-            elif isinstance(opt, Adam):
-                m, v = self.opt_state
-                ops.adam_keras_dev(self.flat_params, m, v, self.flat_grads, self._iter_dev, self._lr_t, opt.lr, opt.beta_1,
-                                   opt.beta_2, opt.epsilon, opt.decay, 1.0)
-            else:
-                ops.sgd_keras(self.flat_params, self.opt_state[0], self.flat_grads, 0, opt.lr, opt.momentum, 0.0, 1.0)
+            self._step_tail(loss_, scale, dp)
             return outs_, loss_, dys_
-        # No garbage collection while recording (as in _capture_step): a cycle that finalises an OLD model's memory pool, graphs or
-        # streams inside this pool's use_mem_pool block aborts the process ('Fatal Python error: Aborted ... Garbage-collecting'
-        # under dlwp_stream_wait).
-        import gc
-        gc.collect()
-        gc_was_on = gc.isenabled()
-        gc.disable()
-        try:
+        with _no_gc():
             with torch.cuda.use_mem_pool(pool, device=self.device):
                 _lib.check(_lib.lib.dlwp_train_step_record_begin(h, ctypes.c_void_p(main.cuda_stream)))
                 try:
@@ -1221,9 +840,6 @@ class Trainer(object):
                 if rc == _lib.EUNSUPPORTED:          # an entry point without a tape record ran inside the step: the shape stays eager
                     return {'refused': True, 'loss': loss_vals, 'why': _lib.lib.dlwp_last_error().decode('utf-8', 'replace')}
                 _lib.check(rc)
-        finally:
-            if gc_was_on:
-                gc.enable()
         keep = (outs, loss_vals, dys, dict(ops._workspaces), dict(ops._workspaces2),
                 self.model.train_executor.scratch(int(x.shape[0])), self.model.train_executor.phase_buffers(),
                 self._prep_cache.get(int(x.shape[0])), self._side, pool)
@@ -1289,8 +905,6 @@ class Trainer(object):
         return why
 
     def _capture_step(self, x, ys, n_global, scale, dp):
-        from . import ops
-        opt = self.model.optimizer
         gx = x.clone()
         gys = [t.clone() for t in ys]
         if self._iter_dev is None:
@@ -1298,36 +912,18 @@ class Trainer(object):
             self._lr_t = torch.zeros(1, dtype=torch.float32, device=self.device)
         if self.opt_state is None:
             raise RuntimeError('the optimizer slots must exist before the step is captured')
-        import gc
         from ._lib import capture_lock
         torch.cuda.synchronize(self.device)
         g = torch.cuda.CUDAGraph()
-        # No garbage collection while the stream is capturing: a collection cycle that finalises an old model's graphs, streams,
-        # events or device memory (hipGraphExecDestroy, hipStreamDestroy, hipFree ...) in the middle of a capture aborts the
-        # process or leaves a graph that crashes at launch (r3: seen as 'Fatal Python error: Aborted ... Garbage-collecting' inside
-        # _capture_step and as segmentation faults in replay, 3 of 7 full test runs, once small steps were captured by default).
-        gc.collect()
-        gc_was_on = gc.isenabled()
-        gc.disable()
-        try:
-            return self._capture_locked(g, gx, gys, n_global, scale, dp, opt, capture_lock)
-        finally:
-            if gc_was_on:
-                gc.enable()
+        with _no_gc():
+            return self._capture_locked(g, gx, gys, n_global, scale, dp, capture_lock)
 
-    def _capture_locked(self, g, gx, gys, n_global, scale, dp, opt, capture_lock):
+    def _capture_locked(self, g, gx, gys, n_global, scale, dp, capture_lock):
         from . import ops
         x = gx
         with capture_lock, torch.cuda.graph(g, capture_error_mode='thread_local'):
             outs, loss_vals, dys = self._forward_backward(gx, gys, scale)
-            if dp is not None:       # the exchange and the update stay outside: a collective in between
-                ops.axpby(loss_vals.view(-1), self._loss_tail.view(-1), scale, 0.0)
-            elif isinstance(opt, Adam):
-                m, v = self.opt_state
-                ops.adam_keras_dev(self.flat_params, m, v, self.flat_grads, self._iter_dev, self._lr_t, opt.lr, opt.beta_1,
-                                   opt.beta_2, opt.epsilon, opt.decay, 1.0)
-            else:
-                ops.sgd_keras(self.flat_params, self.opt_state[0], self.flat_grads, 0, opt.lr, opt.momentum, 0.0, 1.0)
+            self._step_tail(loss_vals, scale, dp)
         # everything the captured launches point into must outlive the graph, whatever the caches do later
         keep = (outs, loss_vals, dys, dict(ops._workspaces), dict(ops._workspaces2),
                 self.model.train_executor.scratch(int(x.shape[0])), self.model.train_executor.phase_buffers(),

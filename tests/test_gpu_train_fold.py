@@ -490,3 +490,182 @@ def test_step_with_the_activation_backward_in_the_data_gradients_equals_the_step
         assert np.abs(a[1] - b[1]).max() <= 5e-6 * np.abs(b[1]).max()
         for wa, wb in zip(a[2], b[2]):
             assert np.abs(wa - wb).max() <= 5e-6
+
+
+def _functional_step_against_autograd(m, weighted, x, y, forward):
+    """One train_on_batch of the compiled functional model `m` against float64 autograd, at the tolerances of
+    test_train_step_gradients_loss_and_adam_match_autograd_oracle.  `weighted`: the layers whose weights `forward(x, tw)` -- the
+    model restated on torch -- takes, in its order; biases are randomised first.  Returns the trainer."""
+    from oracle import torch_ref
+    rng = np.random.default_rng(3)
+    m.set_weights([(0.1 * rng.standard_normal(a.shape)).astype(np.float32) if a.ndim == 1 else a for a in m.get_weights()])
+    tw = torch_ref.to_torch_weights([tuple(lay.get_weights()) for lay in weighted], dtype=torch.float64, requires_grad=True)
+    out = forward(torch.tensor(x, dtype=torch.float64), tw)
+    yt = torch.tensor(y, dtype=torch.float64)
+    loss = ((out - yt) ** 2).mean()
+    loss.backward()
+    vals = m.train_on_batch(x, y)
+    torch.cuda.synchronize()
+    print('loss', vals[0], float(loss), 'mae', vals[1], float((out - yt).abs().mean()))
+    assert vals[0] == pytest.approx(float(loss), rel=2e-5)
+    assert vals[1] == pytest.approx(float((out - yt).abs().mean()), rel=2e-5)
+    tr = m._trainer
+    for lay, item in zip(weighted, tw):
+        for (name, _), a in zip(lay._weights, item):
+            g_ref = a.grad.numpy()
+            g_ref = g_ref.transpose(2, 3, 1, 0) if g_ref.ndim == 4 else g_ref
+            g = tr._grad_view(lay, name).cpu().numpy()
+            print(lay.name, name, np.abs(g - g_ref).max(), np.abs(g_ref).max())
+            assert np.abs(g - g_ref).max() <= 2e-4 * max(np.abs(g_ref).max(), 1e-6), (lay.name, name)
+    return tr
+
+
+def _conv(tw, t, act, pad=1):
+    import torch.nn.functional as F
+    t = F.conv2d(F.pad(t, (pad,) * 4), tw[0], tw[1])
+    return torch.tanh(t) if act == 'tanh' else t
+
+
+def test_pooled_sources_read_through_channel_windows_match_the_autograd_oracle():
+    """Two convolutions read MaxPooling2D(2) of the channel windows [4, 12) and [0, 4) of one tensor, with kernels the library
+    keeps on the fused pooling loader: each data gradient is un-pooled against a copy of its own window of the source
+    (copy_channels in front of maxpool2_bwd) and lands in that window of the source's gradient."""
+    import torch.nn.functional as F
+    from dlwp_amd import custom, layers as L, plan as P
+    from dlwp_amd.engine import Model
+    from tests.nets import CF
+    cs = (2, 8, 12)
+    x0 = L.Input(shape=cs)
+    pool = L.MaxPooling2D(2, **CF)
+    c0 = L.Conv2D(12, 3, padding='same', activation='tanh', **CF)
+    ca = L.Conv2D(8, 3, padding='same', activation='tanh', **CF)
+    cb = L.Conv2D(4, 3, padding='same', activation='tanh', **CF)
+    c1 = L.Conv2D(2, 3, padding='same', activation='linear', **CF)
+    t = c0(x0)
+    out = c1(L.concatenate([ca(pool(custom.slice_layer(4, 12, axis=1)(t))), cb(pool(custom.slice_layer(0, 4, axis=1)(t)))], axis=1))
+    np.random.seed(2)
+    m = Model(inputs=x0, outputs=out)
+    m.compile(optimizer='adam', loss='mse', metrics=['mae'])
+    reads = sorted((op.in_c_off, op.xs[0]) for op in m.plan.ops if op.kind == 'conv' and op.src_mode == P.SRC_MAXPOOL2)
+    assert reads == [(0, 4), (4, 8)]
+
+    def forward(xt, tw):
+        t = _conv(tw[0], xt, 'tanh')
+        a = _conv(tw[1], F.max_pool2d(t[:, 4:], 2), 'tanh')
+        b = _conv(tw[2], F.max_pool2d(t[:, :4], 2), 'tanh')
+        return _conv(tw[3], torch.cat([a, b], dim=1), 'linear')
+    rng = np.random.default_rng(4)
+    x = rng.standard_normal((5,) + cs).astype(np.float32)
+    y = rng.standard_normal((5, 2, 4, 6)).astype(np.float32)
+    _functional_step_against_autograd(m, [c0, ca, cb, c1], x, y, forward)
+
+
+def test_padding_layer_inside_the_net_matches_the_autograd_oracle():
+    """TFPadding2D('REFLECT') between a convolution and a MaxPooling2D(2): the padding cannot ride in a loader (the pooling reads
+    the padded tensor), so it is an op of its own and the backward pass runs its adjoint (pad2d_bwd: the mirrored border
+    folds back onto the interior); the convolution behind it reads the pooled, padded tensor whole (odd pooled size 5 x 8)."""
+    import torch.nn.functional as F
+    from dlwp_amd import custom, layers as L, plan as P
+    from dlwp_amd.engine import Model
+    from tests.nets import CF
+    cs = (2, 8, 12)
+    x0 = L.Input(shape=cs)
+    c0 = L.Conv2D(6, 3, padding='same', activation='tanh', **CF)
+    c1 = L.Conv2D(2, 3, padding='same', activation='linear', **CF)
+    out = c1(L.MaxPooling2D(2, **CF)(custom.TFPadding2D((1, 2), mode='REFLECT', **CF)(c0(x0))))
+    np.random.seed(3)
+    m = Model(inputs=x0, outputs=out)
+    m.compile(optimizer='adam', loss='mse', metrics=['mae'])
+    assert [(op.kind, op.src_mode) for op in m.plan.ops] == [('conv', P.SRC_DIRECT), ('pad', P.SRC_DIRECT), ('conv', P.SRC_MAXPOOL2)]
+
+    def forward(xt, tw):
+        t = F.pad(_conv(tw[0], xt, 'tanh'), (2, 2, 1, 1), mode='reflect')
+        return _conv(tw[1], F.max_pool2d(t, 2), 'linear')
+    rng = np.random.default_rng(5)
+    x = rng.standard_normal((4,) + cs).astype(np.float32)
+    y = rng.standard_normal((4, 2, 5, 8)).astype(np.float32)
+    _functional_step_against_autograd(m, [c0, c1], x, y, forward)
+
+
+def test_layer_no_output_depends_on_gets_a_zero_gradient():
+    """A layer of the model that no output depends on (the functional constructor collects only layers that reach an output, so
+    it is added to model.layers by hand before compile): its slice of the flat gradient buffer, stale from whatever stood
+    there, is zeroed by the step; every other gradient matches the oracle."""
+    from dlwp_amd import layers as L
+    from dlwp_amd.engine import Model
+    from tests.nets import CF
+    cs = (2, 8, 12)
+    x0 = L.Input(shape=cs)
+    c0 = L.Conv2D(6, 3, padding='same', activation='tanh', **CF)
+    c1 = L.Conv2D(2, 3, padding='same', activation='linear', **CF)
+    spare = L.Conv2D(3, 3, padding='same', activation='tanh', **CF)
+    t = c0(x0)
+    np.random.seed(4)
+    m = Model(inputs=x0, outputs=c1(t))
+    spare.build(t.shape, m.device, np.random.RandomState(5))
+    m.layers.append(spare)
+    m.compile(optimizer='adam', loss='mse', metrics=['mae'])
+    tr = m._trainer
+    assert any(lay is spare for lay, _, _, _, _ in tr.entries)
+    tr.flat_grads.fill_(7.0)
+    rng = np.random.default_rng(6)
+    x = rng.standard_normal((3,) + cs).astype(np.float32)
+    y = rng.standard_normal((3,) + cs).astype(np.float32)
+    _functional_step_against_autograd(m, [c0, c1], x, y, lambda xt, tw: _conv(tw[1], _conv(tw[0], xt, 'tanh'), 'linear'))
+    assert float(tr._grad_view(spare, 'kernel').abs().max()) == 0.0 and float(tr._grad_view(spare, 'bias').abs().max()) == 0.0
+    assert not bool((tr.flat_grads == 7.0).any())
+
+
+def test_convlstm_step_whose_output_feeds_nothing_matches_the_autograd_oracle():
+    """ConvLSTM2D over three time steps, return_sequences, of which the next layer reads h_0 and h_1 only: the last step's
+    output feeds nothing (the backward pass deposits zeros as its gradient before the gate backward runs), so the gradients of
+    the three weights are those of back-propagation through the first two steps alone."""
+    import torch.nn.functional as F
+    from dlwp_amd import custom, layers as L
+    from dlwp_amd.engine import Model
+    from oracle import torch_ref
+    from tests.nets import CF
+    T, C, H, W, f = 3, 2, 8, 12, 4
+    x0 = L.Input(shape=(T, C, H, W))
+    lstm = L.ConvLSTM2D(f, 3, padding='same', activation='tanh', return_sequences=True, **CF)
+    c1 = L.Conv2D(2, 3, padding='same', activation='linear', **CF)
+    out = c1(custom.slice_layer(0, (T - 1) * f, axis=1)(L.Reshape((T * f, H, W))(lstm(x0))))
+    np.random.seed(5)
+    m = Model(inputs=x0, outputs=out)
+    m.compile(optimizer='adam', loss='mse', metrics=['mae'])
+    last = [op for op in m.plan.ops if op.kind == 'lstm'][-1]
+    reader = m.plan.ops[-1]
+    assert last.out_c_off == (T - 1) * f and (reader.src, reader.in_c_off, reader.xs[0]) == (last.dst, 0, (T - 1) * f)
+
+    def forward(xt, tw):
+        h = torch_ref.conv_lstm2d(F.pad(xt, (1, 1, 1, 1)), *tw[0], dilation=1, activation='tanh', return_sequences=True)
+        return _conv(tw[1], h.reshape(h.shape[0], T * f, H, W)[:, :(T - 1) * f], 'linear')
+    rng = np.random.default_rng(7)
+    x = rng.standard_normal((4, T, C, H, W)).astype(np.float32)
+    y = rng.standard_normal((4, 2, H, W)).astype(np.float32)
+    _functional_step_against_autograd(m, [lstm, c1], x, y, forward)
+
+
+def test_partially_overlapping_channel_windows_are_refused_in_the_backward_pass(monkeypatch):
+    """Two convolutions read the windows [0, 8) and [4, 12) of one 12-channel tensor: the second data gradient to arrive meets
+    a window that holds a gradient in part.  The backward pass has no route for that and says so (it does not add into, or
+    overwrite, half a window)."""
+    from dlwp_amd import custom, layers as L
+    from dlwp_amd.engine import Model
+    from tests.nets import CF
+    monkeypatch.setenv('DLWP_TRAIN_GRAPH', '0')
+    cs = (2, 8, 12)
+    x0 = L.Input(shape=cs)
+    t = L.Conv2D(12, 3, padding='same', activation='tanh', **CF)(x0)
+    a = L.Conv2D(4, 3, padding='same', activation='tanh', **CF)(custom.slice_layer(0, 8, axis=1)(t))
+    b = L.Conv2D(4, 3, padding='same', activation='tanh', **CF)(custom.slice_layer(4, 12, axis=1)(t))
+    out = L.Conv2D(2, 3, padding='same', activation='linear', **CF)(L.concatenate([a, b], axis=1))
+    np.random.seed(1)
+    m = Model(inputs=x0, outputs=out)
+    m.compile(optimizer='adam', loss='mse')
+    reads = sorted((op.in_c_off, op.xs[0]) for op in m.plan.ops if op.kind == 'conv' and op.src == 0)
+    assert reads == [(0, 8), (4, 8)]
+    x = np.random.default_rng(2).standard_normal((3,) + cs).astype(np.float32)
+    with pytest.raises(NotImplementedError, match='partially overlapping channel windows'):
+        m.train_on_batch(x, x)
+    torch.cuda.synchronize()
