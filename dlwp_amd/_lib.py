@@ -33,6 +33,8 @@ OP_CONV2D, OP_PAD2D, OP_MAXPOOL2, OP_UPSAMPLE2, OP_COPYCH, OP_LSTM_GATES, OP_PHA
 OP_ROWCONV2D = 8
 OP_BATCHNORM = 9
 OP_DENSE = 10
+OP_SCALE = 11
+SCALE_STANDARD, SCALE_MINMAX = 0, 1                 # dlwp_scale kinds
 BUF_NONE = -1000
 STEP_LANES, STEP_GRAPH, STEP_GRAPH_BRANCHES, STEP_LANES_RECORDED = 0, 1, 2, 3
 
@@ -99,6 +101,11 @@ class Dropout(ctypes.Structure):
     """dlwp_dropout (include/dlwp_hip.h): what names one mask -- seed, layer, step -- and how it is applied"""
     _fields_ = [('seed', ctypes.c_ulonglong), ('layer', ctypes.c_uint), ('step', ctypes.c_uint), ('threshold', ctypes.c_uint),
                 ('scale', ctypes.c_float)]
+
+
+class Scale(ctypes.Structure):
+    """dlwp_scale (include/dlwp_hip.h): samples, features per sample and the scaler kind of one scaler / imputer launch"""
+    _fields_ = [('n', ctypes.c_int), ('f', ctypes.c_int), ('kind', ctypes.c_int)]
 
 
 class LaunchInfo(ctypes.Structure):
@@ -249,6 +256,8 @@ _sig('dlwp_dense_bwd_data', [_vp] * 5 + [Dense, _vp])
 _sig('dlwp_dense_bwd_weight', [_vp] * 6 + [Dense, _vp])
 _sig('dlwp_dropout_fwd', [_vp, _vp, _vp, ctypes.c_longlong, Dropout, _vp])
 _sig('dlwp_dropout_bwd', [_vp, _vp, _vp, ctypes.c_longlong, Dropout, _vp])
+_sig('dlwp_scale_fwd', [_vp] * 6 + [Scale, _vp])
+_sig('dlwp_scale_inv', [_vp] * 5 + [Scale, _vp])
 _sig('dlwp_copy_channels', [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp])
 _sig('dlwp_series_merge_time', [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp])
 _sig('dlwp_rollout_workspace_bytes', [_vp, _P(Op), _i, _i], _sz)

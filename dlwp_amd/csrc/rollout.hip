@@ -70,6 +70,11 @@ int enqueue_op(dlwp_handle_t h, const dlwp_op& op, const void* src, void* dst, c
       const dlwp_dense d{op.xs.n, op.xs.c * op.xs.h * op.xs.w, op.conv.cout, op.conv.act};
       return dlwp_dense_fwd(h, src, w, b, dst, d, (void*)s);
     }
+    case DLWP_OP_SCALE: {       // w / b = shift / scale (nullable), aux[0] = fill (forward only); op.aux[1] = kind, op.aux[2] = direction
+      const dlwp_scale d{op.xs.n, op.xs.c * op.xs.h * op.xs.w, op.aux[1]};
+      if (op.aux[2]) return dlwp_scale_inv(h, src, dst, w, b, d, (void*)s);
+      return dlwp_scale_fwd(h, src, dst, aux[0], w, b, d, (void*)s);
+    }
     case DLWP_OP_COPYCH:
       return dlwp_copy_channels(h, src, dst, op.xs.n, op.xs.c, op.xs.h * op.xs.w, op.conv.in_c_off,
                                 op.conv.in_c_total, op.conv.out_c_off, op.conv.out_c_total, dtype, (void*)s);
@@ -198,6 +203,11 @@ static int create_impl(dlwp_handle_t h, const dlwp_op* plan_in, int n_ops, void*
       DLWP_CHECK_ARG(op.w >= -1 && op.w < n_buffers && op.b >= -1 && op.b < n_buffers && op.aux[0] >= 0 && op.aux[0] < n_buffers &&
                          op.aux[1] >= 0 && op.aux[1] < n_buffers,
                      "rollout op %d: batch-normalisation buffers out of range", i);
+    if (op.kind == DLWP_OP_SCALE)
+      DLWP_CHECK_ARG(op.w >= -1 && op.w < n_buffers && op.b >= -1 && op.b < n_buffers &&
+                         (op.aux[0] == DLWP_BUF_NONE || (op.aux[0] >= 0 && op.aux[0] < n_buffers && op.aux[2] == 0)) &&
+                         (op.aux[1] == DLWP_SCALE_STANDARD || op.aux[1] == DLWP_SCALE_MINMAX) && (op.aux[2] == 0 || op.aux[2] == 1),
+                     "rollout op %d: scaler buffers, kind or direction out of range", i);
     if (op.kind == DLWP_OP_LSTM_GATES)
       for (int k = 0; k < 3; ++k)
         DLWP_CHECK_ARG((k < 2 && op.aux[k] == DLWP_BUF_NONE) || (op.aux[k] >= 0 && op.aux[k] < n_buffers),
@@ -278,14 +288,16 @@ static int create_impl(dlwp_handle_t h, const dlwp_op* plan_in, int n_ops, void*
         const dlwp_op& op = plan[i];
         if (op.kind == DLWP_OP_PHASE_WEIGHTS) continue;   // done once, at the head of the graph
         const bool weighted = op.kind == DLWP_OP_CONV2D || op.kind == DLWP_OP_ROWCONV2D || op.kind == DLWP_OP_DENSE;
+        const bool scale = op.kind == DLWP_OP_SCALE;
         const bool bn = op.kind == DLWP_OP_BATCHNORM;
-        const void* w = (weighted || (bn && op.w >= 0)) ? buffers[op.w] : nullptr;
-        const void* b = ((weighted || bn) && op.b >= 0) ? buffers[op.b] : nullptr;
+        const void* w = (weighted || ((bn || scale) && op.w >= 0)) ? buffers[op.w] : nullptr;
+        const void* b = ((weighted || bn || scale) && op.b >= 0) ? buffers[op.b] : nullptr;
         void* aux[3] = {nullptr, nullptr, nullptr};
         if (bn) {                                          // (parameter buffers: the same for every member group)
           aux[0] = buffers[op.aux[0]];
           aux[1] = buffers[op.aux[1]];
         }
+        if (scale && op.aux[0] != DLWP_BUF_NONE) aux[0] = buffers[op.aux[0]];   // (float64 parameters: the same for every member group)
         if (op.kind == DLWP_OP_LSTM_GATES)
           for (int k = 0; k < 3; ++k) aux[k] = op.aux[k] == DLWP_BUF_NONE ? nullptr : resolve(op.aux[k], t, g);
         if (op.kind == DLWP_OP_CONV2D && op.conv.lstm_f > 0)

@@ -27,11 +27,35 @@ def default_device():
     return torch.device('cpu')     # weights can be held for planning / inspection; every compute call will raise
 
 
-class Executor(object):
-    """Runs a Plan on one device for a given batch size.  Buffers are cached per batch size."""
+class ScaleStage(object):
+    """The parameters of one 'scale' op (csrc/scale.hip): kind 'standard' | 'minmax' and the per-feature float64 device vectors
+    fill (the imputer's statistics_; input side only), shift (mean_ | min_) and scale (scale_) -- None where sklearn leaves that
+    stage out.  Uploaded once; the launches read them every time they run."""
 
-    def __init__(self, plan, device, activation_dtype='float32'):
+    def __init__(self, kind, fill=None, shift=None, scale=None, device=None):
+        if kind not in ('standard', 'minmax'):
+            raise ValueError("scaler kind must be 'standard' or 'minmax'")
+        up = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64).reshape(-1)).to(device)  # noqa: E731
+        self.kind, self.fill, self.shift, self.scale = kind, up(fill), up(shift), up(scale)
+
+    @property
+    def tensors(self):
+        return (self.shift, self.scale, self.fill)
+
+
+class Executor(object):
+    """Runs a Plan on one device for a given batch size.  Buffers are cached per batch size.
+    transform: {'head': ScaleStage | None, 'tail': ScaleStage | None} of a plan built with an input / output transform."""
+
+    def __init__(self, plan, device, activation_dtype='float32', transform=None):
         self.plan, self.device = plan, device
+        self.transform = dict(transform or {})
+        for op in plan.ops:
+            if op.kind == 'scale':
+                st = self.transform.get(op.role)
+                f = int(np.prod(op.xs))
+                if st is None or any(t is not None and t.numel() != f for t in st.tensors):
+                    raise ValueError("the plan's %s 'scale' op needs scaler parameters of %d features" % (op.role, f))
         self._bufs = {}
         self._descs = None
         self._pool2 = None      # _pooled_too(): convolutions of a training forward that store their pooled image as well
@@ -306,6 +330,12 @@ class Executor(object):
                 else:
                     ops.batchnorm_fwd_infer(src, lay.gamma, lay.beta, lay.moving_mean, lay.moving_variance, lay.epsilon,
                                             out=dst)
+            elif op.kind == 'scale':          # the wrapper's imputer + scaler in front, its inverse scaler behind (in place)
+                st = self.transform[op.role]
+                if op.role == 'head':
+                    ops.scale_fwd(src, st.kind, st.fill, st.shift, st.scale, out=dst)
+                else:
+                    ops.scale_inv(src, st.kind, st.shift, st.scale, out=dst)
             elif op.kind == 'lstm':
                 zh, cp, co = op.aux
                 ops.convlstm_gates(src, res(zh) if zh is not None else None, res(cp) if cp is not None else None,
@@ -454,6 +484,15 @@ class Executor(object):
                 if t is not None:
                     table.append(t)
             bidx[id(lay)] = ent
+        sidx = {}                                  # scaler / imputer: shift, scale, fill (index | -1), float64, per role
+        for role, st in self.transform.items():
+            if st is not None:
+                ent = []
+                for t in st.tensors:
+                    ent.append(len(table) if t is not None else -1)
+                    if t is not None:
+                        table.append(t)
+                sidx[role] = ent
         pidx = []                                  # derived (phase-summed) kernels: (w2 index, b2 index | -1)
         for w2, b2 in self.phase_buffers():
             pidx.append((len(table), len(table) + 1 if b2 is not None else -1))
@@ -463,7 +502,7 @@ class Executor(object):
         kind = {'conv': _lib.OP_CONV2D, 'pad': _lib.OP_PAD2D, 'maxpool': _lib.OP_MAXPOOL2,
                 'upsample': _lib.OP_UPSAMPLE2, 'copy': _lib.OP_COPYCH, 'lstm': _lib.OP_LSTM_GATES,
                 'phasew': _lib.OP_PHASE_WEIGHTS, 'd2s': _lib.OP_DEPTH2SPACE, 'rowconv': _lib.OP_ROWCONV2D,
-                'bn': _lib.OP_BATCHNORM, 'dense': _lib.OP_DENSE}
+                'bn': _lib.OP_BATCHNORM, 'dense': _lib.OP_DENSE, 'scale': _lib.OP_SCALE}
         arr = (_lib.Op * len(self.plan.ops))()
         for k, (op, d) in enumerate(zip(self.plan.ops, self._descriptors())):
             o = arr[k]
@@ -505,6 +544,11 @@ class Executor(object):
                 g_i, b_i, o.aux[0], o.aux[1] = bidx[id(op.layer)]
                 o.w, o.b = g_i, b_i
                 o.aux[2] = struct.unpack('<i', struct.pack('<f', op.layer.epsilon))[0]
+            elif op.kind == 'scale':                   # float64 parameters, read at every launch; the fill on the input side only
+                o.w, o.b, f_i = sidx[op.role]
+                o.aux[0] = f_i if (f_i >= 0 and op.role == 'head') else _lib.BUF_NONE
+                o.aux[1] = ops.SCALE_KINDS[self.transform[op.role].kind]
+                o.aux[2] = 0 if op.role == 'head' else 1
             elif op.kind == 'maxpool':
                 o.aux[0] = _lib.BF16 if op.src in self._bf16 else _lib.F32
             elif op.kind == 'pad':
@@ -700,6 +744,7 @@ class Model(object):
         self.history = None
         self._seed = seed
         self._trainer = None
+        self._scaled = None
         if inputs is not None:
             self._init_graph(inputs, outputs)
 
@@ -723,9 +768,51 @@ class Model(object):
         self.activation_dtype = getattr(self, 'activation_dtype', 'float32')
         self.executor = Executor(self.infer_plan, self.device, self.activation_dtype)
         self._train_executor = None
+        self._scaled = None      # set_io_transform: the second inference executor, with the wrapper's scaler in its plan
+        self.__dict__.pop('_io_transform_of', None)      # (what a wrapper last uploaded, DLWPNeuralNet._sync_device_transform)
+        self._drop_rollouts()
         self.input_shape = (None,) + tuple(self.inputs[0].shape)
         shapes = [(None,) + tuple(o.shape) for o in self.outputs]
         self.output_shape = shapes[0] if len(shapes) == 1 else shapes
+
+    # -- captured rollouts ----------------------------------------------------------------------------------------------- #
+    _ROLLOUT_CACHES = ('_rollouts', '_rollouts_streamed', '_rollouts_fed')
+
+    def _drop_rollouts(self):
+        """Forget every captured rollout, of the plain call and of the scaled variant (the graphs bury themselves): what they hold
+        -- weight addresses, the plan, the scaler's parameter addresses -- is about to change."""
+        for name in self._ROLLOUT_CACHES:
+            self.__dict__.pop(name, None)
+            self.__dict__.pop(name + '_scaled', None)
+
+    def _rollout_cache(self, name, scaled):
+        return self.__dict__.setdefault(name + '_scaled' if scaled else name, {})
+
+    # -- the wrapper's scaler and imputer as launches of the model call ---------------------------------------------------- #
+    def set_io_transform(self, head=None, tail=None):
+        """head / tail: ScaleStage | None -- SimpleImputer + scaler transform of the model input, inverse scaler transform of the
+        (single) model output (DLWPNeuralNet.predict, DLWP/model/models.py:230-245).  Builds a SECOND inference executor over a plan
+        that carries them as 'scale' ops (plan.build_plan(transform=...)), sharing the layers' weight tensors; float32 activation
+        storage.  Only calls that pass scaled=True run it: predict, predict_on_device, rollout_on_device, streamed_rollout and the
+        fed_rollout_* calls; every other call runs exactly the launches it ran before.  Both None: the variant is removed.  Captured
+        graphs are dropped (a refitted scaler never meets a graph made for the old one)."""
+        self._drop_rollouts()
+        self._scaled = None
+        self.__dict__.pop('_io_transform_of', None)
+        if head is None and tail is None:
+            return self
+        plan = P.build_plan(self.inputs, self.outputs, inference=True, transform=(head is not None, tail is not None))
+        self._scaled = Executor(plan, self.device, 'float32', transform={'head': head, 'tail': tail})
+        return self
+
+    def _executor_of(self, scaled):
+        if not scaled:
+            return self.executor
+        if self._scaled is None:
+            raise RuntimeError('scaled=True needs an input / output transform (Model.set_io_transform)')
+        if self.activation_dtype != 'float32':
+            raise NotImplementedError('the scaled model call runs on float32 activation storage only')
+        return self._scaled
 
     # -- storage type of the activations between the layers (inference) ------------------------------------------------- #
     def set_activation_dtype(self, dtype):
@@ -758,8 +845,7 @@ class Model(object):
                 self.infer_plan = P.build_plan(self.inputs, self.outputs, inference=True, fuse_d2s=False, fuse_lstm=True,
                                                fuse_lstm_step=False)
                 self.executor = Executor(self.infer_plan, self.device, dtype)
-            self.__dict__.pop('_rollouts', None)
-            self.__dict__.pop('_rollouts_streamed', None)
+            self._drop_rollouts()
         return self
 
     @property
@@ -818,17 +904,19 @@ class Model(object):
         res = [o.reshape((n,) + tuple(s)) for o, s in zip(outs, self.plan.output_shapes)]
         return res
 
-    def predict_on_device(self, x):
-        """x: float32 device tensor (n,)+input_shape  ->  device tensor (or list for multi-output models)."""
+    def predict_on_device(self, x, scaled=False):
+        """x: float32 device tensor (n,)+input_shape  ->  device tensor (or list for multi-output models).
+        scaled: through the wrapper's imputer / scaler (set_io_transform) -- unscaled in, unscaled out."""
         if x.dtype != torch.float32:
             x = x.float()
         x = x.contiguous()
-        outs = self._logical_outputs(self.executor.run(x), x.shape[0])
+        outs = self._logical_outputs(self._executor_of(scaled).run(x), x.shape[0])
         return outs[0] if len(outs) == 1 else outs
 
-    def predict(self, x, batch_size=None, verbose=0, steps=None, **kwargs):
+    def predict(self, x, batch_size=None, verbose=0, steps=None, scaled=False, **kwargs):
         """numpy in, numpy out (Keras contract).  batch_size only bounds the device working set: results do not depend
-        on it (tests/test_gpu_model.py checks bit-identity)."""
+        on it (tests/test_gpu_model.py checks bit-identity).  scaled: as predict_on_device."""
+        on_device = (lambda t: self.predict_on_device(t, scaled=True)) if scaled else self.predict_on_device
         x = np.ascontiguousarray(x, dtype=np.float32)
         if tuple(x.shape[1:]) != tuple(self.inputs[0].shape):
             raise ValueError('expected input of shape %r, got %r' % ((None,) + tuple(self.inputs[0].shape), x.shape))
@@ -844,7 +932,7 @@ class Model(object):
             pinned = None
             for lo in range(0, n, chunk):
                 xd = torch.from_numpy(x[lo:lo + chunk]).to(self.device, non_blocking=False)
-                outs = self.predict_on_device(xd)
+                outs = on_device(xd)
                 outs = outs if isinstance(outs, list) else [outs]
                 if pinned is None:
                     pinned = [host_result_buffer((n,) + tuple(o.shape[1:])) for o in outs]
@@ -861,7 +949,7 @@ class Model(object):
             return results[0] if len(results) == 1 else results
         for lo in range(0, n, chunk):
             xd = torch.from_numpy(x[lo:lo + chunk]).to(self.device, non_blocking=False)
-            outs = self.predict_on_device(xd)
+            outs = on_device(xd)
             outs = outs if isinstance(outs, list) else [outs]
             host = [o.cpu().numpy() for o in outs]
             if results is None:
@@ -872,18 +960,20 @@ class Model(object):
             results = [np.empty((0,) + tuple(s), dtype=np.float32) for s in self.plan.output_shapes]
         return results[0] if len(results) == 1 else results
 
-    def rollout_on_device(self, state0, calls, series=None, graph_cache=True):
+    def rollout_on_device(self, state0, calls, series=None, graph_cache=True, scaled=False):
         """Autoregressive rollout entirely in HBM: returns series (calls*n_outputs, n)+input_shape (device).
-        The captured hipGraph is cached per (n, calls) and replayed on later calls."""
+        The captured hipGraph is cached per (n, calls) and replayed on later calls.  scaled: every call through the wrapper's
+        imputer / scaler (set_io_transform; graphs cached apart); state and series stay in unscaled units."""
         n = state0.shape[0]
         n_out = len(self.outputs)
         key = (n, int(calls))
-        cache = self.__dict__.setdefault('_rollouts', {})
+        executor = self._executor_of(scaled)
+        cache = self._rollout_cache('_rollouts', scaled)
         entry = cache.get(key) if graph_cache else None
         if entry is None:
             s0 = torch.empty((n,) + self.plan._in_store, dtype=torch.float32, device=self.device)
             ser = torch.empty((calls * n_out, n) + self.plan._in_store, dtype=torch.float32, device=self.device)
-            g = self.executor.make_rollout(s0, ser, calls)
+            g = executor.make_rollout(s0, ser, calls)
             entry = (g, s0, ser)
             if graph_cache:
                 if len(cache) > 2:
@@ -898,8 +988,9 @@ class Model(object):
             return series
         return out
 
-    def _fed_entry(self, n, calls, src, shift, tail, sol, sol_map, mean, sliced):
+    def _fed_entry(self, n, calls, src, shift, tail, sol, sol_map, mean, sliced, scaled=False):
         """the cached graphs + buffers of a fed rollout: one graph of all calls, or (sliced) one graph per call"""
+        executor = self._executor_of(scaled)
         if len(self.plan.output_store) != 1:
             raise ValueError('a fed rollout needs a model with one output')
         c_in, h, w = self.plan._in_store
@@ -910,7 +1001,7 @@ class Model(object):
         sol_map = tuple(int(v) for v in sol_map) if sol is not None else None
         planes = int(sol.shape[2]) if sol is not None else 0
         key = (n, calls, src, int(shift), int(tail), sol_map, planes, mean is not None, bool(sliced))
-        cache = self.__dict__.setdefault('_rollouts_fed', {})
+        cache = self._rollout_cache('_rollouts_fed', scaled)
         ent = cache.get(key)
         if ent is None:
             from . import ops
@@ -926,11 +1017,11 @@ class Model(object):
             mean_d = torch.empty((c_in, h, w), **f32) if mean is not None else None
             fed = (fb, sb, sol_d, mean_d, calls)
             if not sliced:
-                graphs = [self.executor._make_rollout(sa, ser, calls, fed=fed)]
+                graphs = [executor._make_rollout(sa, ser, calls, fed=fed)]
             else:
                 graphs = []
                 for j in range(calls):
-                    graphs.append(self.executor._make_rollout(sa, ser, calls, fed=fed, span=(j, 1),
+                    graphs.append(executor._make_rollout(sa, ser, calls, fed=fed, span=(j, 1),
                                                               ws=graphs[0].ws if graphs else None, prepared=bool(graphs)))
             ent = cache[key] = (graphs, sa, sb, ser, sol_d, mean_d)
         return ent
@@ -945,21 +1036,23 @@ class Model(object):
         if mean_d is not None:
             mean_d.copy_(as_dev(mean).reshape(mean_d.shape), non_blocking=True)
 
-    def fed_rollout_on_device(self, state0, calls, src, shift=0, tail=0, sol=None, sol_map=None, mean=None):
+    def fed_rollout_on_device(self, state0, calls, src, shift=0, tail=0, sol=None, sol_map=None, mean=None, scaled=False):
         """A rollout whose outputs are NOT its next inputs, entirely in HBM (dlwp_rollout_create_fed): between two model calls ONE
         launch builds the next state from the old one (rows shifted by `shift`), the call's output (src[c] = -1 - j), the insolation
         block of the call (sol: (calls - 1, tail, planes) + grid, channel c takes plane sol_map[c]) and the mean state -- the
         bookkeeping TimeSeriesEstimator.predict does on the host with xarray between two model.predict round trips
         (DLWP/model/extensions.py:206-240) and the step_sequence shift of DLWP/model/models.py:280-290.
-        state0: (n,) + input shape, device or host.  Returns the device series (calls, n) + output shape; cached per configuration."""
+        state0: (n,) + input shape, device or host.  Returns the device series (calls, n) + output shape; cached per configuration.
+        scaled: every model call through the wrapper's imputer / scaler (set_io_transform); the states, the mean and the series are
+        in unscaled units, as in the reference's loop."""
         n, calls = int(state0.shape[0]), int(calls)
-        ent = self._fed_entry(n, calls, src, shift, tail, sol, sol_map, mean, sliced=False)
+        ent = self._fed_entry(n, calls, src, shift, tail, sol, sol_map, mean, sliced=False, **({'scaled': True} if scaled else {}))
         self._fed_inputs(ent, calls, state0, sol, mean)
         ent[0][0].launch()
         return ent[3].reshape((calls, n) + tuple(self.plan.output_shapes[0]))
 
     def fed_rollout_to_host(self, state0, calls, src, shift=0, tail=0, sol=None, sol_map=None, mean=None, t_out=1, kept=None,
-                            perm=None, time_major=True, blocks=None):
+                            perm=None, time_major=True, blocks=None, scaled=False):
         """The same forecast with its series going home WHILE it runs, in the layout the reference returns
         (DLWP/model/extensions.py:243-302): one hipGraph per model call (call + feedback), launched back to back; behind call j, on
         a copy stream, its output (n, t_out, C) is arranged into its block of the result -- time first (kept, n, C) or, time_major
@@ -969,7 +1062,7 @@ class Model(object):
         import ctypes as ct
         from . import _lib, util
         n, calls = int(state0.shape[0]), int(calls)
-        ent = self._fed_entry(n, calls, src, shift, tail, sol, sol_map, mean, sliced=True)
+        ent = self._fed_entry(n, calls, src, shift, tail, sol, sol_map, mean, sliced=True, **({'scaled': True} if scaled else {}))
         graphs, _, _, ser, _, _ = ent
         c_tot, h, w = self.plan.output_store[0]
         t_out = int(t_out)
@@ -1022,26 +1115,26 @@ class Model(object):
                 main.wait_stream(s_)
         return util.pinned_results.lend(host)
 
-    def streamed_rollout(self, n, calls, head_chunks=4):
+    def streamed_rollout(self, n, calls, head_chunks=4, scaled=False):
         """The time-sliced rollout of n members x `calls` model applications (Executor.make_streamed_rollout), cached like the
-        one-graph rollouts of rollout_on_device."""
+        one-graph rollouts of rollout_on_device (scaled: as there)."""
         key = (int(n), int(calls), int(head_chunks))
-        cache = self.__dict__.setdefault('_rollouts_streamed', {})
+        executor = self._executor_of(scaled)
+        cache = self._rollout_cache('_rollouts_streamed', scaled)
         ent = cache.get(key)
         if ent is None:
             if cache:
                 for old in cache.values():
                     old.close()
                 cache.clear()
-            ent = cache[key] = self.executor.make_streamed_rollout(n, calls, head_chunks)
+            ent = cache[key] = executor.make_streamed_rollout(n, calls, head_chunks)
         return ent
 
     # -- training (dlwp_amd.training) ---------------------------------------------------------------------------------- #
     @_mirrored
     def compile(self, optimizer='adam', loss=None, metrics=None, loss_weights=None, **kwargs):
         from . import training
-        self.__dict__.pop('_rollouts', None)     # compile re-homes the weights into one flat buffer: drop captured graphs
-        self.__dict__.pop('_rollouts_streamed', None)
+        self._drop_rollouts()                    # compile re-homes the weights into one flat buffer: drop captured graphs
         self.optimizer = training.get_optimizer(optimizer)
         self.loss = loss
         self.loss_weights = loss_weights

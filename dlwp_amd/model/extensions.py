@@ -26,7 +26,7 @@ stays in HBM, one launch between two model calls does the row shift, the NaN / m
 past the data (a table computed once for all lead times before the rollout: util.insolation depends on the times
 only) and the scatter of the predicted channels, all calls in ONE hipGraph.  The reference's form of the same loop --
 model.predict (H2D + D2H of the full state) and three host copies of the state per step -- remains for foreign model
-objects, scalers and DLWP_ESTIMATOR_HOST=1 (the parity tests run both and compare bit for bit).
+objects, scalers the device path does not cover and DLWP_ESTIMATOR_HOST=1 (the parity tests run both and compare bit for bit).
 The result carries the reference's coordinates (f_hour, time, [time_step,] varlev | variable, level, lat, lon) in a
 LabeledArray.
 """
@@ -85,14 +85,15 @@ class TimeSeriesEstimator(object):
 
     def _fed_rollout_ok(self, p_shape, t_shape, n, calls=1):
         """Can the whole loop run on the device?  A dlwp_amd network behind a DLWPNeuralNet / single-output DLWPFunctional with
-        identity scaling, stored as (channels, lat, lon) with at most 128 state channels, and room in HBM for the two states, the
-        series and the activations of all samples at once (the row shift couples the samples: they are not chunked)."""
+        identity scaling or a scaler / imputer the model call carries itself (DLWPNeuralNet._device_io), stored as (channels, lat,
+        lon) with at most 128 state channels, and room in HBM for the two states, the series and the activations of all samples at
+        once (the row shift couples the samples: they are not chunked)."""
         import os
         wrapper, net = self.model, getattr(self.model, 'model', None)
         if os.environ.get('DLWP_ESTIMATOR_HOST', '0') == '1' or not hasattr(net, 'fed_rollout_on_device'):
             return False
-        if getattr(wrapper, 'impute', False) or getattr(wrapper, 'scaler_type', None) is not None:
-            return False
+        if self._wrapper_scales() and not (hasattr(wrapper, '_device_io') and wrapper._device_io()):
+            return False                                            # (a scaler / imputer the model call cannot carry: host loop)
         if len(net.outputs) != 1 or tuple(p_shape[1:]) != tuple(net.inputs[0].shape) or \
                 tuple(t_shape[1:]) != tuple(net.outputs[0].shape) or net.device.type != 'cuda':
             return False
@@ -104,6 +105,9 @@ class TimeSeriesEstimator(object):
         need = 4 * n * sum(int(np.prod(b)) for b in net.infer_plan.buffers) + 8 * int(np.prod(p_shape)) + \
             4 * int(calls) * int(np.prod(t_shape)) + 8 * int(np.prod(t_shape))         # activations, two states, the series, staging
         return need < 0.8 * free
+
+    def _wrapper_scales(self):
+        return bool(getattr(self.model, 'impute', False) or getattr(self.model, 'scaler_type', None) is not None)
 
     # -- the forecast ------------------------------------------------------------------------------------------------ #
     def predict(self, steps, impute=False, keep_time_dim=False, prefer_first_times=True, **kwargs):
@@ -218,6 +222,8 @@ class TimeSeriesEstimator(object):
                 for s in range(effective_steps):
                     print('Time step %d/%d' % (s + 1, effective_steps))
             fed = dict(shift=k, tail=tail, sol=sol, sol_map=sol_map, mean=p_mean.reshape((t_in * c_in,) + hw) if impute else None)
+            if self._wrapper_scales():          # the wrapper's imputer / scaler run inside every model call (_fed_rollout_ok)
+                fed['scaled'] = True
             if return_device:
                 return self.model.model.fed_rollout_on_device(p.reshape((n, t_in * c_in) + hw), effective_steps, src, **fed)
             # the series leaves for the host while the rollout runs, each call's block already in the returned layout: time first,

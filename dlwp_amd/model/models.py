@@ -73,11 +73,12 @@ class _Wrapper(object):
         return (hasattr(net, 'rollout_on_device') and tuple(predictors.shape[1:]) == tuple(net.inputs[0].shape)
                 and all(tuple(o.shape) == tuple(net.inputs[0].shape) for o in net.outputs))
 
-    def _rollout_chunk(self, x, calls, keep_time_dim, fresh=False):
+    def _rollout_chunk(self, x, calls, keep_time_dim, fresh=False, scaled=False):
         """All `calls` model applications of the members in device tensor x as one hipGraph; merge of the time axis on the
-        device too.  fresh: the result must not alias the graph's cached series buffer."""
+        device too.  fresh: the result must not alias the graph's cached series buffer.  scaled: every call through the wrapper's
+        imputer / scaler on the device (DLWPNeuralNet._device_io)."""
         from .. import ops
-        series = self.model.rollout_on_device(x, calls)          # (calls*n_out, N) + state shape
+        series = self.model.rollout_on_device(x, calls, **({'scaled': True} if scaled else {}))   # (calls*n_out, N) + state shape
         n_slots, n_sample = series.shape[0], series.shape[1]
         if series.dim() == 3:            # a dense model: (slots, N, F) -> (slots, N, time_dim, F / time_dim) or time-major
             if keep_time_dim:
@@ -103,7 +104,7 @@ class _Wrapper(object):
     #: starts on the first chunk while the others are still being uploaded
     host_head_chunks = 4
 
-    def _rollout_device(self, predictors, calls, keep_time_dim, return_device=False):
+    def _rollout_device(self, predictors, calls, keep_time_dim, return_device=False, scaled=False):
         import torch
         net = self.model
         on_host = not isinstance(predictors, torch.Tensor)
@@ -116,11 +117,11 @@ class _Wrapper(object):
         if not streamed:
             x = predictors if not on_host else \
                 torch.from_numpy(np.ascontiguousarray(predictors, dtype=np.float32)).to(net.device)
-            out = self._rollout_chunk(x, calls, keep_time_dim)
+            out = self._rollout_chunk(x, calls, keep_time_dim, scaled=scaled)
             return out if return_device else out.cpu().numpy()
-        return self._rollout_streamed(predictors, calls, keep_time_dim)
+        return self._rollout_streamed(predictors, calls, keep_time_dim, scaled=scaled)
 
-    def _rollout_streamed(self, predictors, calls, keep_time_dim):
+    def _rollout_streamed(self, predictors, calls, keep_time_dim, scaled=False):
         """The rollout with its series going home WHILE it runs (the metric's own API -- numpy in, numpy out,
         DLWP/model/models.py:265-301, call site examples/plot_forecasts.py:234-239 -- at the device-resident speed).
         The rollout is one hipGraph PER MODEL CALL (engine.StreamedRollout), all members in each, launched back to back on the
@@ -149,7 +150,7 @@ class _Wrapper(object):
         on_host = not isinstance(predictors, torch.Tensor)
         n = int(predictors.shape[0])
         td = int(self.time_dim)
-        sr = net.streamed_rollout(n, calls, int(self.host_head_chunks) if on_host else 1)
+        sr = net.streamed_rollout(n, calls, int(self.host_head_chunks) if on_host else 1, **({'scaled': True} if scaled else {}))
         n_out = sr.n_out
         member = int(sr.s0[0].numel())
         run = member // td
@@ -381,6 +382,137 @@ class DLWPNeuralNet(_Wrapper):
         self.scaler_fit(predictors, targets, **(scaler_kwargs or {}))
         self._is_init_fit = True
 
+    # -- scaling / imputing on the device (csrc/scale.hip): predict and the rollouts of a scaled wrapper stay in HBM ------ #
+    def device_transform_stages(self):
+        """Can the model call carry this wrapper's imputer and scaler as launches of its own?  False, or the stages
+        {'head': {'kind', 'fill', 'shift', 'scale'} | None, 'tail': {'kind', 'shift', 'scale'} | None} with kind 'standard' |
+        'minmax' | None (an imputer alone) and one flag per parameter vector that takes part.  Eligible:
+          * the network is a dlwp_amd model on a CUDA device with float32 activation storage and exactly one output, no data-parallel
+            driver attached (gpus == 1);
+          * the scaler is exactly a StandardScaler (any with_mean / with_std), exactly a MinMaxScaler with clip=False, or None --
+            subclasses may override transform, so they stay on the host;
+          * the imputer, where impute_missing is set, is exactly a SimpleImputer(strategy='mean') for NaN without a NaN in
+            statistics_ (sklearn drops such columns: the shape changes);
+          * every parameter vector has the flattened input size -- the output size too for the inverse transform, and the output
+            is a vector per sample there (sklearn's inverse_transform refuses arrays of more than two axes: that call raises as before).
+        scale_targets=False: no inverse transform behind the call; apply_same_y_scaling=False: it takes scaler_y's parameters."""
+        net = self.model
+        if net is None or not hasattr(net, 'set_io_transform') or getattr(net, 'device', None) is None or net.device.type != 'cuda':
+            return False
+        if getattr(net, 'activation_dtype', 'float32') != 'float32' or len(net.outputs) != 1 or int(self.gpus) != 1 or \
+                net.__dict__.get('_driver') is not None:
+            return False
+        f_in, f_out = int(np.prod(net.inputs[0].shape)), int(np.prod(net.outputs[0].shape))
+
+        def scaler_stage(sc, f):
+            """(kind, shift used, scale used) of a fitted scaler of f features, or None"""
+            try:
+                from sklearn.preprocessing import MinMaxScaler, StandardScaler
+            except ImportError:
+                return None
+            if type(sc) is StandardScaler:
+                if not hasattr(sc, 'scale_'):
+                    return None
+                use = (bool(sc.with_mean), bool(sc.with_std))
+                par = (sc.mean_ if use[0] else None, sc.scale_ if use[1] else None)
+            elif type(sc) is MinMaxScaler:
+                if getattr(sc, 'clip', False) or not hasattr(sc, 'scale_'):
+                    return None
+                use, par = (True, True), (sc.min_, sc.scale_)
+            else:
+                return None
+            if any(u and (a is None or np.ndim(a) != 1 or len(a) != f) for u, a in zip(use, par)):
+                return None
+            return {'kind': 'standard' if type(sc) is StandardScaler else 'minmax', 'shift': use[0], 'scale': use[1]}
+
+        head = {'kind': None, 'fill': False, 'shift': False, 'scale': False}
+        if self.impute:
+            try:
+                from sklearn.impute import SimpleImputer
+            except ImportError:
+                return False
+            im = self.imputer
+            if type(im) is not SimpleImputer or im.strategy != 'mean' or not hasattr(im, 'statistics_') or \
+                    getattr(im, 'add_indicator', False):
+                return False
+            mv = im.missing_values
+            if not (isinstance(mv, float) and mv != mv):
+                return False
+            st = np.asarray(im.statistics_)
+            if st.ndim != 1 or len(st) != f_in or st.dtype.kind != 'f' or np.isnan(st).any():
+                return False
+            head['fill'] = True
+        tail = None
+        if self.scaler_type is not None:
+            got = scaler_stage(self.scaler, f_in)
+            if got is None:
+                return False
+            head.update(got)
+            if self.scale_targets:
+                if len(net.outputs[0].shape) != 1:
+                    return False
+                tail = scaler_stage(self.scaler_y, f_out)
+                if tail is None:
+                    return False
+        if tail is not None and not (tail['shift'] or tail['scale']):
+            tail = None
+        if not (head['fill'] or head['shift'] or head['scale']):
+            head = None
+        return {'head': head, 'tail': tail}
+
+    def _transform_sources(self):
+        """what the uploaded parameters were made from: compared by identity at every call, so a refit (init_fit makes new scaler
+        objects, fit() new parameter arrays) or a scaler / imputer assigned from a loaded wrapper is uploaded again"""
+        objs = [self.model, self.scaler, self.scaler_y, self.imputer]
+        for sc in (self.scaler, self.scaler_y, self.imputer):
+            for name in ('mean_', 'scale_', 'min_', 'statistics_'):
+                objs.append(getattr(sc, name, None))
+        flags = (self.scaler_type, bool(self.scale_targets), bool(self.apply_same_y_scaling), bool(self.impute), int(self.gpus),
+                 getattr(self.model, 'activation_dtype', None),
+                 tuple(getattr(sc, name, None) for sc in (self.scaler, self.scaler_y) for name in ('with_mean', 'with_std', 'clip')))
+        return objs, flags
+
+    def _sync_device_transform(self):
+        """Decide eligibility and upload the parameters (float64: sklearn's own values, exactly) when the scaler, the imputer or the
+        network changed since the last time; the network keeps the result (this object stays picklable, util.save_model)."""
+        net = self.model
+        if net is None or not hasattr(net, 'set_io_transform'):
+            return False
+        objs, flags = self._transform_sources()
+        have = net.__dict__.get('_io_transform_of')
+        if have is not None and have[1] == flags and len(have[0]) == len(objs) and all(a is b for a, b in zip(have[0], objs)):
+            return have[2]
+        stages = self.device_transform_stages()
+        if stages and (stages['head'] or stages['tail']):
+            from ..engine import ScaleStage
+
+            def stage(flags_, sc, im):
+                if flags_ is None:
+                    return None
+                shift = (sc.mean_ if flags_['kind'] == 'standard' else sc.min_) if flags_['shift'] else None
+                return ScaleStage(flags_['kind'] or 'standard', fill=im.statistics_ if flags_.get('fill') else None, shift=shift,
+                                  scale=sc.scale_ if flags_['scale'] else None, device=net.device)
+            net.set_io_transform(stage(stages['head'], self.scaler, self.imputer), stage(stages['tail'], self.scaler_y, None))
+        else:
+            stages = False
+            if net.__dict__.get('_scaled') is not None:
+                net.set_io_transform(None, None)
+        net.__dict__['_io_transform_of'] = (objs, flags, stages)
+        return stages
+
+    def _device_io(self, predictors=None):
+        """The stages (device_transform_stages) when THIS call may run the imputer / scaler on the device, else False: a wrapper that
+        scales or imputes, not forced to the host (DLWP_SCALER_HOST=1), float32 data (sklearn transforms float64 arrays in float64:
+        another rounding) and an eligible scaler."""
+        import os
+        if (self.scaler_type is None and not self.impute) or os.environ.get('DLWP_SCALER_HOST', '0') == '1':
+            return False
+        if predictors is not None:
+            dt = getattr(predictors, 'dtype', None)
+            if dt is None or str(dt) not in ('float32', 'torch.float32'):
+                return False
+        return self._sync_device_transform()
+
     # -- fit / predict / evaluate ------------------------------------------------------------------------------------- #
     def _prepare(self, predictors, targets=None):
         if self.impute:
@@ -410,6 +542,9 @@ class DLWPNeuralNet(_Wrapper):
         return self.model.fit_generator(generator, **kwargs)
 
     def predict(self, predictors, **kwargs):
+        if self._device_io(predictors):
+            # imputer, scaler and inverse scaler are launches of the model call: one upload, one download, sklearn's bits
+            return self.model.predict(predictors, scaled=True, **kwargs)
         predicted = self.model.predict(self._prepare(predictors), **kwargs)
         if self.scale_targets and self.scaler_type is not None:
             return self.scaler_y.inverse_transform(predicted)
@@ -433,9 +568,12 @@ class DLWPNeuralNet(_Wrapper):
             return drv.sharded_rollout(self, predictors, time_steps, dict(kwargs, step_sequence=step_sequence,
                                                                            keep_time_dim=keep_time_dim))
         n_calls = time_steps if step_sequence else int(math.ceil(1. * time_steps / self.time_dim))
-        identity_io = (not self.impute) and (self.scaler_type is None)
+        # a scaled / imputing wrapper whose transforms run inside the model call (_device_io) takes the device paths of an identity
+        # wrapper: state and series stay in unscaled units, as in the reference's loop (out = self.predict(state); state = out)
+        scaled = bool(self._device_io(predictors))
+        identity_io = ((not self.impute) and (self.scaler_type is None)) or scaled
         if identity_io and not step_sequence and self._device_rollout_ok(predictors):
-            return self._rollout_device(predictors, n_calls, keep_time_dim, return_device)
+            return self._rollout_device(predictors, n_calls, keep_time_dim, return_device, scaled=scaled)
         if identity_io and step_sequence and self._device_rollout_ok(predictors) and self.model.device.type == 'cuda' and \
                 hasattr(self.model, 'fed_rollout_on_device'):
             # one predicted step per call: the next input is the last time_dim - 1 input steps + the FIRST predicted step
@@ -449,12 +587,12 @@ class DLWPNeuralNet(_Wrapper):
                 if kwargs.get('verbose', 0) > 0:
                     for t in range(n_calls):
                         print('Time step %d/%d' % (t + 1, n_calls))
-                series = self.model.fed_rollout_on_device(predictors, n_calls, src)
+                series = self.model.fed_rollout_on_device(predictors, n_calls, src, **({'scaled': True} if scaled else {}))
                 merged = series.reshape((n_calls, int(predictors.shape[0]), td, -1) + tuple(predictors.shape[-2:]))
                 if not keep_time_dim:
                     merged = merged[:, :, 0]
                 return merged.contiguous() if return_device else merged.cpu().numpy()
-        # generic host loop (foreign model objects, scalers)
+        # generic host loop (foreign model objects, scalers the device path does not cover, DLWP_SCALER_HOST=1)
         verbose = kwargs.get('verbose', 0)
         n_sample = predictors.shape[0]
         feature_shape = self._feature_shape(predictors)

@@ -1102,6 +1102,53 @@ def batchnorm_bwd(x, dy, gamma, save_mean, save_invstd, ws, dgamma=None, dbeta=N
 
 
 # ------------------------------------------------------------------------------------------------------------------ #
+# the wrapper's scaler and imputer (csrc/scale.hip)
+# ------------------------------------------------------------------------------------------------------------------ #
+SCALE_KINDS = {'standard': _lib.SCALE_STANDARD, 'minmax': _lib.SCALE_MINMAX}
+
+
+def _scale_desc(x, kind, *params):
+    """x: (n, ...) float32 -- a sample's features are everything behind the first axis; params: float64 vectors of that length"""
+    if x.dtype != torch.float32 or x.dim() < 1:
+        raise ValueError('expected a float32 tensor of samples, got %s' % x.dtype)
+    n = int(x.shape[0])
+    f = 1
+    for s in x.shape[1:]:
+        f *= int(s)
+    for p in params:
+        if p is not None and (p.dtype != torch.float64 or not p.is_contiguous() or p.numel() != f or p.device != x.device):
+            raise ValueError('scaler parameters are contiguous float64 vectors of %d features on the device of x' % f)
+    return _lib.Scale(n, f, SCALE_KINDS[kind] if not isinstance(kind, int) else int(kind))
+
+
+def _scale_out(x, out):
+    if not x.is_contiguous():
+        raise ValueError('expected a contiguous tensor')
+    y = out if out is not None else torch.empty_like(x)
+    if y.dtype != torch.float32 or not y.is_contiguous() or y.numel() != x.numel():
+        raise ValueError('out must be a contiguous float32 tensor of the size of x')
+    return y
+
+
+def scale_fwd(x, kind, fill=None, shift=None, scale=None, out=None):
+    """SimpleImputer.transform (fill = statistics_), then the scaler's transform: 'standard' (x - shift) / scale with shift / scale =
+    mean_ / scale_, 'minmax' x * scale + shift with shift / scale = min_ / scale_.  Every parameter is a float64 device vector or
+    None (that stage is left out); sklearn's arithmetic bit for bit (include/dlwp_hip.h).  out may be x."""
+    d = _scale_desc(x, kind, fill, shift, scale)
+    y = _scale_out(x, out)
+    _lib.check(_lib.lib.dlwp_scale_fwd(_lib.handle(_dev(x)), _ptr(x), _ptr(y), _ptr(fill), _ptr(shift), _ptr(scale), d, _stream(x)))
+    return y
+
+
+def scale_inv(x, kind, shift=None, scale=None, out=None):
+    """The scaler's inverse_transform: 'standard' x * scale + shift, 'minmax' (x - shift) / scale.  out may be x."""
+    d = _scale_desc(x, kind, shift, scale)
+    y = _scale_out(x, out)
+    _lib.check(_lib.lib.dlwp_scale_inv(_lib.handle(_dev(x)), _ptr(x), _ptr(y), _ptr(shift), _ptr(scale), d, _stream(x)))
+    return y
+
+
+# ------------------------------------------------------------------------------------------------------------------ #
 # Dense and Dropout (csrc/dense.hip)
 # ------------------------------------------------------------------------------------------------------------------ #
 

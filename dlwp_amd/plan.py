@@ -65,7 +65,8 @@ class View(object):
 
 
 class PlanOp(object):
-    """One launch.  kind in {'conv','rowconv','pad','maxpool','upsample','copy','lstm','phasew','d2s','bn','dense','dropout'}."""
+    """One launch.  kind in {'conv','rowconv','pad','maxpool','upsample','copy','lstm','phasew','d2s','bn','dense','dropout',
+    'scale'}."""
 
     def __init__(self, kind, src, dst, xs, **kw):
         self.kind, self.src, self.dst = kind, src, dst
@@ -97,6 +98,9 @@ class PlanOp(object):
         self.filters = kw.pop('filters', None)    # output channels
         self.wparam = kw.pop('wparam', None)      # index into plan.phase_params: derived kernel / bias instead of the layer's
         self.alg_flops = kw.pop('alg_flops', None)   # algorithmic FLOPs per sample of the ORIGINAL layer
+        # scale only (inference plans with an input / output transform): 'head' = imputer + scaler transform of the model input,
+        # 'tail' = the scaler's inverse transform of the model output; the executor holds the parameters
+        self.role = kw.pop('role', None)
         assert not kw, kw
 
     @property
@@ -322,12 +326,21 @@ def _supports_lstm_step(lay, f, ho, wo, t_len, cin, v, halo, act, rec_act):
         return False
 
 
-def build_plan(inputs, outputs, inference=False, fuse_d2s=True, fuse_lstm=False, fuse_lstm_step=True):
+def build_plan(inputs, outputs, inference=False, fuse_d2s=True, fuse_lstm=False, fuse_lstm_step=True, transform=None):
     """inputs: [KTensor] (exactly one), outputs: [KTensor].  Returns a Plan.  inference=True additionally moves a
     MaxPooling2D(2) that is the only consumer of a convolution into that convolution's epilogue (the pre-pooling tensor
-    is never written; the training plan keeps it because the backward pass needs it)."""
+    is never written; the training plan keeps it because the backward pass needs it).
+    transform = (head, tail) (inference plans of a model with one output): the wrapper's imputer / scaler as launches of the model
+    call (csrc/scale.hip).  head: a 'scale' op in front reads the input state and writes a buffer of its own, which every consumer
+    of the model input reads instead; tail: a 'scale' op at the end rewrites the output slot in place.  The state a rollout feeds
+    back therefore stays in unscaled units."""
     if len(inputs) != 1:
         raise NotImplementedError('exactly one model input is supported')
+    head, tail = (bool(transform[0]), bool(transform[1])) if transform is not None else (False, False)
+    if (head or tail) and not inference:
+        raise ValueError('an input / output transform belongs to inference plans: training data is prepared on the host')
+    if tail and len(outputs) != 1:
+        raise ValueError('an output transform needs a model with exactly one output, got %d' % len(outputs))
     plan = Plan()
     x_in = inputs[0]
     plan.input_shape = tuple(x_in.shape)
@@ -358,6 +371,10 @@ def build_plan(inputs, outputs, inference=False, fuse_d2s=True, fuse_lstm=False,
 
     plan._in_store = store_of(x_in.shape)
     views = {}
+    in_buf = STATE_IN                  # what the consumers of the model input read
+    if head:
+        in_buf = plan.new_buffer(*plan._in_store)
+        plan.ops.append(PlanOp('scale', STATE_IN, in_buf, plan._in_store, role='head', out_shape=plan._in_store))
 
     producer = {}                      # scratch buffer -> the conv op that wrote all of it
 
@@ -419,7 +436,7 @@ def build_plan(inputs, outputs, inference=False, fuse_d2s=True, fuse_lstm=False,
             if t.uid != x_in.uid:
                 raise ValueError('graph reaches an Input that is not the model input')
             c, h, w = plan._in_store
-            views[t.uid] = View(STATE_IN, 0, c, c, h, w, shape=tuple(t.shape) if len(t.shape) != 3 else None)
+            views[t.uid] = View(in_buf, 0, c, c, h, w, shape=tuple(t.shape) if len(t.shape) != 3 else None)
             continue
         ins = [views[i.uid] for i in t.inputs]
         outs = out_index.get(t.uid, [])
@@ -814,4 +831,6 @@ def build_plan(inputs, outputs, inference=False, fuse_d2s=True, fuse_lstm=False,
     for o, st in enumerate(plan.output_store):
         if st is None:
             raise RuntimeError('output %d was never produced' % o)
+    if tail:
+        plan.ops.append(PlanOp('scale', OUT(0), OUT(0), plan.output_store[0], role='tail', out_shape=plan.output_store[0]))
     return plan

@@ -607,6 +607,31 @@ typedef struct {
 int dlwp_dropout_fwd(dlwp_handle_t, const void* x, void* y, long long n, dlwp_dropout d, void* stream);
 int dlwp_dropout_bwd(dlwp_handle_t, const void* dy, void* dx, long long n, dlwp_dropout d, void* stream);
 
+/* ---- the wrapper's scaler and imputer on the device: DLWPNeuralNet(scaler_type='StandardScaler' | 'MinMaxScaler',
+ *      impute_missing=True) runs SimpleImputer.transform and the scaler's transform in front of every model call and the
+ *      scaler's inverse_transform behind it (DLWP/model/models.py:134-170, 230-245) -- sklearn on the host.  Here one launch per
+ *      direction on n samples of f contiguous float32 features (csrc/scale.hip).  fill / shift / scale: per-feature FLOAT64
+ *      device arrays of f elements (sklearn's statistics_, mean_ | min_, scale_), each nullable = that stage is left out
+ *      (no imputer, with_mean=False, with_std=False).  The arithmetic is numpy's when sklearn updates a float32 array in place
+ *      with float64 parameters -- every stage in double, rounded to float32 BEFORE the next one, IEEE division, no fused
+ *      multiply-add -- so the results equal sklearn's bit for bit:
+ *          fwd, impute                : x = isnan(x) ? (float)fill[j] : x
+ *          fwd, DLWP_SCALE_STANDARD   : t = (float)((double)x - shift[j]);  y = (float)((double)t / scale[j])
+ *          fwd, DLWP_SCALE_MINMAX     : t = (float)((double)x * scale[j]);  y = (float)((double)t + shift[j])
+ *          inv, DLWP_SCALE_STANDARD   : t = (float)((double)x * scale[j]);  y = (float)((double)t + shift[j])
+ *          inv, DLWP_SCALE_MINMAX     : t = (float)((double)x - shift[j]);  y = (float)((double)t / scale[j])
+ *      y may alias x.  float4 accesses where f % 4 == 0 and x, y are 16-byte aligned, element accesses otherwise (any float
+ *      alignment).  Inference only: never part of a recorded training step.                                                  */
+#define DLWP_SCALE_STANDARD 0
+#define DLWP_SCALE_MINMAX   1
+typedef struct {
+  int n, f;                       /* samples, features per sample                                          */
+  int kind;                       /* DLWP_SCALE_*                                                          */
+} dlwp_scale;
+int dlwp_scale_fwd(dlwp_handle_t, const void* x, void* y, const void* fill, const void* shift, const void* scale, dlwp_scale d,
+                   void* stream);
+int dlwp_scale_inv(dlwp_handle_t, const void* x, void* y, const void* shift, const void* scale, dlwp_scale d, void* stream);
+
 /* ---- rollout: the N-step predict_timeseries loop (DLWP/model/models.py:277-293, 439-447) captured as ONE hipGraph.
  *      A plan is an array of dlwp_op describing one model call; buffer index >= 0 = caller scratch buffer,
  *      DLWP_BUF_STATE_IN = the call's input state, DLWP_BUF_OUT(o) = output o of the call.  Call t reads
@@ -629,6 +654,10 @@ int dlwp_dropout_bwd(dlwp_handle_t, const void* dy, void* dx, long long n, dlwp_
                                    * aux[0] / aux[1] = moving mean / variance buffer, aux[2] = the bits of epsilon (float).
                                    * The moving statistics are read at every launch: a graph never holds stale ones.      */
 #define DLWP_OP_DENSE     10      /* dlwp_dense_fwd: src, dst, w, b (| -1); xs = (n, k, 1, 1), conv.cout = units, conv.act       */
+#define DLWP_OP_SCALE     11      /* dlwp_scale_fwd / dlwp_scale_inv: src, dst (may be the same buffer), xs = (n, c, h, w) with
+                                   * f = c h w; w / b = shift / scale buffer | -1, aux[0] = fill buffer | -1000, aux[1] =
+                                   * DLWP_SCALE_*, aux[2] = 0 forward | 1 inverse (no fill).  float64 parameter buffers, read
+                                   * at every launch: a graph never holds a refitted scaler's old values.                  */
 typedef struct {
   int kind;                 /* DLWP_OP_*                                                                */
   int src, dst;             /* buffer indices                                                              */
