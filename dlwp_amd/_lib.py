@@ -225,6 +225,10 @@ _sig('dlwp_copy_many', [_vp, _vp, _vp, _vp, _i, _vp])
 _sig('dlwp_adam_keras_dev', [_vp, _vp, _vp, _vp, _vp, _sz] + [ctypes.c_float] * 5 + [_vp, _vp, ctypes.c_float, _vp])
 _sig('dlwp_sgd_keras', [_vp, _vp, _vp, _vp, _sz] + [ctypes.c_float] * 3 + [ctypes.c_longlong, ctypes.c_float, _vp])
 _sig('dlwp_axpby', [_vp, _vp, _vp, _sz, ctypes.c_float, ctypes.c_float, _vp])
+_sig('dlwp_grad_clip_factor_workspace', [_vp], _sz)
+_sig('dlwp_grad_clip_factor', [_vp, _vp, _sz, ctypes.c_float, ctypes.c_float, _vp, _sz, _vp, _vp])
+_sig('dlwp_optimizer_step', [_vp, _i, _vp, _vp, _vp, _vp, _vp, _sz] + [ctypes.c_float] * 6 +
+     [ctypes.c_double, ctypes.c_longlong, ctypes.c_float, ctypes.c_float, _vp, _vp])
 _sig('dlwp_prepare_begin', [_vp])
 _sig('dlwp_prepare_flush', [_vp, _vp])
 _sig('dlwp_reductions_begin', [_vp])

@@ -54,7 +54,9 @@ def install(force=False):
     keras.metrics = _module('keras.metrics', **losses)
     keras.regularizers = _module('keras.regularizers', l2=regularizers.l2, l1_l2=regularizers.l1_l2,
                                  L1L2=regularizers.L1L2)
-    keras.optimizers = _module('keras.optimizers', Adam=training.Adam, SGD=training.SGD)
+    keras.optimizers = _module('keras.optimizers', Optimizer=training.Optimizer, SGD=training.SGD, RMSprop=training.RMSprop,
+                               Adagrad=training.Adagrad, Adadelta=training.Adadelta, Adam=training.Adam, Adamax=training.Adamax,
+                               Nadam=training.Nadam, get=training.get_optimizer)
     dlwp = _module('DLWP')
     dlwp.custom = _module('DLWP.custom', **{k: v for k, v in vars(custom).items() if not k.startswith('_')})
     dlwp.util = _module('DLWP.util', **{k: v for k, v in vars(util).items() if not k.startswith('_')})

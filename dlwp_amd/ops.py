@@ -998,6 +998,47 @@ def sgd_keras(p, vel, g, iteration, lr=0.01, momentum=0.0, decay=0.0, grad_scale
                                        int(iteration), grad_scale, _stream(p)))
 
 
+#: dlwp_optimizer_step kinds (include/dlwp_hip.h: DLWP_OPT_*) and the slot arrays each takes
+OPT_SGD, OPT_SGD_NESTEROV, OPT_RMSPROP, OPT_ADAGRAD, OPT_ADADELTA, OPT_ADAM, OPT_ADAM_AMSGRAD, OPT_ADAMAX, OPT_NADAM = range(9)
+OPT_SLOTS = (1, 1, 1, 1, 2, 2, 3, 2, 2)
+
+
+def grad_clip_factor(g, clipnorm, grad_scale=1.0, out=None, ws_key=None):
+    """out (3 device floats) <- {factor, norm, norm^2} of the gradient g * grad_scale: factor = clipnorm / norm where norm >=
+    clipnorm, else exactly 1 (Keras' clip_norm).  A fixed double-precision tree: the same input gives the same bits.  Nothing
+    comes back to the host: optimizer_step reads the factor from `out`."""
+    _check_f32(g, out)
+    if out is None:
+        out = torch.empty(3, dtype=torch.float32, device=g.device)
+    if out.numel() < 3:
+        raise ValueError('grad_clip_factor: 3 output floats, please')
+    h = _lib.handle(_dev(out))
+    ws = workspace2(out.device, _lib.lib.dlwp_grad_clip_factor_workspace(h), ('clip', ws_key))
+    _lib.check(_lib.lib.dlwp_grad_clip_factor(h, _ptr(g) if g.numel() else None, g.numel(), float(grad_scale), float(clipnorm),
+                                              _ptr(ws), ws.numel(), _ptr(out), _stream(out)))
+    return out
+
+
+def optimizer_step(kind, p, slots, g, iteration, lr, decay=0.0, h1=0.0, h2=0.0, epsilon=1e-7, schedule_decay=0.0,
+                   m_schedule=1.0, grad_scale=1.0, clipvalue=0.0, factor=None):
+    """One update of kind OPT_* (dlwp_optimizer_step: the formulas are in include/dlwp_hip.h) in one launch.  slots: OPT_SLOTS[kind]
+    tensors like p; factor: the device tensor grad_clip_factor filled, or None."""
+    kind = int(kind)
+    slots = tuple(slots)
+    if not 0 <= kind < len(OPT_SLOTS) or len(slots) != OPT_SLOTS[kind]:
+        raise ValueError('optimizer_step: kind %r takes %s slot arrays, %d given'
+                         % (kind, OPT_SLOTS[kind] if 0 <= kind < len(OPT_SLOTS) else 'no', len(slots)))
+    _check_f32(p, g, factor, *slots)
+    if any(t.numel() != p.numel() for t in slots + (g,)):
+        raise ValueError('optimizer_step: parameters, slots and gradient must have the same number of elements')
+    if p.numel() == 0:
+        return
+    s = [_ptr(t) for t in slots] + [None] * (3 - len(slots))
+    _lib.check(_lib.lib.dlwp_optimizer_step(_lib.handle(_dev(p)), kind, _ptr(p), s[0], s[1], s[2], _ptr(g), p.numel(), lr, decay,
+                                            h1, h2, epsilon, schedule_decay, float(m_schedule), int(iteration), grad_scale,
+                                            clipvalue, _ptr(factor) if factor is not None else None, _stream(p)))
+
+
 def copy_many(pairs):
     """[(src, dst), ...] (at most 8 contiguous float32 tensors of equal element counts per pair) copied by ONE launch."""
     pairs = list(pairs)

@@ -312,9 +312,8 @@ def export_keras_hdf5(model, path):
             g.create_dataset('%s/%s:0' % (lay.name, nm), np.ascontiguousarray(a, dtype=np.float32))
     if model.optimizer is not None:
         opt = model.optimizer
-        ocfg = {k: v for k, v in vars(opt).items() if isinstance(v, (int, float)) and k != 'iterations'}
-        if type(opt).__name__ == 'Adam':
-            ocfg['amsgrad'] = False
+        # (Keras' get_config: the constructor arguments; iterations and Nadam's m_schedule are state, not configuration)
+        ocfg = {k: v for k, v in vars(opt).items() if isinstance(v, (int, float)) and k not in ('iterations', 'm_schedule')}
         loss = model.loss
         tc = {'optimizer_config': {'class_name': type(opt).__name__, 'config': ocfg},
               'loss': loss if isinstance(loss, (str, dict, list)) else getattr(loss, '__name__', 'loss'),
@@ -328,8 +327,9 @@ def export_keras_hdf5(model, path):
                 priv.create_dataset('loss_mean', np.asarray(loss.mean, dtype=np.float32))
             if loss.row_weights is not None:
                 priv.create_dataset('loss_row_weights', np.asarray(loss.row_weights, dtype=np.float32))
-        # optimizer state in Keras' order -- Adam: iterations, the first moments of every weight, the second moments, one
-        # (1,)-shaped placeholder per weight (amsgrad off: keras.optimizers.Adam keeps K.zeros(1) there); SGD: iterations, moments
+        # optimizer state in Keras' order -- iterations, then slot after slot (training.Optimizer.n_slots, Keras' weight order) the
+        # arrays of every weight.  Adam: first moments, second moments, then vhat -- with amsgrad off one (1,)-shaped placeholder per
+        # weight (keras.optimizers.Adam keeps K.zeros(1) there)
         tr = getattr(model, '_trainer', None)
         if tr is not None and tr.opt_state is not None:
             ow = root.create_group('optimizer_weights')
@@ -342,7 +342,7 @@ def export_keras_hdf5(model, path):
                     names.append('training/%s/Variable%s:0' % (oname, '' if k == 0 else '_%d' % k))
                     arrays.append(np.ascontiguousarray(slot[off:off + numel].reshape(shape), dtype=np.float32))
                     k += 1
-            if oname == 'Adam':
+            if oname == 'Adam' and not opt.amsgrad:
                 for _ in tr.entries:
                     names.append('training/%s/Variable_%d:0' % (oname, k))
                     arrays.append(np.zeros((1,), dtype=np.float32))
@@ -537,17 +537,16 @@ def import_keras_hdf5(path, custom_objects=None, device=None, compile=True, pack
         if ocls is not None and known:
             ocfg = {k: v for k, v in oc.get('config', {}).items() if isinstance(v, (int, float))}
             metrics = _resolve_metrics(tc.get('metrics'), custom_objects, package_objects)
-            ocfg.pop('amsgrad', None)
             model.compile(optimizer=ocls(**ocfg), loss=loss, metrics=metrics, loss_weights=tc.get('loss_weights'))
             if 'optimizer_weights' in f:
-                # keras.engine.saving.load_model: optimizer.set_weights(values in the order of weight_names) -- Adam: iterations,
-                # first moments, second moments (+ one placeholder per weight); SGD: iterations, moments
+                # keras.engine.saving.load_model: optimizer.set_weights(values in the order of weight_names) -- iterations, then
+                # n_slots() arrays per weight, slot after slot (Adam without amsgrad: + one placeholder per weight, not read)
                 import torch
                 ow = f['optimizer_weights']
                 vals = [np.asarray(ow[n][...]) for n in attr_list(ow, 'weight_names')]
                 tr = model._trainer
                 n_par = len(tr.entries)
-                n_slots = 2 if oc.get('class_name') == 'Adam' else 1
+                n_slots = model.optimizer.n_slots()
                 shapes = [tuple(e[4]) for e in tr.entries]
                 ok = len(vals) >= 1 + n_slots * n_par and all(
                     tuple(vals[1 + sl * n_par + i].shape) == shapes[i] for sl in range(n_slots) for i in range(n_par))
@@ -614,8 +613,11 @@ def load_model_file(path, custom_objects=None, device=None, package_objects=None
         ocls = getattr(training, comp['optimizer']['class'])
         ocfg = dict(comp['optimizer']['config'])
         iters = int(ocfg.pop('iterations', 0))
+        m_schedule = ocfg.pop('m_schedule', None)
         opt = ocls(**ocfg)
         opt.iterations = iters
+        if m_schedule is not None:
+            opt.m_schedule = float(m_schedule)
         loss = comp['loss']
         if isinstance(loss, dict):
             sp = loss['spec']
@@ -634,4 +636,6 @@ def load_model_file(path, custom_objects=None, device=None, package_objects=None
                                  for a in slots)
         elif iters:
             opt.iterations = 0      # a file without the moments: restart the bias correction with them (m = v = 0)
+            if m_schedule is not None:
+                opt.m_schedule = 1.0
     return model

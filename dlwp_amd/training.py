@@ -26,38 +26,202 @@ from .custom import Callback, History
 # ------------------------------------------------------------------------------------------------------------------ #
 
 class Optimizer(object):
-    def __init__(self, lr, decay):
+    """keras.optimizers.Optimizer: `clipnorm` / `clipvalue` are the only keywords beyond a class's own (Keras raises TypeError for
+    any other, and so does this); like Keras the two attributes exist only where they were passed.  The update is
+    dlwp_optimizer_step of kind `step_kind()` on `n_slots()` flat slot buffers, in Keras' weight order (include/dlwp_hip.h)."""
+
+    def __init__(self, lr, decay, **kwargs):
+        for k in kwargs:
+            if k not in ('clipnorm', 'clipvalue'):
+                raise TypeError('Unexpected keyword argument passed to optimizer: ' + str(k))
         self.lr, self.decay = float(lr), float(decay)
         self.iterations = 0
+        for k, v in kwargs.items():
+            if v is not None:
+                setattr(self, k, float(v))
+
+    def clips(self):
+        """(clipnorm, clipvalue), 0 where Keras would not clip"""
+        cn, cv = float(getattr(self, 'clipnorm', 0.0)), float(getattr(self, 'clipvalue', 0.0))
+        return (cn if cn > 0 else 0.0), (cv if cv > 0 else 0.0)
+
+    def legacy_kernel(self):
+        """True: the update is dlwp_adam_keras / dlwp_sgd_keras, as before the other optimizers existed"""
+        return False
+
+    def n_slots(self):
+        from . import ops
+        return ops.OPT_SLOTS[self.step_kind()]
+
+    def step_depends_on_iteration(self):
+        """does a launch argument of the update change from step to step (such a step is never replayed)?"""
+        return self.decay != 0.0
+
+    def step_args(self):
+        """keyword arguments of ops.optimizer_step beyond kind, buffers, iteration, grad_scale and clipping"""
+        raise NotImplementedError
+
+    def after_step(self):
+        self.iterations += 1
 
 
 class Adam(Optimizer):
     """keras.optimizers.Adam (Keras 2.2 form: epsilon outside the sqrt, bias correction folded into lr_t)."""
 
     def __init__(self, lr=0.001, beta_1=0.9, beta_2=0.999, epsilon=None, decay=0., amsgrad=False, **kwargs):
-        super(Adam, self).__init__(lr, decay)
-        if amsgrad:
-            raise NotImplementedError('amsgrad is not implemented')
+        super(Adam, self).__init__(lr, decay, **kwargs)
         self.beta_1, self.beta_2 = float(beta_1), float(beta_2)
         self.epsilon = 1e-7 if epsilon is None else float(epsilon)      # K.epsilon()
+        self.amsgrad = bool(amsgrad)
+
+    def legacy_kernel(self):
+        return not self.amsgrad and self.clips() == (0.0, 0.0)
+
+    def step_kind(self):
+        from . import ops
+        return ops.OPT_ADAM_AMSGRAD if self.amsgrad else ops.OPT_ADAM
+
+    def step_depends_on_iteration(self):
+        return True      # lr_t
+
+    def step_args(self):
+        return dict(lr=self.lr, decay=self.decay, h1=self.beta_1, h2=self.beta_2, epsilon=self.epsilon)
 
 
 class SGD(Optimizer):
     def __init__(self, lr=0.01, momentum=0., decay=0., nesterov=False, **kwargs):
-        super(SGD, self).__init__(lr, decay)
-        if nesterov:
-            raise NotImplementedError('nesterov momentum is not implemented')
+        super(SGD, self).__init__(lr, decay, **kwargs)
         self.momentum = float(momentum)
+        self.nesterov = bool(nesterov)
+
+    def legacy_kernel(self):
+        return not self.nesterov and self.clips() == (0.0, 0.0)
+
+    def step_kind(self):
+        from . import ops
+        return ops.OPT_SGD_NESTEROV if self.nesterov else ops.OPT_SGD
+
+    def step_args(self):
+        return dict(lr=self.lr, decay=self.decay, h1=self.momentum)
+
+
+class RMSprop(Optimizer):
+    """keras.optimizers.RMSprop: a <- rho a + (1 - rho) g^2; p -= lr' g / (sqrt(a) + eps)"""
+
+    def __init__(self, lr=0.001, rho=0.9, epsilon=None, decay=0., **kwargs):
+        super(RMSprop, self).__init__(lr, decay, **kwargs)
+        self.rho = float(rho)
+        self.epsilon = 1e-7 if epsilon is None else float(epsilon)
+
+    def step_kind(self):
+        from . import ops
+        return ops.OPT_RMSPROP
+
+    def step_args(self):
+        return dict(lr=self.lr, decay=self.decay, h1=self.rho, epsilon=self.epsilon)
+
+
+class Adagrad(Optimizer):
+    """keras.optimizers.Adagrad: a <- a + g^2; p -= lr' g / (sqrt(a) + eps)"""
+
+    def __init__(self, lr=0.01, epsilon=None, decay=0., **kwargs):
+        super(Adagrad, self).__init__(lr, decay, **kwargs)
+        self.epsilon = 1e-7 if epsilon is None else float(epsilon)
+
+    def step_kind(self):
+        from . import ops
+        return ops.OPT_ADAGRAD
+
+    def step_args(self):
+        return dict(lr=self.lr, decay=self.decay, epsilon=self.epsilon)
+
+
+class Adadelta(Optimizer):
+    """keras.optimizers.Adadelta: slots a (squared gradients), d (squared updates)"""
+
+    def __init__(self, lr=1.0, rho=0.95, epsilon=None, decay=0., **kwargs):
+        super(Adadelta, self).__init__(lr, decay, **kwargs)
+        self.rho = float(rho)
+        self.epsilon = 1e-7 if epsilon is None else float(epsilon)
+
+    def step_kind(self):
+        from . import ops
+        return ops.OPT_ADADELTA
+
+    def step_args(self):
+        return dict(lr=self.lr, decay=self.decay, h1=self.rho, epsilon=self.epsilon)
+
+
+class Adamax(Optimizer):
+    """keras.optimizers.Adamax: slots m, u (the exponentially weighted infinity norm)"""
+
+    def __init__(self, lr=0.002, beta_1=0.9, beta_2=0.999, epsilon=None, decay=0., **kwargs):
+        super(Adamax, self).__init__(lr, decay, **kwargs)
+        self.beta_1, self.beta_2 = float(beta_1), float(beta_2)
+        self.epsilon = 1e-7 if epsilon is None else float(epsilon)
+
+    def step_kind(self):
+        from . import ops
+        return ops.OPT_ADAMAX
+
+    def step_depends_on_iteration(self):
+        return True
+
+    def step_args(self):
+        return dict(lr=self.lr, decay=self.decay, h1=self.beta_1, h2=self.beta_2, epsilon=self.epsilon)
+
+
+def nadam_schedule(beta_1, schedule_decay, iteration, m_schedule):
+    """(mu_t, mu_{t+1}, ms_new, ms_next) of Keras' Nadam before step `iteration` -- double arithmetic on the float32-rounded
+    hyper-parameters, the same expressions dlwp_optimizer_step evaluates"""
+    import math
+    b1, sd = float(np.float32(beta_1)), float(np.float32(schedule_decay))
+    t = float(iteration) + 1.0
+    mu_t = b1 * (1.0 - 0.5 * math.pow(0.96, t * sd))
+    mu_t1 = b1 * (1.0 - 0.5 * math.pow(0.96, (t + 1.0) * sd))
+    ms_new = float(m_schedule) * mu_t
+    return mu_t, mu_t1, ms_new, ms_new * mu_t1
+
+
+class Nadam(Optimizer):
+    """keras.optimizers.Nadam: slots m, v; `m_schedule` (the running product of the momentum schedule, 1 before the first step) is a
+    host scalar that the npz archive keeps and a Keras HDF5 file does not (Keras re-starts it at 1 too)."""
+
+    def __init__(self, lr=0.002, beta_1=0.9, beta_2=0.999, epsilon=None, schedule_decay=0.004, **kwargs):
+        super(Nadam, self).__init__(lr, 0.0, **kwargs)
+        del self.decay                     # (Keras' Nadam has none)
+        self.beta_1, self.beta_2 = float(beta_1), float(beta_2)
+        self.epsilon = 1e-7 if epsilon is None else float(epsilon)
+        self.schedule_decay = float(schedule_decay)
+        self.m_schedule = 1.0
+
+    def step_kind(self):
+        from . import ops
+        return ops.OPT_NADAM
+
+    def step_depends_on_iteration(self):
+        return True
+
+    def step_args(self):
+        return dict(lr=self.lr, h1=self.beta_1, h2=self.beta_2, epsilon=self.epsilon, schedule_decay=self.schedule_decay,
+                    m_schedule=self.m_schedule)
+
+    def after_step(self):
+        self.m_schedule = nadam_schedule(self.beta_1, self.schedule_decay, self.iterations, self.m_schedule)[2]
+        self.iterations += 1
+
+
+_OPTIMIZERS = {'sgd': SGD, 'rmsprop': RMSprop, 'adagrad': Adagrad, 'adadelta': Adadelta, 'adam': Adam, 'adamax': Adamax,
+               'nadam': Nadam}
 
 
 def get_optimizer(spec):
     if isinstance(spec, Optimizer):
         return spec
     if isinstance(spec, str):
-        table = {'adam': Adam, 'sgd': SGD}
-        if spec.lower() not in table:
-            raise NotImplementedError("optimizer %r is not implemented ('adam', 'sgd' are)" % spec)
-        return table[spec.lower()]()
+        if spec.lower() not in _OPTIMIZERS:
+            raise ValueError('Could not interpret optimizer identifier: %r (%s are known)' % (spec, ', '.join(sorted(_OPTIMIZERS))))
+        return _OPTIMIZERS[spec.lower()]()
     raise TypeError('optimizer must be a name or a dlwp_amd.training.Optimizer instance')
 
 
@@ -242,6 +406,7 @@ class Trainer(object):
         self._graph_seen = {}
         self._iter_dev = None         # Adam's step number on the device (advanced inside the captured step)
         self._iter_shadow = None
+        self._clip_out = None         # {factor, norm, norm^2} of the clipnorm pass, on the device (see _optimizer_step)
         self._fold = None             # see _fold_ok
         self._prep_cache = {}         # batch size -> prepared weights of the step (see _prepare_step)
         self._side = None             # second stream: the weight gradients run beside the data-gradient chain
@@ -671,10 +836,7 @@ class Trainer(object):
     def _ensure_opt_state(self):
         opt = self.model.optimizer
         if self.opt_state is None:
-            if isinstance(opt, Adam):
-                self.opt_state = (torch.zeros_like(self.flat_params), torch.zeros_like(self.flat_params))
-            else:
-                self.opt_state = (torch.zeros_like(self.flat_params),)
+            self.opt_state = tuple(torch.zeros_like(self.flat_params) for _ in range(opt.n_slots()))
 
     def _exchange_and_apply(self, dp):
         """The data-parallel half of a step: the flat gradient buffer (loss table in its tail) summed over the ranks, then the
@@ -683,7 +845,7 @@ class Trainer(object):
         opt = self.model.optimizer
         if dp.wants_oneshot(self._flat_exchange):
             self._ensure_opt_state()
-            if isinstance(opt, Adam):
+            if isinstance(opt, Adam) and opt.legacy_kernel():
                 m, v = self.opt_state
                 dp.oneshot_adam_(self._flat_exchange, self.flat_params.numel(), self.flat_params, m, v, opt.lr, opt.beta_1,
                                  opt.beta_2, opt.epsilon, opt.decay, opt.iterations, 1.0 / dp.world)
@@ -698,14 +860,30 @@ class Trainer(object):
         from . import ops
         opt = self.model.optimizer
         self._ensure_opt_state()
-        if isinstance(opt, Adam):
+        if not opt.legacy_kernel():
+            self._optimizer_step(grad_scale)
+        elif isinstance(opt, Adam):
             m, v = self.opt_state
             ops.adam_keras(self.flat_params, m, v, self.flat_grads, opt.iterations, opt.lr, opt.beta_1, opt.beta_2,
                            opt.epsilon, opt.decay, grad_scale)
         else:
             ops.sgd_keras(self.flat_params, self.opt_state[0], self.flat_grads, opt.iterations, opt.lr, opt.momentum,
                           opt.decay, grad_scale)
-        opt.iterations += 1
+        opt.after_step()
+
+    def _optimizer_step(self, grad_scale):
+        """dlwp_optimizer_step on the flat buffers, behind the clipnorm pass where the optimizer has one: the factor (and the norm,
+        never read back) stays on the device in self._clip_out."""
+        from . import ops
+        opt = self.model.optimizer
+        clipnorm, clipvalue = opt.clips()
+        factor = None
+        if clipnorm > 0:
+            if self._clip_out is None:
+                self._clip_out = torch.zeros(3, dtype=torch.float32, device=self.device)
+            factor = ops.grad_clip_factor(self.flat_grads, clipnorm, grad_scale, out=self._clip_out, ws_key=id(self))
+        ops.optimizer_step(opt.step_kind(), self.flat_params, self.opt_state, self.flat_grads, opt.iterations,
+                           grad_scale=grad_scale, clipvalue=clipvalue, factor=factor, **opt.step_args())
 
     # -- public steps -------------------------------------------------------------------------------------------------- #
     def _host_rows(self, a, lo, hi):
@@ -750,14 +928,21 @@ class Trainer(object):
         grid points) as 'graph', larger ones as 'lanes' (their weight gradients gain from the side streams: batch 64 1.78 ->
         1.68 ms in r3).  DLWP_TRAIN_STEP=graph|lanes|branches|torch picks the form.  Never replayed: kernel regularisers (their
         penalty is read back to the host every step), SGD with decay (its rate is a launch argument), models with Dropout layers
-        (the step number that keys their masks is a launch argument), steps on the CPU device."""
+        (the step number that keys their masks is a launch argument), steps on the CPU device.  Of the optimizers behind
+        dlwp_optimizer_step, those whose launch arguments do not change with the step number replay -- RMSprop, Adagrad, Adadelta
+        and SGD (nesterov or clipped) with decay == 0, clipped or not: the clipnorm factor lives on the device.  Adamax, Nadam,
+        amsgrad or clipped Adam and anything with decay > 0 carry step-dependent scalars as launch arguments and stay eager (no
+        device-side step counter for them yet), as SGD with decay does."""
         opt = self.model.optimizer
         mode = os.environ.get('DLWP_TRAIN_GRAPH', 'auto')
         if self.device.type != 'cuda' or mode == '0' or n_local is None:
             return False
         if any(True for _ in self._regularized()) or self.plan.dropout_layers:
             return False
-        if not (isinstance(opt, Adam) or (isinstance(opt, SGD) and opt.decay == 0.0)):
+        if opt.legacy_kernel():
+            if not (isinstance(opt, Adam) or opt.decay == 0.0):
+                return False
+        elif opt.step_depends_on_iteration():
             return False
         form = os.environ.get('DLWP_TRAIN_STEP')
         if form not in (None, '', 'graph', 'lanes', 'branches', 'torch'):
@@ -777,6 +962,8 @@ class Trainer(object):
         opt = self.model.optimizer
         if dp is not None:
             ops.axpby(loss_vals.view(-1), self._loss_tail.view(-1), scale, 0.0)
+        elif not opt.legacy_kernel():
+            self._optimizer_step(1.0)
         elif isinstance(opt, Adam):
             m, v = self.opt_state
             ops.adam_keras_dev(self.flat_params, m, v, self.flat_grads, self._iter_dev, self._lr_t, opt.lr, opt.beta_1,
@@ -939,7 +1126,8 @@ class Trainer(object):
         opt = self.model.optimizer
         # the captured launches carry the optimizer's hyper-parameters as arguments: a changed rate (scheduler, callback,
         # load_model) must not replay the old ones
-        hyper = tuple(float(getattr(opt, k)) for k in ('lr', 'decay', 'beta_1', 'beta_2', 'epsilon', 'momentum')
+        hyper = tuple((k, float(getattr(opt, k))) for k in ('lr', 'decay', 'beta_1', 'beta_2', 'epsilon', 'momentum', 'rho',
+                                                            'nesterov', 'amsgrad', 'schedule_decay', 'clipnorm', 'clipvalue')
                       if hasattr(opt, k))
         form = self._graph_ok(int(x.shape[0]))
         key = (int(x.shape[0]), int(n_global), 0 if dp is None else dp.world, hyper, 'torch' if form == 'torch' else 'tape')

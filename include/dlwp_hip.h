@@ -423,6 +423,45 @@ int    dlwp_adam_keras_dev(dlwp_handle_t, void* p, void* m, void* v, const void*
 int    dlwp_sgd_keras(dlwp_handle_t, void* p, void* vel, const void* g, size_t n, float lr, float momentum, float decay,
                       long long iteration, float grad_scale, void* stream);
 int    dlwp_axpby(dlwp_handle_t, const void* x, void* y, size_t n, float a, float b, void* stream);   /* y = a*x + b*y */
+/* ---- the other Keras 2.2.4 optimizers and Keras' gradient clipping (keras/optimizers.py; csrc/optimizers.hip): ONE update entry
+ *      with a kind code.  g' below is the gradient the update sees: g * grad_scale, times *factor_dev (nullable: the clipnorm factor
+ *      of dlwp_grad_clip_factor), clamped to [-clipvalue, clipvalue] when clipvalue > 0.  it = iteration (the count BEFORE the step),
+ *      t = it + 1, lr' = lr / (1 + decay it); step-dependent scalars are evaluated in double on the host and rounded once.
+ *        kind              slots        h1, h2        update
+ *        SGD               s0 = m       momentum      v = h1 m - lr' g'; m <- v; p += v
+ *        SGD_NESTEROV      s0 = m       momentum      v as above; m <- v; p += h1 v - lr' g'
+ *        RMSPROP           s0 = a       rho           a <- h1 a + (1 - h1) g'^2; p -= lr' g' / (sqrt(a) + eps)
+ *        ADAGRAD           s0 = a                     a <- a + g'^2; p -= lr' g' / (sqrt(a) + eps)
+ *        ADADELTA          s0 = a, s1 = d  rho        a as RMSPROP; upd = g' sqrt(d + eps) / sqrt(a + eps); p -= lr' upd;
+ *                                                     d <- h1 d + (1 - h1) upd^2
+ *        ADAM              s0 = m, s1 = v  b1, b2     dlwp_adam_keras on g'
+ *        ADAM_AMSGRAD      + s2 = vhat                vhat <- max(vhat, v); p -= lr_t m / (sqrt(vhat) + eps)
+ *        ADAMAX            s0 = m, s1 = u  b1, b2     lr_t = lr' / (1 - b1^t); m as Adam; u <- max(b2 u, |g'|); p -= lr_t m / (u + eps)
+ *        NADAM             s0 = m, s1 = v  b1, b2     mu_t = b1 (1 - 0.5 0.96^(t sd)), mu_t1 the same at t + 1 (sd = schedule_decay);
+ *                                                     ms_new = m_schedule mu_t, ms_next = ms_new mu_t1 (the CALLER keeps m_schedule:
+ *                                                     1 before the first step, ms_new after each); m, v as Adam;
+ *                                                     p -= lr ((1 - mu_t) g' / (1 - ms_new) + mu_t1 m / (1 - ms_next))
+ *                                                             / (sqrt(v / (1 - b2^t)) + eps);   decay is not used
+ *      Unused slot pointers may be null.  One launch; arrays may start at any element of a larger buffer (16-byte accesses where all
+ *      of them share their offset inside a 16-byte unit); nothing outside [0, n) is written and g is only read.
+ *      dlwp_grad_clip_factor: factor_dev (device, 3 floats) <- {factor, norm, norm^2}, norm = sqrt(sum (g_i grad_scale)^2), factor =
+ *      clipnorm / norm where norm >= clipnorm > 0, else exactly 1.  Double-precision fixed tree, no atomics: bit-reproducible.
+ *      ws >= dlwp_grad_clip_factor_workspace() bytes, 8-byte aligned.                                                          */
+#define DLWP_OPT_SGD           0
+#define DLWP_OPT_SGD_NESTEROV  1
+#define DLWP_OPT_RMSPROP       2
+#define DLWP_OPT_ADAGRAD       3
+#define DLWP_OPT_ADADELTA      4
+#define DLWP_OPT_ADAM          5
+#define DLWP_OPT_ADAM_AMSGRAD  6
+#define DLWP_OPT_ADAMAX        7
+#define DLWP_OPT_NADAM         8
+size_t dlwp_grad_clip_factor_workspace(dlwp_handle_t);
+int    dlwp_grad_clip_factor(dlwp_handle_t, const void* g, size_t n, float grad_scale, float clipnorm, void* ws, size_t ws_bytes,
+                             float* factor_dev, void* stream);
+int    dlwp_optimizer_step(dlwp_handle_t, int kind, void* p, void* s0, void* s1, void* s2, const void* g, size_t n, float lr,
+                           float decay, float h1, float h2, float epsilon, float schedule_decay, double m_schedule,
+                           long long iteration, float grad_scale, float clipvalue, const float* factor_dev, void* stream);
 /* count <= 8 contiguous float32 copies dsts[i] <- srcs[i] (floats[i] elements each) in ONE launch: the batch and its targets
  * on their way into the fixed buffers a captured training step reads (a device-to-device memcpy each before: ~5 us apiece). */
 int    dlwp_copy_many(dlwp_handle_t, const void* const* srcs, void* const* dsts, const size_t* floats, int count, void* stream);
