@@ -34,6 +34,10 @@ OP_ROWCONV2D = 8
 OP_BATCHNORM = 9
 OP_DENSE = 10
 OP_SCALE = 11
+OP_ACTIVATION = 12
+OP_MERGE = 13
+ELT_RELU, ELT_ELU, ELT_SELU, ELT_SIGMOID, ELT_HARD_SIGMOID, ELT_SOFTPLUS, ELT_SOFTSIGN, ELT_TANH = 0, 1, 2, 3, 4, 5, 6, 7   # dlwp_activation kinds
+MERGE_ADD, MERGE_SUBTRACT, MERGE_MULTIPLY, MERGE_AVERAGE, MERGE_MAXIMUM, MERGE_MINIMUM = 0, 1, 2, 3, 4, 5            # dlwp_merge kinds
 SCALE_STANDARD, SCALE_MINMAX = 0, 1                 # dlwp_scale kinds
 BUF_NONE = -1000
 STEP_LANES, STEP_GRAPH, STEP_GRAPH_BRANCHES, STEP_LANES_RECORDED = 0, 1, 2, 3
@@ -101,6 +105,16 @@ class Dropout(ctypes.Structure):
     """dlwp_dropout (include/dlwp_hip.h): what names one mask -- seed, layer, step -- and how it is applied"""
     _fields_ = [('seed', ctypes.c_ulonglong), ('layer', ctypes.c_uint), ('step', ctypes.c_uint), ('threshold', ctypes.c_uint),
                 ('scale', ctypes.c_float)]
+
+
+class Activation(ctypes.Structure):
+    """dlwp_activation (include/dlwp_hip.h): the kind of one activation launch and the relu family's / ELU's parameters"""
+    _fields_ = [('kind', ctypes.c_int), ('alpha', ctypes.c_float), ('max_value', ctypes.c_float), ('theta', ctypes.c_float)]
+
+
+class Merge(ctypes.Structure):
+    """dlwp_merge (include/dlwp_hip.h): the kind of one merge launch and how many of its four source arguments it reads"""
+    _fields_ = [('kind', ctypes.c_int), ('n_src', ctypes.c_int)]
 
 
 class Scale(ctypes.Structure):
@@ -260,6 +274,10 @@ _sig('dlwp_dense_bwd_data', [_vp] * 5 + [Dense, _vp])
 _sig('dlwp_dense_bwd_weight', [_vp] * 6 + [Dense, _vp])
 _sig('dlwp_dropout_fwd', [_vp, _vp, _vp, ctypes.c_longlong, Dropout, _vp])
 _sig('dlwp_dropout_bwd', [_vp, _vp, _vp, ctypes.c_longlong, Dropout, _vp])
+_sig('dlwp_activation_fwd', [_vp, _vp, _vp, ctypes.c_longlong, Activation, _vp])
+_sig('dlwp_activation_bwd', [_vp, _vp, _vp, _vp, ctypes.c_longlong, Activation, _vp])
+_sig('dlwp_merge_fwd', [_vp] * 6 + [ctypes.c_longlong, Merge, _vp])
+_sig('dlwp_merge_bwd', [_vp] * 10 + [ctypes.c_longlong, Merge, _vp])
 _sig('dlwp_scale_fwd', [_vp] * 6 + [Scale, _vp])
 _sig('dlwp_scale_inv', [_vp] * 5 + [Scale, _vp])
 _sig('dlwp_copy_channels', [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp])

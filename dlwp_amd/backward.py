@@ -486,6 +486,24 @@ class BackwardPass(object):
         if dx is not None:
             self.book.deposit(op.src, 0, c.src.shape[1], dx)
 
+    def _act(self, c):
+        """keras activation layers: dx = dy f'(x), f' from the layer's input, which the training plan keeps"""
+        if c.op.src == P.STATE_IN:
+            return
+        dx = ops.activation_bwd(c.src, c.gD, *c.op.layer.eltwise)
+        self.book.deposit(c.op.src, 0, c.src.shape[1], dx)
+
+    def _merge(self, c):
+        """keras merge layers: every source's gradient from one pass over the sources and dy.  Each source gets a NEW tensor, also
+        where the gradient is dy itself (Add): GradBook.deposit adopts a buffer's first gradient without a copy and later adds into it
+        in place, so a tensor handed to two sources would collect both sources' other gradients."""
+        op, book = c.op, self.book
+        srcs = [op.src] + list(op.aux)
+        dxs = ops.merge_bwd(op.layer.kind, [book.tensor(b) for b in srcs], c.gD, want=[b != P.STATE_IN for b in srcs])
+        for b, dx in zip(srcs, dxs):
+            if dx is not None:
+                book.deposit(b, 0, dx.shape[1], dx)
+
     def _lstm(self, c):
         op, gD, book = c.op, c.gD, self.book
         zh_i, cp_i, co_i = op.aux
@@ -538,4 +556,5 @@ class BackwardPass(object):
             self.book.deposit(c.op.src, 0, c.src.shape[1], ops.upsample2_bwd(c.gD))
 
     adjoints = {'d2s': _d2s, 'conv': _conv, 'rowconv': _rowconv, 'dense': _dense, 'dropout': _dropout, 'bn': _bn,
-                'lstm': _lstm, 'copy': _copy, 'pad': _pad, 'maxpool': _maxpool, 'upsample': _upsample}
+                'lstm': _lstm, 'copy': _copy, 'pad': _pad, 'maxpool': _maxpool, 'upsample': _upsample, 'act': _act,
+                'merge': _merge}

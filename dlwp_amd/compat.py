@@ -40,6 +40,12 @@ def install(force=False):
     keras = _module('keras')
     keras.layers = _module('keras.layers', **{k: v for k, v in vars(layers).items() if not k.startswith('_')})
     keras.layers.convolutional = _module('keras.layers.convolutional', ZeroPadding2D=layers.ZeroPadding2D)
+    keras.layers.advanced_activations = _module('keras.layers.advanced_activations', LeakyReLU=layers.LeakyReLU, ReLU=layers.ReLU,
+                                                ELU=layers.ELU, ThresholdedReLU=layers.ThresholdedReLU, PReLU=layers.PReLU,
+                                                Softmax=layers.Softmax)
+    keras.layers.merge = _module('keras.layers.merge', Concatenate=layers.Concatenate, concatenate=layers.concatenate,
+                                 **{k: getattr(layers, k) for k in ('Add', 'Subtract', 'Multiply', 'Average', 'Maximum', 'Minimum',
+                                                                    'add', 'subtract', 'multiply', 'average', 'maximum', 'minimum')})
     keras.models = _module('keras.models', Model=engine.Model, Sequential=engine.Sequential)
     keras.callbacks = _module('keras.callbacks', Callback=custom.Callback, History=custom.History,
                               EarlyStopping=custom.EarlyStopping)

@@ -75,6 +75,17 @@ int enqueue_op(dlwp_handle_t h, const dlwp_op& op, const void* src, void* dst, c
       if (op.aux[2]) return dlwp_scale_inv(h, src, dst, w, b, d, (void*)s);
       return dlwp_scale_fwd(h, src, dst, aux[0], w, b, d, (void*)s);
     }
+    case DLWP_OP_ACTIVATION: {  // keras activation layers: conv.act = DLWP_ELT_*, alpha / max_value / theta as bits in op.aux[0..2]
+      dlwp_activation d{op.conv.act, 0.f, 0.f, 0.f};
+      memcpy(&d.alpha, &op.aux[0], sizeof(float));
+      memcpy(&d.max_value, &op.aux[1], sizeof(float));
+      memcpy(&d.theta, &op.aux[2], sizeof(float));
+      return dlwp_activation_fwd(h, src, dst, (long long)op.xs.n * op.xs.c * op.xs.h * op.xs.w, d, (void*)s);
+    }
+    case DLWP_OP_MERGE: {       // keras merge layers: src and aux[0..2] = the sources (resolved by the caller; null = absent)
+      const dlwp_merge d{op.conv.act, 1 + (aux[0] != nullptr) + (aux[1] != nullptr) + (aux[2] != nullptr)};
+      return dlwp_merge_fwd(h, src, aux[0], aux[1], aux[2], dst, (long long)op.xs.n * op.xs.c * op.xs.h * op.xs.w, d, (void*)s);
+    }
     case DLWP_OP_COPYCH:
       return dlwp_copy_channels(h, src, dst, op.xs.n, op.xs.c, op.xs.h * op.xs.w, op.conv.in_c_off,
                                 op.conv.in_c_total, op.conv.out_c_off, op.conv.out_c_total, dtype, (void*)s);
@@ -208,6 +219,11 @@ static int create_impl(dlwp_handle_t h, const dlwp_op* plan_in, int n_ops, void*
                          (op.aux[0] == DLWP_BUF_NONE || (op.aux[0] >= 0 && op.aux[0] < n_buffers && op.aux[2] == 0)) &&
                          (op.aux[1] == DLWP_SCALE_STANDARD || op.aux[1] == DLWP_SCALE_MINMAX) && (op.aux[2] == 0 || op.aux[2] == 1),
                      "rollout op %d: scaler buffers, kind or direction out of range", i);
+    if (op.kind == DLWP_OP_MERGE)      // further sources: scratch buffers, the input state or earlier outputs; in front of any gap
+      for (int k = 0; k < 3; ++k)
+        DLWP_CHECK_ARG(op.aux[k] == DLWP_BUF_NONE ? k > 0 : (op.aux[k] >= DLWP_BUF_OUT(n_outputs - 1) && op.aux[k] < n_buffers &&
+                                                            (k == 0 || op.aux[k - 1] != DLWP_BUF_NONE)),
+                       "rollout op %d: merge source %d (buffer %d) out of range", i, k + 1, op.aux[k]);
     if (op.kind == DLWP_OP_LSTM_GATES)
       for (int k = 0; k < 3; ++k)
         DLWP_CHECK_ARG((k < 2 && op.aux[k] == DLWP_BUF_NONE) || (op.aux[k] >= 0 && op.aux[k] < n_buffers),
@@ -298,7 +314,7 @@ static int create_impl(dlwp_handle_t h, const dlwp_op* plan_in, int n_ops, void*
           aux[1] = buffers[op.aux[1]];
         }
         if (scale && op.aux[0] != DLWP_BUF_NONE) aux[0] = buffers[op.aux[0]];   // (float64 parameters: the same for every member group)
-        if (op.kind == DLWP_OP_LSTM_GATES)
+        if (op.kind == DLWP_OP_LSTM_GATES || op.kind == DLWP_OP_MERGE)
           for (int k = 0; k < 3; ++k) aux[k] = op.aux[k] == DLWP_BUF_NONE ? nullptr : resolve(op.aux[k], t, g);
         if (op.kind == DLWP_OP_CONV2D && op.conv.lstm_f > 0)
           for (int k = 0; k < 3; ++k) aux[k] = op.aux[k + 1] == DLWP_BUF_NONE ? nullptr : resolve(op.aux[k + 1], t, g);

@@ -160,7 +160,7 @@ class Executor(object):
         cells = {b for op in fused for b in op.aux[1:] if b is not None}
 
         def buffers_of(op):
-            extra = [b for b in (op.aux or ()) if isinstance(b, int)] if op.kind in ('conv', 'lstm') else []
+            extra = [b for b in (op.aux or ()) if isinstance(b, int)] if op.kind in ('conv', 'lstm', 'merge') else []
             return [op.src, op.dst] + extra
         cells_private = all((op.kind == 'conv' and op.lstm_f) or not (set(buffers_of(op)) & cells) for op in plan.ops)
 
@@ -330,6 +330,10 @@ class Executor(object):
                 else:
                     ops.batchnorm_fwd_infer(src, lay.gamma, lay.beta, lay.moving_mean, lay.moving_variance, lay.epsilon,
                                             out=dst)
+            elif op.kind == 'act':            # keras activation layers: whole flat buffers (csrc/eltwise.hip)
+                ops.activation_fwd(src, *op.layer.eltwise, out=dst)
+            elif op.kind == 'merge':          # keras merge layers: 2 to 4 whole flat buffers of one size
+                ops.merge_fwd(op.layer.kind, [src] + [res(b) for b in op.aux], out=dst)
             elif op.kind == 'scale':          # the wrapper's imputer + scaler in front, its inverse scaler behind (in place)
                 st = self.transform[op.role]
                 if op.role == 'head':
@@ -502,7 +506,8 @@ class Executor(object):
         kind = {'conv': _lib.OP_CONV2D, 'pad': _lib.OP_PAD2D, 'maxpool': _lib.OP_MAXPOOL2,
                 'upsample': _lib.OP_UPSAMPLE2, 'copy': _lib.OP_COPYCH, 'lstm': _lib.OP_LSTM_GATES,
                 'phasew': _lib.OP_PHASE_WEIGHTS, 'd2s': _lib.OP_DEPTH2SPACE, 'rowconv': _lib.OP_ROWCONV2D,
-                'bn': _lib.OP_BATCHNORM, 'dense': _lib.OP_DENSE, 'scale': _lib.OP_SCALE}
+                'bn': _lib.OP_BATCHNORM, 'dense': _lib.OP_DENSE, 'scale': _lib.OP_SCALE, 'act': _lib.OP_ACTIVATION,
+                'merge': _lib.OP_MERGE}
         arr = (_lib.Op * len(self.plan.ops))()
         for k, (op, d) in enumerate(zip(self.plan.ops, self._descriptors())):
             o = arr[k]
@@ -544,6 +549,15 @@ class Executor(object):
                 g_i, b_i, o.aux[0], o.aux[1] = bidx[id(op.layer)]
                 o.w, o.b = g_i, b_i
                 o.aux[2] = struct.unpack('<i', struct.pack('<f', op.layer.epsilon))[0]
+            elif op.kind == 'act':                     # the kind, and alpha / max_value / theta as float bits
+                d_act = ops.activation_desc(*op.layer.eltwise)
+                o.conv.act = d_act.kind
+                for j, v in enumerate((d_act.alpha, d_act.max_value, d_act.theta)):
+                    o.aux[j] = struct.unpack('<i', struct.pack('<f', v))[0]
+            elif op.kind == 'merge':                   # the other sources ride in aux
+                o.conv.act = ops.MERGE_KINDS[op.layer.kind]
+                for j in range(3):
+                    o.aux[j] = op.aux[j] if j < len(op.aux) else _lib.BUF_NONE
             elif op.kind == 'scale':                   # float64 parameters, read at every launch; the fill on the input side only
                 o.w, o.b, f_i = sidx[op.role]
                 o.aux[0] = f_i if (f_i >= 0 and op.role == 'head') else _lib.BUF_NONE
@@ -827,6 +841,10 @@ class Model(object):
         if dtype == 'bfloat16' and self.plan.dense_layers:
             raise NotImplementedError('bfloat16 activation storage of a model with Dense layers is not implemented (the dense '
                                       'kernels read and write float32)')
+        if dtype == 'bfloat16' and self.plan.eltwise_layers:
+            raise NotImplementedError('bfloat16 activation storage of a model with activation / merge layers (%s) is not '
+                                      'implemented (the element-wise kernels read and write float32)'
+                                      % ', '.join(lay.name for lay in self.plan.eltwise_layers))
         if dtype != self.activation_dtype:
             self.activation_dtype = dtype
             # interleaved phase stores (dlwp_conv2d.out_d2s) belong to the float32 Winograd kernels; with bfloat16 storage

@@ -813,3 +813,218 @@ class Concatenate(Layer):
 
 def concatenate(inputs, axis=-1, **kwargs):
     return Concatenate(axis=axis, **kwargs)(list(inputs))
+
+
+# ------------------------------------------------------------------------------------------------------------------ #
+# Activation layers (keras.layers.Activation, keras.layers.advanced_activations) and merge layers (keras.layers.merge):
+# element-wise, no weights, no state -- a layer object may be applied any number of times.  The closed forms are the
+# project's statement of Keras 2.2.x; the kernels are csrc/eltwise.hip.
+# ------------------------------------------------------------------------------------------------------------------ #
+
+#: what Activation(name) lowers to: 'relu' is the relu family at its defaults, 'linear' is a view
+ELTWISE_ACTIVATIONS = ('relu', 'elu', 'selu', 'sigmoid', 'hard_sigmoid', 'softplus', 'softsign', 'tanh')
+
+
+def _relu_family(who, alpha, max_value, theta):
+    """(alpha, max_value | None, theta) of y = x > theta ? min(x, max_value) : alpha (x - theta), validated"""
+    alpha, theta = float(alpha), float(theta)
+    max_value = None if max_value is None else float(max_value)
+    if not alpha >= 0.0 or math.isinf(alpha):
+        raise ValueError('%s: the negative slope must be a finite number >= 0, got %r' % (who, alpha))
+    if not theta >= 0.0 or math.isinf(theta):
+        if theta < 0.0:
+            raise NotImplementedError('%s: a negative threshold (%r) is not implemented' % (who, theta))
+        raise ValueError('%s: the threshold must be a finite number, got %r' % (who, theta))
+    if max_value is not None and not max_value > theta:
+        raise NotImplementedError('%s: max_value=%r at or below the threshold %r is not implemented' % (who, max_value, theta))
+    return alpha, max_value, theta
+
+
+class _ActivationLayer(Layer):
+    """An element-wise function of one tensor.  eltwise: None (the identity: a view, no launch) or (kind, alpha,
+    max_value | None, theta) with kind in ELTWISE_ACTIVATIONS -- what plan / engine / backward launch."""
+    eltwise = None
+
+    def compute_output_shape(self, input_shape):
+        if isinstance(input_shape, list):
+            raise ValueError('%s takes one input tensor, got a list of %d' % (self.name, len(input_shape)))
+        return tuple(input_shape)
+
+
+class Activation(_ActivationLayer):
+    """keras.layers.Activation(activation): 'linear' | 'relu' | 'elu' | 'selu' | 'sigmoid' | 'hard_sigmoid' | 'softplus' |
+    'softsign' | 'tanh', or a Keras activation function of one of those names.  'softmax' and 'exponential' are not implemented."""
+
+    def __init__(self, activation, **kwargs):
+        super(Activation, self).__init__(**kwargs)
+        if callable(activation):
+            activation = getattr(activation, '__name__', None)
+        if activation is None:
+            activation = 'linear'
+        if activation in ('softmax', 'exponential'):
+            raise NotImplementedError('Activation(%r) is not implemented' % (activation,))
+        if activation != 'linear' and activation not in ELTWISE_ACTIVATIONS:
+            raise ValueError('Activation: unknown activation function %r' % (activation,))
+        self.activation = activation
+        if activation == 'relu':
+            self.eltwise = ('relu', 0.0, None, 0.0)
+        elif activation == 'elu':
+            self.eltwise = ('elu', 1.0, None, 0.0)
+        elif activation != 'linear':
+            self.eltwise = (activation, 0.0, None, 0.0)
+
+    def get_config(self):
+        cfg = super(Activation, self).get_config()
+        cfg.update({'activation': self.activation})
+        return cfg
+
+
+class LeakyReLU(_ActivationLayer):
+    """keras.layers.LeakyReLU(alpha=0.3): x > 0 ? x : alpha x"""
+
+    def __init__(self, alpha=0.3, **kwargs):
+        super(LeakyReLU, self).__init__(**kwargs)
+        self.alpha = _relu_family('LeakyReLU', alpha, None, 0.0)[0]
+        self.eltwise = ('relu', self.alpha, None, 0.0)
+
+    def get_config(self):
+        cfg = super(LeakyReLU, self).get_config()
+        cfg.update({'alpha': self.alpha})
+        return cfg
+
+
+class ReLU(_ActivationLayer):
+    """keras.layers.ReLU(max_value=None, negative_slope=0., threshold=0.): x > threshold ? min(x, max_value) :
+    negative_slope (x - threshold).  ReLU(max_value=m, negative_slope=a) is the capped leaky ReLU."""
+
+    def __init__(self, max_value=None, negative_slope=0., threshold=0., **kwargs):
+        super(ReLU, self).__init__(**kwargs)
+        self.negative_slope, self.max_value, self.threshold = _relu_family('ReLU', negative_slope, max_value, threshold)
+        self.eltwise = ('relu', self.negative_slope, self.max_value, self.threshold)
+
+    def get_config(self):
+        cfg = super(ReLU, self).get_config()
+        cfg.update({'max_value': self.max_value, 'negative_slope': self.negative_slope, 'threshold': self.threshold})
+        return cfg
+
+
+class ELU(_ActivationLayer):
+    """keras.layers.ELU(alpha=1.0): x > 0 ? x : alpha (exp(x) - 1)"""
+
+    def __init__(self, alpha=1.0, **kwargs):
+        super(ELU, self).__init__(**kwargs)
+        self.alpha = float(alpha)
+        if math.isnan(self.alpha) or math.isinf(self.alpha):
+            raise ValueError('ELU: alpha must be a finite number, got %r' % (alpha,))
+        self.eltwise = ('elu', self.alpha, None, 0.0)
+
+    def get_config(self):
+        cfg = super(ELU, self).get_config()
+        cfg.update({'alpha': self.alpha})
+        return cfg
+
+
+class ThresholdedReLU(_ActivationLayer):
+    """keras.layers.ThresholdedReLU(theta=1.0): x > theta ? x : 0"""
+
+    def __init__(self, theta=1.0, **kwargs):
+        super(ThresholdedReLU, self).__init__(**kwargs)
+        self.theta = _relu_family('ThresholdedReLU', 0.0, None, theta)[2]
+        self.eltwise = ('relu', 0.0, None, self.theta)
+
+    def get_config(self):
+        cfg = super(ThresholdedReLU, self).get_config()
+        cfg.update({'theta': self.theta})
+        return cfg
+
+
+class PReLU(Layer):
+    """keras.layers.PReLU has a learned slope per element: not implemented."""
+
+    def __init__(self, *args, **kwargs):
+        raise NotImplementedError('PReLU (a learned negative slope) is not implemented; LeakyReLU(alpha) has a fixed one')
+
+
+class Softmax(Layer):
+    """keras.layers.Softmax normalises along an axis, it is not element-wise: not implemented."""
+
+    def __init__(self, *args, **kwargs):
+        raise NotImplementedError('Softmax is not implemented (the element-wise activations of keras.layers.Activation are)')
+
+
+MERGE_MAX_INPUTS = 4
+
+
+class _Merge(Layer):
+    """keras.layers.merge._Merge on inputs of identical shape: ((a o b) o c) o d, left to right in float32, 2 to 4 inputs."""
+    kind = None
+
+    def compute_output_shape(self, shapes):
+        if not isinstance(shapes, list) or len(shapes) < 2:
+            raise ValueError('A merge layer should be called on a list of at least 2 inputs (%s)' % self.name)
+        if len(shapes) > MERGE_MAX_INPUTS:
+            raise NotImplementedError('%s: %d inputs; merging more than %d is not implemented (nest two layers)'
+                                      % (self.name, len(shapes), MERGE_MAX_INPUTS))
+        for s in shapes[1:]:
+            if tuple(s) != tuple(shapes[0]):
+                raise ValueError('%s: inputs must have the same shape (no broadcasting), got %r' % (self.name, shapes))
+        return tuple(shapes[0])
+
+
+class Add(_Merge):
+    """keras.layers.Add"""
+    kind = 'add'
+
+
+class Subtract(_Merge):
+    """keras.layers.Subtract: exactly two inputs, a - b"""
+    kind = 'subtract'
+
+    def compute_output_shape(self, shapes):
+        if not isinstance(shapes, list) or len(shapes) != 2:
+            raise ValueError('A `Subtract` layer should be called on exactly 2 inputs')
+        return super(Subtract, self).compute_output_shape(shapes)
+
+
+class Multiply(_Merge):
+    """keras.layers.Multiply"""
+    kind = 'multiply'
+
+
+class Average(_Merge):
+    """keras.layers.Average: the left-to-right sum divided by float32(number of inputs)"""
+    kind = 'average'
+
+
+class Maximum(_Merge):
+    """keras.layers.Maximum (NaN propagates, as in np.maximum)"""
+    kind = 'maximum'
+
+
+class Minimum(_Merge):
+    """keras.layers.Minimum (NaN propagates, as in np.minimum)"""
+    kind = 'minimum'
+
+
+def add(inputs, **kwargs):
+    return Add(**kwargs)(list(inputs))
+
+
+def subtract(inputs, **kwargs):
+    return Subtract(**kwargs)(list(inputs))
+
+
+def multiply(inputs, **kwargs):
+    return Multiply(**kwargs)(list(inputs))
+
+
+def average(inputs, **kwargs):
+    return Average(**kwargs)(list(inputs))
+
+
+def maximum(inputs, **kwargs):
+    return Maximum(**kwargs)(list(inputs))
+
+
+def minimum(inputs, **kwargs):
+    return Minimum(**kwargs)(list(inputs))

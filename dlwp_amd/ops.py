@@ -1269,3 +1269,86 @@ def dropout_bwd(dy, rate, seed, layer, step, out=None):
     _lib.check(_lib.lib.dlwp_dropout_bwd(_lib.handle(_dev(dy)), _ptr(dy), _ptr(dx), dy.numel(), dropout_desc(rate, seed, layer, step),
                                          _stream(dy)))
     return dx
+
+
+# ------------------------------------------------------------------------------------------------------------------ #
+# Activation and merge layers (csrc/eltwise.hip)
+# ------------------------------------------------------------------------------------------------------------------ #
+
+ELT_KINDS = {'relu': _lib.ELT_RELU, 'elu': _lib.ELT_ELU, 'selu': _lib.ELT_SELU, 'sigmoid': _lib.ELT_SIGMOID,
+             'hard_sigmoid': _lib.ELT_HARD_SIGMOID, 'softplus': _lib.ELT_SOFTPLUS, 'softsign': _lib.ELT_SOFTSIGN,
+             'tanh': _lib.ELT_TANH}
+MERGE_KINDS = {'add': _lib.MERGE_ADD, 'subtract': _lib.MERGE_SUBTRACT, 'multiply': _lib.MERGE_MULTIPLY,
+               'average': _lib.MERGE_AVERAGE, 'maximum': _lib.MERGE_MAXIMUM, 'minimum': _lib.MERGE_MINIMUM}
+
+
+def activation_desc(kind, alpha=0.0, max_value=None, theta=0.0):
+    """dlwp_activation of (kind, alpha, max_value | None, theta) -- a layer's `eltwise` tuple; no cap is max_value = +inf"""
+    return _lib.Activation(ELT_KINDS[kind] if not isinstance(kind, int) else int(kind), float(alpha),
+                           float('inf') if max_value is None else float(max_value), float(theta))
+
+
+def activation_fwd(x, kind, alpha=0.0, max_value=None, theta=0.0, out=None):
+    """y = f(x), element by element (include/dlwp_hip.h: DLWP_ELT_*); out: a contiguous tensor of x.numel() floats, not x."""
+    _check_f32(x, out)
+    y = out if out is not None else torch.empty_like(x)
+    if y.numel() != x.numel():
+        raise ValueError('activation_fwd: output of %r for an input of %r' % (tuple(y.shape), tuple(x.shape)))
+    _lib.check(_lib.lib.dlwp_activation_fwd(_lib.handle(_dev(x)), _ptr(x), _ptr(y), x.numel(),
+                                            activation_desc(kind, alpha, max_value, theta), _stream(x)))
+    return y
+
+
+def activation_bwd(x, dy, kind, alpha=0.0, max_value=None, theta=0.0, out=None):
+    """dx = dy f'(x) from the forward's INPUT x; out: not x, not dy."""
+    _check_f32(x, dy, out)
+    if dy.numel() != x.numel():
+        raise ValueError('activation_bwd: gradient of %r for an input of %r' % (tuple(dy.shape), tuple(x.shape)))
+    dx = out if out is not None else torch.empty_like(x)
+    if dx.numel() != x.numel():
+        raise ValueError('activation_bwd: output of %r for an input of %r' % (tuple(dx.shape), tuple(x.shape)))
+    _lib.check(_lib.lib.dlwp_activation_bwd(_lib.handle(_dev(x)), _ptr(x), _ptr(dy), _ptr(dx), x.numel(),
+                                            activation_desc(kind, alpha, max_value, theta), _stream(x)))
+    return dx
+
+
+def _merge_args(who, kind, xs):
+    xs = list(xs)
+    if not 2 <= len(xs) <= 4:
+        raise ValueError('%s: %d sources (2 to 4)' % (who, len(xs)))
+    _check_f32(*xs)
+    if any(t.numel() != xs[0].numel() for t in xs):
+        raise ValueError('%s: sources of different sizes %r' % (who, [tuple(t.shape) for t in xs]))
+    return xs, _lib.Merge(MERGE_KINDS[kind] if not isinstance(kind, int) else int(kind), len(xs))
+
+
+def merge_fwd(kind, xs, out=None):
+    """y = ((x0 o x1) o x2) o x3 over 2 to 4 tensors of one size, left to right ('average': that sum / float32(len(xs)))."""
+    xs, d = _merge_args('merge_fwd', kind, xs)
+    _check_f32(out)
+    y = out if out is not None else torch.empty_like(xs[0])
+    if y.numel() != xs[0].numel():
+        raise ValueError('merge_fwd: output of %r for sources of %r' % (tuple(y.shape), tuple(xs[0].shape)))
+    p = [_ptr(t) for t in xs] + [_ptr(None)] * (4 - len(xs))
+    _lib.check(_lib.lib.dlwp_merge_fwd(_lib.handle(_dev(y)), p[0], p[1], p[2], p[3], _ptr(y), y.numel(), d, _stream(y)))
+    return y
+
+
+def merge_bwd(kind, xs, dy, outs=None, want=None):
+    """The gradient of every source in one pass: a list with one NEW tensor per source (None where want[i] is false), or the
+    tensors of `outs` (None entries are not written).  No two sources share a gradient tensor."""
+    xs, d = _merge_args('merge_bwd', kind, xs)
+    _check_f32(dy)
+    if dy.numel() != xs[0].numel():
+        raise ValueError('merge_bwd: gradient of %r for sources of %r' % (tuple(dy.shape), tuple(xs[0].shape)))
+    if outs is None:
+        outs = [torch.empty_like(t) if (want is None or want[i]) else None for i, t in enumerate(xs)]
+    outs = list(outs)
+    _check_f32(*outs)
+    if len(outs) != len(xs) or any(o is not None and o.numel() != dy.numel() for o in outs):
+        raise ValueError('merge_bwd: one gradient tensor (or None) of the sources\' size per source')
+    p = [_ptr(t) for t in xs] + [_ptr(None)] * (4 - len(xs))
+    q = [_ptr(t) for t in outs] + [_ptr(None)] * (4 - len(xs))
+    _lib.check(_lib.lib.dlwp_merge_bwd(_lib.handle(_dev(dy)), p[0], p[1], p[2], p[3], _ptr(dy), q[0], q[1], q[2], q[3],
+                                       dy.numel(), d, _stream(dy)))
+    return outs

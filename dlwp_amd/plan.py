@@ -66,7 +66,7 @@ class View(object):
 
 class PlanOp(object):
     """One launch.  kind in {'conv','rowconv','pad','maxpool','upsample','copy','lstm','phasew','d2s','bn','dense','dropout',
-    'scale'}."""
+    'scale','act','merge'}."""
 
     def __init__(self, kind, src, dst, xs, **kw):
         self.kind, self.src, self.dst = kind, src, dst
@@ -82,6 +82,7 @@ class PlanOp(object):
         self.inner = kw.pop('inner', 1)     # pad only: 1 = NCHW rows, C = NHWC
         self.out_shape = kw.pop('out_shape', None)   # per-sample (c, h, w) this op produces (window it writes)
         # lstm only: src = zx buffer, dst = h buffer; aux = (zh buffer | None, c_prev buffer | None, c_out buffer)
+        # merge only: src = the first source, aux = the buffers of the other sources (1 to 3), all read as whole flat tensors
         self.aux = kw.pop('aux', None)
         self.out_pool = kw.pop('out_pool', False)   # conv only: MaxPooling2D(2) applied in the epilogue (inference plans)
         self.out_d2s = kw.pop('out_d2s', False)     # conv only: the 4 F phase channels stored interleaved (inference plans)
@@ -122,6 +123,10 @@ class PlanOp(object):
                 self.out_c_total, ' +pool' if self.out_pool else '', ' phase-kernels' if self.wparam is not None else '')
             if self.lstm_f:
                 extra += ' +cell-update F=%d aux%r rec%d' % (self.lstm_f, self.aux, self.rec_act)
+        if self.kind == 'act':
+            extra = ' %s %r' % (self.layer.name, self.layer.eltwise)
+        if self.kind == 'merge':
+            extra = ' %s %s%r' % (self.layer.name, self.layer.kind, (self.src,) + tuple(self.aux))
         return '<%s %s -> %s xs=%s%s>' % (self.kind, self.src, self.dst, self.xs, extra)
 
 
@@ -137,6 +142,7 @@ class Plan(object):
         self.bn_layers = []      # BatchNormalization layers in plan order (one 'bn' op each)
         self.dense_layers = []   # Dense layers in plan order (one 'dense' op each)
         self.dropout_layers = [] # Dropout layers in graph order (training plans: one 'dropout' op each; its index keys the mask)
+        self.eltwise_layers = [] # activation / merge layers with a launch, in first-use order (stateless: any number of ops each)
 
     def new_buffer(self, c, h, w):
         self.buffers.append((int(c), int(h), int(w)))
@@ -174,7 +180,7 @@ class Plan(object):
         tot = 0
         for op in self.ops:
             c, h, w = op.xs
-            tot += c * h * w * itemsize
+            tot += c * h * w * itemsize * (1 + len(op.aux) if op.kind == 'merge' else 1)
             co, ho, wo = op.out_shape
             tot += co * ho * wo * itemsize
         for lay in self.conv_layers:
@@ -192,6 +198,10 @@ class Plan(object):
             for b, role in ((op.src, 'r'), (op.dst, 'w')):
                 if b >= 0:
                     ok[b] = ok.get(b, True) and op.kind in ('conv', 'maxpool', 'lstm') and not (role == 'w' and op.out_d2s)
+            if op.kind == 'merge':                                                # (float32 kernels)
+                for b in op.aux:
+                    if b >= 0:
+                        ok[b] = False
             if op.kind == 'lstm' or (op.kind == 'conv' and op.lstm_f):
                 zh, cp, co = op.aux
                 for b in (cp, co):                                                # the cell state stays float32
@@ -794,6 +804,49 @@ def build_plan(inputs, outputs, inference=False, fuse_d2s=True, fuse_lstm=False,
                     dst = plan.new_buffer(v.c, v.h, v.w)
                 emit(PlanOp('dropout', v.buf, dst, (v.c, v.h, v.w), layer=lay, out_c_total=v.c, out_shape=(v.c, v.h, v.w)))
                 views[t.uid] = View(dst, 0, v.c, v.c, v.h, v.w, shape=shp)
+        elif isinstance(lay, L._ActivationLayer):
+            # keras activation layers (csrc/eltwise.hip): 'linear' passes the view on; every other kind reads its input as a whole
+            # flat buffer (materialised like BatchNormalization's: the training plan keeps it, the backward takes f' from it) and
+            # writes a new buffer or the model's output slot.  Nothing lazy crosses the layer, and no state: the same layer object
+            # may appear in any number of ops.
+            if lay.eltwise is None:
+                views[t.uid] = ins[0].copy()
+            else:
+                shp = ins[0].shape
+                v = materialize(ins[0])
+                if not v.full:
+                    v = materialize(v, dst=plan.new_buffer(*v.logical))
+                if outs:
+                    dst = OUT(outs[0])
+                    plan.output_store[outs[0]] = (v.c, v.h, v.w)
+                else:
+                    dst = plan.new_buffer(v.c, v.h, v.w)
+                if lay not in plan.eltwise_layers:
+                    plan.eltwise_layers.append(lay)
+                emit(PlanOp('act', v.buf, dst, (v.c, v.h, v.w), layer=lay, out_c_total=v.c, out_shape=(v.c, v.h, v.w)))
+                views[t.uid] = View(dst, 0, v.c, v.c, v.h, v.w, shape=shp)
+        elif isinstance(lay, L._Merge):
+            # keras merge layers (csrc/eltwise.hip): 2 to 4 whole flat buffers of one size -> a new buffer or the output slot
+            shp = ins[0].shape
+            vs = []
+            for v in ins:
+                v = materialize(v)
+                if not v.full:
+                    v = materialize(v, dst=plan.new_buffer(*v.logical))
+                vs.append(v)
+            v0 = vs[0]
+            if any(v.c * v.h * v.w != v0.c * v0.h * v0.w for v in vs):
+                raise ValueError('%s: inputs of different sizes' % lay.name)
+            if outs:
+                dst = OUT(outs[0])
+                plan.output_store[outs[0]] = (v0.c, v0.h, v0.w)
+            else:
+                dst = plan.new_buffer(v0.c, v0.h, v0.w)
+            if lay not in plan.eltwise_layers:
+                plan.eltwise_layers.append(lay)
+            emit(PlanOp('merge', v0.buf, dst, (v0.c, v0.h, v0.w), layer=lay, aux=tuple(v.buf for v in vs[1:]), out_c_total=v0.c,
+                        out_shape=(v0.c, v0.h, v0.w)))
+            views[t.uid] = View(dst, 0, v0.c, v0.c, v0.h, v0.w, shape=shp)
         else:
             raise NotImplementedError('layer %s (%s) has no HIP lowering' % (lay.name, type(lay).__name__))
 
@@ -809,7 +862,7 @@ def build_plan(inputs, outputs, inference=False, fuse_d2s=True, fuse_lstm=False,
             # that launch write the output slot itself instead of copying the buffer (9 us per forward of config 4 at 8 members).
             if k == 0 and v.full and v.buf >= 0:
                 def reads(op):
-                    extra = [b for b in (op.aux or ()) if isinstance(b, int)] if op.kind in ('conv', 'lstm') else []
+                    extra = [b for b in (op.aux or ()) if isinstance(b, int)] if op.kind in ('conv', 'lstm', 'merge') else []
                     return op.src == v.buf or v.buf in extra
                 writers = [op for op in plan.ops if op.dst == v.buf]
                 w0 = writers[0] if len(writers) == 1 else None

@@ -64,6 +64,10 @@ def _layer_config(lay):
         cfg.update(start=lay.start, end=lay.end, axis=lay.axis)
     elif isinstance(lay, L.Concatenate):
         cfg.update(axis=lay.axis)
+    elif isinstance(lay, L._ActivationLayer):      # Activation, LeakyReLU, ReLU, ELU, ThresholdedReLU: Keras' own config keys
+        cfg.update({k: v for k, v in lay.get_config().items() if k not in ('name', 'trainable')})
+    elif isinstance(lay, L._Merge):                # (nothing but the inbound nodes, like Concatenate)
+        pass
     else:
         raise NotImplementedError('cannot serialise layer %s (%s)' % (lay.name, type(lay).__name__))
     if lay.batch_input_shape is not None and not isinstance(lay, L.InputLayer):
@@ -226,6 +230,10 @@ def _keras_layer_spec(lay):
         c.update(start=lay.start, end=lay.end, axis=lay.axis)
     elif isinstance(lay, L.Concatenate):
         c.update(axis=lay.axis)
+    elif isinstance(lay, L._ActivationLayer):      # keras.layers.Activation / advanced_activations: get_config() as Keras has it
+        c.update({k: v for k, v in lay.get_config().items() if k not in ('name', 'trainable')})
+    elif isinstance(lay, L._Merge):                # keras.layers.merge: name and trainable only
+        pass
     else:
         raise NotImplementedError('no Keras description of layer %s (%s)' % (lay.name, cname))
     if lay.batch_input_shape is not None and not isinstance(lay, L.InputLayer):
@@ -495,7 +503,8 @@ def import_keras_hdf5(path, custom_objects=None, device=None, compile=True, pack
                 nm, k, srcs = item
                 if all(s in tensors for s in srcs):
                     ins = [tensors[s] for s in srcs]
-                    tensors[(nm, k)] = by_name[nm](ins if isinstance(by_name[nm], L.Concatenate) or len(ins) > 1 else ins[0])
+                    tensors[(nm, k)] = by_name[nm](ins if isinstance(by_name[nm], (L.Concatenate, L._Merge)) or len(ins) > 1
+                                                   else ins[0])
                     pending.remove(item)
                     progressed = True
             if not progressed:
@@ -601,7 +610,7 @@ def load_model_file(path, custom_objects=None, device=None, package_objects=None
             tensors.append(L.KTensor(lay.batch_input_shape[1:], lay, ()))
         else:
             ins = [tensors[i] for i in node['inputs']]
-            tensors.append(lay(ins if isinstance(lay, L.Concatenate) else ins[0]))
+            tensors.append(lay(ins if isinstance(lay, (L.Concatenate, L._Merge)) else ins[0]))
     model = engine.Model(inputs=[tensors[i] for i in arch['inputs']], outputs=[tensors[i] for i in arch['outputs']],
                          name=arch.get('name'), device=device)
     for lay in objs:

@@ -646,6 +646,56 @@ typedef struct {
 int dlwp_dropout_fwd(dlwp_handle_t, const void* x, void* y, long long n, dlwp_dropout d, void* stream);
 int dlwp_dropout_bwd(dlwp_handle_t, const void* dy, void* dx, long long n, dlwp_dropout d, void* stream);
 
+/* ---- keras activation layers (Activation, LeakyReLU, ReLU, ELU, ThresholdedReLU) and merge layers (Add, Subtract, Multiply,
+ *      Average, Maximum, Minimum) on n contiguous float32 elements (csrc/eltwise.hip; the closed forms: DESIGN.md section 5.25).
+ *      Any float alignment: 16-byte accesses when every operand pointer of a call is 16-byte aligned, element accesses otherwise.
+ *      A result never aliases an operand.  No workspace, no atomics: two runs give the same bits.
+ *      activation kinds, y = f(x) and dx = dy f'(x) with f' taken from the stored INPUT x; NaN in x gives NaN in y and dx:
+ *        DLWP_ELT_RELU          x > theta ? min(x, max_value) : alpha (x - theta)   (alpha 0: 0 for every number x <= theta);
+ *                               f' = x > theta ? (x <= max_value ? 1 : 0) : alpha.  alpha >= 0, theta >= 0, max_value > theta
+ *                               (+inf: no cap).  LeakyReLU, ReLU, ThresholdedReLU and Activation('relu') are this kind.
+ *        DLWP_ELT_ELU           x > 0 ? x : alpha (exp(x) - 1)
+ *        DLWP_ELT_SELU          1.0507009873554805 elu(x, 1.6732632423543772)
+ *        DLWP_ELT_SIGMOID       1 / (1 + exp(-x));  f' = y (1 - y)
+ *        DLWP_ELT_HARD_SIGMOID  clip(0.2 x + 0.5, 0, 1);  f' = 0.2 for -2.5 < x < 2.5, else 0
+ *        DLWP_ELT_SOFTPLUS      log(1 + exp(x));  f' = sigmoid(x)
+ *        DLWP_ELT_SOFTSIGN      x / (1 + |x|);  f' = 1 / (1 + |x|)^2
+ *        DLWP_ELT_TANH          tanh(x), the convolution epilogues' form;  f' = 1 - y^2                                        */
+#define DLWP_ELT_RELU         0
+#define DLWP_ELT_ELU          1
+#define DLWP_ELT_SELU         2
+#define DLWP_ELT_SIGMOID      3
+#define DLWP_ELT_HARD_SIGMOID 4
+#define DLWP_ELT_SOFTPLUS     5
+#define DLWP_ELT_SOFTSIGN     6
+#define DLWP_ELT_TANH         7
+typedef struct {
+  int kind;                       /* DLWP_ELT_*                                                            */
+  float alpha, max_value, theta;  /* read by DLWP_ELT_RELU (all three) and DLWP_ELT_ELU (alpha)            */
+} dlwp_activation;
+int dlwp_activation_fwd(dlwp_handle_t, const void* x, void* y, long long n, dlwp_activation d, void* stream);
+int dlwp_activation_bwd(dlwp_handle_t, const void* x, const void* dy, void* dx, long long n, dlwp_activation d, void* stream);
+/*      merge: y = ((x0 o x1) o x2) o x3 over the first n_src sources (2 to 4; Subtract exactly 2), left to right in float32; the
+ *      same tensor may be named as several sources.  Average = that sum / float(n_src), an IEEE division.  Maximum / Minimum
+ *      propagate NaN (np.maximum / np.minimum) and keep the LEFT operand of two equal ones.
+ *      bwd: every non-null dx_i is OVERWRITTEN in one pass -- Add dy; Subtract dy, -dy; Average dy / float(n_src); Multiply dy
+ *      times the product of the other sources multiplied up in source order; Maximum / Minimum dy for the FIRST source equal to
+ *      the result and 0 for the others.  The dx_i are distinct tensors, none of them a source or dy.                            */
+#define DLWP_MERGE_ADD      0
+#define DLWP_MERGE_SUBTRACT 1
+#define DLWP_MERGE_MULTIPLY 2
+#define DLWP_MERGE_AVERAGE  3
+#define DLWP_MERGE_MAXIMUM  4
+#define DLWP_MERGE_MINIMUM  5
+typedef struct {
+  int kind;                       /* DLWP_MERGE_*                                                          */
+  int n_src;                      /* sources read: x0 .. x(n_src - 1); the others are ignored              */
+} dlwp_merge;
+int dlwp_merge_fwd(dlwp_handle_t, const void* x0, const void* x1, const void* x2, const void* x3, void* y, long long n,
+                   dlwp_merge d, void* stream);
+int dlwp_merge_bwd(dlwp_handle_t, const void* x0, const void* x1, const void* x2, const void* x3, const void* dy, void* dx0,
+                   void* dx1, void* dx2, void* dx3, long long n, dlwp_merge d, void* stream);
+
 /* ---- the wrapper's scaler and imputer on the device: DLWPNeuralNet(scaler_type='StandardScaler' | 'MinMaxScaler',
  *      impute_missing=True) runs SimpleImputer.transform and the scaler's transform in front of every model call and the
  *      scaler's inverse_transform behind it (DLWP/model/models.py:134-170, 230-245) -- sklearn on the host.  Here one launch per
@@ -697,6 +747,10 @@ int dlwp_scale_inv(dlwp_handle_t, const void* x, void* y, const void* shift, con
                                    * f = c h w; w / b = shift / scale buffer | -1, aux[0] = fill buffer | -1000, aux[1] =
                                    * DLWP_SCALE_*, aux[2] = 0 forward | 1 inverse (no fill).  float64 parameter buffers, read
                                    * at every launch: a graph never holds a refitted scaler's old values.                  */
+#define DLWP_OP_ACTIVATION 12     /* dlwp_activation_fwd: src, dst, xs = (n, c, h, w) with n c h w elements; conv.act = DLWP_ELT_*,
+                                   * aux[0..2] = the bits of alpha, max_value, theta (floats)                               */
+#define DLWP_OP_MERGE     13      /* dlwp_merge_fwd: src = the first source, aux[0..2] = the others | -1000, dst, xs as above;
+                                   * conv.act = DLWP_MERGE_*                                                                */
 typedef struct {
   int kind;                 /* DLWP_OP_*                                                                */
   int src, dst;             /* buffer indices                                                              */
