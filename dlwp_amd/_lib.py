@@ -22,6 +22,7 @@ OPT_FEW_STREAM = 6
 OPT_SPLITK = 7
 OPT_WINO_XLOADER = 8
 OPT_WINO_FLAT = 9
+OPT_FEW_WINO = 10
 F32, BF16, BF16_O8 = 0, 1, 2
 ROLLOUT_PREPARED = 0x100
 PAD_ZERO, PAD_WRAP, PAD_EDGE, PAD_REFLECT, PAD_SYMMETRIC = 0, 1, 2, 3, 4

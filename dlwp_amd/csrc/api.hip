@@ -148,6 +148,7 @@ static int set_in(dlwp_options& o, int option, int value, int* previous, const c
     case DLWP_OPT_WGRAD_FILL: slot = &o.wgrad_fill; value = value < 1 ? 1 : (value > 64 ? 64 : value); break;
     case DLWP_OPT_WINO_XLOADER: slot = &o.wino_xld; value &= 7; break;
     case DLWP_OPT_WINO_FLAT: slot = &o.wino_flat; value = value < 0 ? 0 : (value > 2 ? 2 : value); break;
+    case DLWP_OPT_FEW_WINO: slot = &o.few_wino; value = value ? 1 : 0; break;
     case DLWP_OPT_SPLITK: slot = &o.splitk; value = value < 0 ? 0 : (value > 64 ? 64 : value); break;
     default: DLWP_FAIL(DLWP_EINVAL, "%s: unknown option %d", fn, option);
   }

@@ -15,6 +15,7 @@ struct dlwp_options {
   int wgrad_fill = 4;   // weight gradient: workgroups per CU the split count aims at, in eighths of 16 waves (DLWP_OPT_WGRAD_FILL)
   int wino_xld = 7;     // Winograd input loaders: bit 0 column pairs, bit 1 source-resolution fetch of an up-sampled source, bit 2 edge pairs (DLWP_OPT_WINO_XLOADER)
   int wino_flat = 1;    // Winograd runs of 64 consecutive tiles on narrow maps: 0 never, 1 from one workgroup per CU on, 2 always (DLWP_OPT_WINO_FLAT)
+  int few_wino = 0;     // conv_fwd_few_wino.hip: the pooled dilation-2 first layer on Winograd multiplies; 0 on a handle, the inference executor scopes it to 1 (DLWP_OPT_FEW_WINO)
   int splitk = 0;       // Winograd forward on small grids: 0 never (default, r5: batch-invariant bits), 1 by rule, k >= 2 forced split count (DLWP_OPT_SPLITK)
 };
 const dlwp_options& dlwp_default_options();

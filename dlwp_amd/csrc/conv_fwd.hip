@@ -779,6 +779,18 @@ int few_stream_grid(dlwp_handle_t h, const ConvArgs& a, const dlwp_conv2d* cd, c
   return (int)(items < slots ? items : slots);
 }
 
+// conv_fwd_few_wino.hip (DLWP_OPT_FEW_WINO = 1) for the pooled dilation-2 layer of at most four input channels?  Returns the grid
+// (0: no).  Another family (Winograd round-off instead of the direct sum's), so the answer follows from the layer's geometry ALONE,
+// never from the batch: a member's bits do not depend on its batch mates.  Grid = 3 workgroups per CU (one channel tile's 64
+// accumulator registers at a time: three waves per SIMD, as conv_fwd_few.hip), one item per workgroup below that.
+int few_wino_grid(dlwp_handle_t h, const ConvArgs& a, const dlwp_conv2d* cd) {
+  if (h->opt.few_wino == 0 || h->opt.forced_cfg >= 0 || cd->kh != cd->kw) return 0;
+  if (!dlwp_conv_few_wino_covers(a, cd->kh, cd->dil_h, cd->dil_w)) return 0;
+  const long long items = (long long)dlwp_ceil_div(a.Ho, 8) * dlwp_ceil_div(a.Wo, 32) * (a.Cout / 32) * a.N;
+  const long long slots = 3ll * h->cu_count;
+  return (int)(items < slots ? items : slots);
+}
+
 // conv_fwd_wino2s.hip instead of the chosen position-split Winograd instance (16-channel blocks: the restated output layer)?
 // Returns the grid (0: no).  Same bits as every non-COMPAT instance of conv_fwd_wino2_kernel.h, so the choice may depend on the
 // batch.  Grid = 2 workgroups of 512 threads per CU (73 KB of LDS each); taken from 2.5 items per workgroup on, as the other
@@ -888,6 +900,16 @@ int dlwp_launch_conv2d(dlwp_handle_t h, const void* x, const void* w, const void
     }
     a.out_pool = 0;                 // (a.Hp / a.Wp stay: the pooled tensor's shape)
     a.y2 = (float*)y_pool;
+  }
+  if (!lstm && !act_epi && !y_pool) {
+    if (const int wg = few_wino_grid(h, a, cd)) {   // the pooled first layer on Winograd multiplies (opt-in: another family's bits)
+      a.tiles_h = dlwp_ceil_div(a.Ho, 8);
+      a.tiles_w = dlwp_ceil_div(a.Wo, 32);
+      a.cout_tiles = a.Cout / 32;
+      dlwp_conv_few_wino_launch(a, wg, s);
+      DLWP_LAUNCH_CHECK("conv2d_fwd_few_wino_f32");
+      return DLWP_OK;
+    }
   }
   if (!lstm && !act_epi) {      // (r4: the streaming kernel also stores the unpooled tensor, alone or beside the pooled one)
     const int fg = few_stream_grid(h, a, cd, lp);
@@ -1058,7 +1080,7 @@ static int split_count_of(dlwp_handle_t h, dlwp_shape4 xs, const dlwp_conv2d* cd
   ConvArgs a = make_args(nullptr, nullptr, nullptr, nullptr, xs, cd, ys, dtype);
   LaunchPlan lp;
   plan_launch(h, a, cd, &lp);
-  if (lp.primary < 0 || few_stream_grid(h, a, cd, lp) > 0) return 1;
+  if (lp.primary < 0 || few_wino_grid(h, a, cd) > 0 || few_stream_grid(h, a, cd, lp) > 0) return 1;
   plan_splitk(h, a, cd, &lp, false, DLWP_SPLITK_REGION_BYTES);
   if (lp.ksplit > 1 && bytes) *bytes = splitk_bytes(registry().entries[lp.primary], lp.grid, lp.ksplit);
   return lp.ksplit;
@@ -1462,6 +1484,12 @@ int dlwp_conv2d_launch_info(dlwp_handle_t h, dlwp_shape4 xs, const dlwp_conv2d* 
     const long long total = (long long)a.N * a.Cout * a.Ho * a.Wo;
     const long long want = (total + 255) / 256, cap = (long long)h->cu_count * 16;
     out2[0] = dlwp_launch_info{-1, (int)(want < cap ? want : cap), 256, 0.0, 0, 0};
+    *n_launches = 1;
+    return DLWP_OK;
+  }
+  if (const int wg = few_wino_grid(h, a, cd)) {   // config -5: conv_fwd_few_wino.hip -- 16 positions x 4 channels x 32 output channels
+    const double items = (double)dlwp_ceil_div(a.Ho, 8) * dlwp_ceil_div(a.Wo, 32) * (a.Cout / 32) * a.N;    // per 2x2 tile, 64 tiles an item
+    out2[0] = dlwp_launch_info{-5, wg, 256, 2.0 * 64.0 * 16.0 * 4.0 * 32.0 * items, 0, 0};
     *n_launches = 1;
     return DLWP_OK;
   }

@@ -653,6 +653,10 @@ static int conv_prepare() {
 // -- same tiles, same bits -- when the batch gives every workgroup several samples to walk over (DLWP_OPT_FEW_STREAM).
 bool dlwp_conv_few_covers(const ConvArgs& a, int ks, int dil_h, int dil_w);
 void dlwp_conv_few_launch(const ConvArgs& a, int dil, int grid, hipStream_t s);
+// conv_fwd_few_wino.hip: the same streaming structure on Winograd F(2x2, 3x3) multiplies for the pooled dilation-2 layer of at most
+// four input channels and whole 32-channel tiles (DLWP_OPT_FEW_WINO) -- the Winograd family's bits, not the direct family's.
+bool dlwp_conv_few_wino_covers(const ConvArgs& a, int ks, int dil_h, int dil_w);
+void dlwp_conv_few_wino_launch(const ConvArgs& a, int grid, hipStream_t s);
 // conv_fwd_wino2s.hip: the streaming form of the position-split Winograd kernel for 16-output-channel blocks
 bool dlwp_conv_wino2s_covers(const ConvArgs& a);
 int dlwp_conv_wino2s_launch(const ConvArgs& a, int grid, hipStream_t s);

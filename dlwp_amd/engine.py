@@ -64,6 +64,17 @@ class Executor(object):
         self._oct = self._octet_buffers() if self._bf16 and os.environ.get('DLWP_BF16_O8', '1') != '0' else set()
         self._bn = {}            # (op index, batch size) -> the batch statistics a training forward keeps for the backward
         self.dropout_step = 0    # the training step whose masks a training forward draws (Trainer: the optimizer's iteration)
+        self._few_wino = None    # few_wino(): does the plan's first convolution run on Winograd multiplies in this executor's launches?
+
+    def few_wino(self):
+        """The pooled dilation-2 first layer on Winograd multiplies (csrc/conv_fwd_few_wino.hip, DLWP_OPT_FEW_WINO): this executor
+        scopes the option to 1 around its own launches and captures when the plan's FIRST convolution qualifies -- a plan with a
+        pooling epilogue, i.e. never the training plan, which materialises both tensors.  DLWP_FEW_WINO=0: never (A/B runs).
+        Launch by launch (Executor.run, and whoever times or asks about a layer with this executor's descriptors) the scope hangs
+        on the layer's descriptor (ops.few_wino_scope_of); a rollout capture is scoped as a whole (_make_rollout)."""
+        if self._few_wino is None:
+            self._descriptors()
+        return self._few_wino
 
     # -- buffers ----------------------------------------------------------------------------------------------------- #
     def scratch(self, n):
@@ -121,6 +132,13 @@ class Executor(object):
                     descs.append(ops.make_pad(*op.halo))
                 else:
                     descs.append(None)
+            self._few_wino = False
+            if os.environ.get('DLWP_FEW_WINO', '1') != '0':
+                for op, d in zip(self.plan.ops, descs):
+                    if op.kind == 'conv':           # the plan's first convolution
+                        if op.src2 is None and ops.few_wino_qualifies(op.xs[0], d, op.src in self._bf16, op.dst in self._bf16):
+                            d.few_wino = self._few_wino = True
+                        break
             self._descs = descs
         return self._descs
 
@@ -449,6 +467,12 @@ class Executor(object):
         reading its state from the series slot the call before wrote (state0 for first = 0) -- one of several graphs launched one
         behind the other on a stream (StreamedRollout).  ws: the prepared-weights workspace to use (slices of one member count
         share it); prepared: the slice launched in front has filled it."""
+        from . import ops
+        # (every rollout form -- grouped, split, fed, streamed -- is captured here: the first layer's family as in Executor.run)
+        with ops.few_wino_scope(self.few_wino(), self.device.index):
+            return self._capture_rollout(state0, series, calls, groups, chain, span, ws, prepared, fed)
+
+    def _capture_rollout(self, state0, series, calls, groups, chain, span, ws, prepared, fed):
         from . import _lib, ops
         _lib.drain_graveyard()          # a safe point: nothing is being captured yet
         n_total = int(state0.shape[0])

@@ -184,12 +184,13 @@ def conv2d(x, w_hwio, bias, cd, out=None, direct=False, x_channels=None, compute
             return None
         _lib.check(rc)
         return out
-    if prepared is not None and not direct:
-        _lib.check(_lib.lib.dlwp_conv2d_fwd_prepared(_lib.handle(_dev(x)), _ptr(x), _ptr(w_hwio), _ptr(prepared),
-                                                     _ptr(bias), _ptr(out), xs, ctypes.byref(cd), dt, _stream(x)))
-        return out
-    _lib.check(fn(_lib.handle(_dev(x)), _ptr(x), _ptr(w_hwio), _ptr(bias), _ptr(out), xs, ctypes.byref(cd), dt,
-                  _stream(x)))
+    with few_wino_scope_of(cd, _dev(x)):
+        if prepared is not None and not direct:
+            _lib.check(_lib.lib.dlwp_conv2d_fwd_prepared(_lib.handle(_dev(x)), _ptr(x), _ptr(w_hwio), _ptr(prepared),
+                                                         _ptr(bias), _ptr(out), xs, ctypes.byref(cd), dt, _stream(x)))
+            return out
+        _lib.check(fn(_lib.handle(_dev(x)), _ptr(x), _ptr(w_hwio), _ptr(bias), _ptr(out), xs, ctypes.byref(cd), dt,
+                      _stream(x)))
     return out
 
 
@@ -433,9 +434,10 @@ def conv_launch_info(x_shape, cd, dtype=None, device_index=0):
     resolution)], one entry per kernel launch (dlwp_conv2d_launch_info)."""
     out = (_lib.LaunchInfo * 2)()
     n = ctypes.c_int(0)
-    _lib.check(_lib.lib.dlwp_conv2d_launch_info(_lib.handle(device_index), Shape4(*[int(v) for v in x_shape]),
-                                                ctypes.byref(cd), _lib.F32 if dtype is None else int(dtype), out,
-                                                ctypes.byref(n)))
+    with few_wino_scope_of(cd, device_index):
+        _lib.check(_lib.lib.dlwp_conv2d_launch_info(_lib.handle(device_index), Shape4(*[int(v) for v in x_shape]),
+                                                    ctypes.byref(cd), _lib.F32 if dtype is None else int(dtype), out,
+                                                    ctypes.byref(n)))
     return [(o.config, o.grid, o.block_threads, o.matrix_flops, bool(o.bf16_matrix), int(o.x_loader)) for o in out[:n.value]]
 
 
@@ -447,6 +449,46 @@ def set_few_stream(mode):
     """DLWP_OPT_FEW_STREAM: the streaming kernel for pooled 3x3 layers of at most four input channels (csrc/conv_fwd_few.hip):
     0 never, 1 from 8 tiles per workgroup on (default), 2 whenever the layer qualifies.  Returns the previous setting."""
     return int(_lib.set_option(_lib.OPT_FEW_STREAM, int(mode)))
+
+
+def set_few_wino(mode, device_index=None):
+    """DLWP_OPT_FEW_WINO: the pooled dilation-2 first layer (3x3, at most four input channels, whole 32-channel tiles, float32) on
+    Winograd multiplies (csrc/conv_fwd_few_wino.hip, launch-info config -5): 0 (default on a handle) keeps the direct family's
+    kernel and bits, 1 takes the kernel at every batch size.  Returns the previous setting."""
+    return int(_lib.set_option(_lib.OPT_FEW_WINO, int(mode), device_index))
+
+
+def few_wino_qualifies(cin, cd, in_bf16=False, out_bf16=False):
+    """Host restatement of dlwp_conv_few_wino_covers' geometry part: does DLWP_OPT_FEW_WINO = 1 change how a convolution with
+    descriptor `cd` on `cin` stored input channels runs?  (The library has the last word: map sizes past its 32-bit offsets, odd
+    pooled widths.)"""
+    return bool(cd.kh == 3 and cd.kw == 3 and cd.dil_h == 2 and cd.dil_w == 2 and 1 <= int(cin) <= 4 and cd.cout % 32 == 0 and
+                cd.out_pool == 1 and cd.src_mode == _lib.SRC_DIRECT and not cd.out_d2s and not cd.lstm_f and
+                not in_bf16 and not out_bf16)
+
+
+class few_wino_scope(object):
+    """`with few_wino_scope(on, device_index):` -- DLWP_OPT_FEW_WINO = 1 on that device's handle (default: the current device) for
+    the launches (or the graph capture) inside, the previous setting afterwards; on = False: nothing changes."""
+
+    def __init__(self, on, device_index=None):
+        self.on, self.dev, self.prev = bool(on), device_index, None
+
+    def __enter__(self):
+        if self.on:
+            self.prev = set_few_wino(1, self.dev)
+        return self
+
+    def __exit__(self, *exc):
+        if self.on:
+            set_few_wino(self.prev, self.dev)
+        return False
+
+
+def few_wino_scope_of(cd, device_index=None):
+    """The scope of a launch with descriptor `cd`: on for the descriptor an inference Executor marked (its plan's first
+    convolution, `cd.few_wino`), so that the layer runs -- and is timed and described -- as in that executor's rollout."""
+    return few_wino_scope(getattr(cd, 'few_wino', False), device_index)
 
 
 def set_wino_xloader(mask):

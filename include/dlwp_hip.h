@@ -164,6 +164,17 @@ int         dlwp_device_info(dlwp_handle_t h, int* cu_count, int* lds_bytes, cha
                                         * from one workgroup per CU on; 2: whenever the layer qualifies.  Not with a forced
                                         * configuration or split-K.  Identical bits whatever the setting (DLWP_WINO_FLAT in the
                                         * environment)                                                                          */
+#define DLWP_OPT_FEW_WINO          10  /* the pooled first layer on Winograd multiplies (csrc/conv_fwd_few_wino.hip, launch-info
+                                        * config -5): 3x3, dilation 2, at most 4 input channels, whole 32-channel tiles,
+                                        * MaxPooling2D(2) epilogue, float32 -- the streaming structure of DLWP_OPT_FEW_STREAM's
+                                        * kernel with F(2x2,3x3) on the four parity sub-lattices: 16 multiplies instead of 36.
+                                        * 0 (default on every handle): plain dlwp_conv2d_fwd calls keep the direct family's
+                                        * bits; 1: a qualifying layer runs the kernel at EVERY batch size (the family follows
+                                        * from the geometry alone: a sample's bits do not depend on its batch mates).  The
+                                        * bits are those of the general Winograd family on this geometry, i.e. ordinary float32
+                                        * round-off away from the direct sum.  Not with a forced configuration.  The inference
+                                        * executor of the Python package scopes it to 1 around its own launches and captures
+                                        * (DLWP_FEW_WINO=0 in the environment keeps it from doing so)                           */
 int         dlwp_set_option(dlwp_handle_t h, int option, int value, int* previous);
 /* the defaults themselves: what handles created AFTERWARDS start from, and what the handle-less host logic (planner hints
  * called with a NULL handle, e.g. on a machine without a GPU) uses.  Existing handles are not touched.                 */
@@ -248,7 +259,8 @@ int dlwp_conv2d_pick_config(dlwp_handle_t, dlwp_shape4 xs, const dlwp_conv2d* cd
  * SQ_INSTS_MFMA x 2048 (v_mfma_f32_16x16x4_f32) of a rocprofv3 --pmc pass.  config: index for dlwp_conv2d_config_info
  * (-1: the one-thread-per-output vector kernel, no matrix work; -2 / -3: the streaming kernels of DLWP_OPT_FEW_STREAM -- few
  * input channels under a pooling epilogue / 16-output-channel Winograd blocks --, whose grid is a number of persistent
- * workgroups, not of tiles).  out2 must hold 2 entries.                                                                   */
+ * workgroups, not of tiles; -4: the flat Winograd runs of DLWP_OPT_WINO_FLAT; -5: the Winograd first-layer kernel of
+ * DLWP_OPT_FEW_WINO).  out2 must hold 2 entries.                                                                   */
 typedef struct {
   int config, grid, block_threads;
   double matrix_flops;
