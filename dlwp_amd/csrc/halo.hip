@@ -829,7 +829,7 @@ int dlwp_pad2d_bwd(dlwp_handle_t h, const void* dy, void* dx, int outer, int H, 
 
 int dlwp_maxpool2_fwd(dlwp_handle_t h, const void* x, void* y, dlwp_shape4 xs, int dtype, void* stream) {
   DLWP_TAPE(h, stream, dlwp_maxpool2_fwd, h, x, y, xs, dtype);
-  const bool x_ok = x && y;
+  const bool x_ok = x && (y || xs.h < 2 || xs.w < 2);  // a map of one row or column pools to an empty tensor: null data pointer
   const bool bf16 = dtype == DLWP_BF16;
   if (bf16) dtype = DLWP_F32;  // the shared argument check knows fp32 only; this entry point also stores bf16
   POOL_ARGS_OK("dlwp_maxpool2_fwd");
@@ -851,7 +851,7 @@ int dlwp_maxpool2_fwd(dlwp_handle_t h, const void* x, void* y, dlwp_shape4 xs, i
 int dlwp_maxpool2_bwd(dlwp_handle_t h, const void* x, const void* dy, void* dx, dlwp_shape4 xs, int dtype,
                       void* stream) {
   DLWP_TAPE(h, stream, dlwp_maxpool2_bwd, h, x, dy, dx, xs, dtype);
-  const bool x_ok = x && dy && dx;
+  const bool x_ok = x && dx && (dy || xs.h < 2 || xs.w < 2);  // (an empty pooled gradient: every dx element is zero)
   POOL_ARGS_OK("dlwp_maxpool2_bwd");
   const long long planes = (long long)xs.n * xs.c;
   const long long total = planes * ((xs.h + 1) / 2) * ((xs.w + 1) / 2);
@@ -928,10 +928,11 @@ int dlwp_copy_channels(dlwp_handle_t h, const void* src, void* dst, int n, int c
 int dlwp_series_merge_time(dlwp_handle_t h, const void* series, void* out, int t, int n, int time_dim, int v, int hw,
                            int dtype, void* stream) {
   DLWP_UNTAPED(dlwp_series_merge_time);
-  DLWP_CHECK_ARG(h && series && out, "dlwp_series_merge_time: null handle or pointer");
+  DLWP_CHECK_ARG(h != nullptr, "dlwp_series_merge_time: null handle or pointer");
   DLWP_CHECK_ARG(dtype == DLWP_F32, "dlwp_series_merge_time: dtype %d not supported", dtype);
   DLWP_CHECK_ARG(t >= 0 && n >= 0 && time_dim > 0 && v > 0 && hw > 0, "dlwp_series_merge_time: bad shape");
-  if (t == 0 || n == 0) return DLWP_OK;
+  if (t == 0 || n == 0) return DLWP_OK;  // empty series: torch hands out null data pointers for empty tensors
+  DLWP_CHECK_ARG(series && out, "dlwp_series_merge_time: null handle or pointer");
   // in [t, n, td, run] with run = v*hw  ->  out [t, td, n, run]
   const long long run = (long long)v * hw;
   const bool vec = run % 4 == 0 && aligned16(series) && aligned16(out);

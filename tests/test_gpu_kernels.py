@@ -1,6 +1,8 @@
 """GPU parity tests proper: every libdlwp_hip.so kernel, called through the C ABI, against the oracle on the same
 seeded inputs and against the committed golden fixtures.  Bit-exact for padding / pooling / copies; fp32 convolution
-within 1e-5 of the float64 direct sum (relative to the output scale; the tolerance BASELINE.md states)."""
+within 1e-5 of the float64 direct sum (relative to the output scale; the tolerance BASELINE.md states).
+The padding / pooling / copy kernels on every route of their host dispatch (misaligned views, channels-last, switch points, capped
+grids, the element-wise backward): tests/test_gpu_halo.py."""
 import numpy as np
 import pytest
 import torch
