@@ -551,10 +551,16 @@ class BackwardPass(object):
         else:
             book.deposit(op.src, 0, c.src.shape[1], ops.maxpool2_bwd(c.src, c.gD))
 
+    def _avgpool(self, c):
+        """AveragePooling2D(2): 0.25 * dy to every element of a window, written in one pass (no part in pending_pool: the fused
+        pooling backward of the convolutions is max-pooling's)."""
+        if c.op.src != P.STATE_IN:
+            self.book.deposit(c.op.src, 0, c.src.shape[1], ops.avgpool2_bwd(c.gD, c.src.shape))
+
     def _upsample(self, c):
         if c.op.src != P.STATE_IN:
             self.book.deposit(c.op.src, 0, c.src.shape[1], ops.upsample2_bwd(c.gD))
 
     adjoints = {'d2s': _d2s, 'conv': _conv, 'rowconv': _rowconv, 'dense': _dense, 'dropout': _dropout, 'bn': _bn,
-                'lstm': _lstm, 'copy': _copy, 'pad': _pad, 'maxpool': _maxpool, 'upsample': _upsample, 'act': _act,
-                'merge': _merge}
+                'lstm': _lstm, 'copy': _copy, 'pad': _pad, 'maxpool': _maxpool, 'avgpool': _avgpool, 'upsample': _upsample,
+                'act': _act, 'merge': _merge}

@@ -6,7 +6,7 @@ reference's scripts import, so code written against jweyn/DLWP + Keras runs uned
     from DLWP.model import DLWPNeuralNet, DataGenerator
     from DLWP.custom import EarlyStoppingMin, RNNResetStates, PeriodicPadding2D, slice_layer
     from DLWP.util import save_model, load_model, train_test_split_ind
-    from keras.layers import Input, ZeroPadding2D, Conv2D, MaxPooling2D, UpSampling2D, concatenate
+    from keras.layers import Input, ZeroPadding2D, Conv2D, MaxPooling2D, AveragePooling2D, UpSampling2D, concatenate
     from keras.models import Model
     from keras.callbacks import History
     from keras.losses import mean_squared_error

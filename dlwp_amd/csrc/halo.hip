@@ -570,6 +570,113 @@ __global__ __launch_bounds__(256) void maxpool2_bwd_kernel(const float* __restri
   }
 }
 
+// ------------------------------------------------------------------------------------------------------------------ //
+// 2x2 average pooling.  A window a b / c d gives ((a + b) + (c + d)) * 0.25f on every route, so the routes agree to the
+// bit; the backward writes 0.25f * dy to the four elements of a window and +0 to an odd last row / column.
+// VEC = windows per thread along a row: 2 = W % 4 == 0 (16-byte accesses on x / dx, 8-byte on y / dy), 1 with PAIR = W even
+// (8-byte accesses on x / dx), 1 without = any W (scalar).  The host picks the route from W and the pointers: every
+// row start (p*H + r)*W is then a multiple of the access width whatever H is.
+// ------------------------------------------------------------------------------------------------------------------ //
+__device__ __forceinline__ float avg4(float a, float b, float c, float d) { return ((a + b) + (c + d)) * 0.25f; }
+
+template <int VEC, bool PAIR>
+__global__ __launch_bounds__(256) void avgpool2_fwd_kernel(const float* __restrict__ x, float* __restrict__ y,
+                                                           long long planes, int H, int W) {
+  const int H2 = H / 2, W2 = W / 2, Wt = W2 / VEC;   // Wt threads per pooled row
+  const long long total = planes * H2 * Wt;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+    const int j = (int)(i % Wt);
+    const long long q = i / Wt;   // = p*H2 + r
+    const int r = (int)(q % H2);
+    const long long p = q / H2;
+    const float* s = x + (p * H + 2 * r) * W + 2 * VEC * j;
+    if (VEC == 2) {
+      const f32x4 a = *(const f32x4*)s, b = *(const f32x4*)(s + W);
+      const f32x2 o = {avg4(a[0], a[1], b[0], b[1]), avg4(a[2], a[3], b[2], b[3])};
+      *(f32x2*)(y + q * W2 + 2 * j) = o;
+    } else if (PAIR) {
+      const f32x2 a = *(const f32x2*)s, b = *(const f32x2*)(s + W);
+      y[i] = avg4(a[0], a[1], b[0], b[1]);
+    } else {
+      y[i] = avg4(s[0], s[1], s[W], s[W + 1]);
+    }
+  }
+}
+
+// bfloat16 storage: the float32 expression on the widened values, rounded to nearest-even once at the store; a 2x2 window is
+// two 32-bit loads when the row length is even
+__global__ __launch_bounds__(256) void avgpool2_fwd_bf16_kernel(const unsigned short* __restrict__ x,
+                                                                unsigned short* __restrict__ y, long long planes, int H,
+                                                                int W) {
+  const int H2 = H / 2, W2 = W / 2;
+  const long long total = planes * H2 * W2;
+  const bool even = (W & 1) == 0;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+    const int j = (int)(i % W2);
+    const long long q = i / W2;
+    const int r = (int)(q % H2);
+    const long long p = q / H2;
+    const unsigned short* s = x + (p * H + 2 * r) * W + 2 * j;
+    unsigned a, b;
+    if (even) {
+      a = *(const unsigned*)s;
+      b = *(const unsigned*)(s + W);
+    } else {
+      a = (unsigned)s[0] | ((unsigned)s[1] << 16);
+      b = (unsigned)s[W] | ((unsigned)s[W + 1] << 16);
+    }
+    const float m = avg4(__builtin_bit_cast(float, a << 16), __builtin_bit_cast(float, a & 0xffff0000u),
+                         __builtin_bit_cast(float, b << 16), __builtin_bit_cast(float, b & 0xffff0000u));
+    y[i] = __builtin_bit_cast(unsigned short, (__bf16)m);
+  }
+}
+
+// one thread per window (VEC = 2: per pair of windows) of the ceil-divided grid; the partial windows of an odd edge write the
+// zeros of the leftover row / column.  Every element of dx is written exactly once.
+template <int VEC, bool PAIR>
+__global__ __launch_bounds__(256) void avgpool2_bwd_kernel(const float* __restrict__ dy, float* __restrict__ dx,
+                                                           long long planes, int H, int W) {
+  const int H2 = H / 2, W2 = W / 2, Hc = (H + 1) / 2, Wc = (W + 1) / 2, Wt = Wc / VEC;   // (VEC == 2: W % 4 == 0, Wc = W2)
+  const long long total = planes * Hc * Wt;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+    const int j = (int)(i % Wt);
+    const long long q = i / Wt;
+    const int r = (int)(q % Hc);
+    const long long p = q / Hc;
+    float* d = dx + (p * H + 2 * r) * W + 2 * VEC * j;
+    const float* g = dy + (p * H2 + r) * W2 + VEC * j;
+    if (VEC == 2) {
+      if (r < H2) {
+        const f32x2 gg = *(const f32x2*)g;
+        const float g0 = 0.25f * gg[0], g1 = 0.25f * gg[1];
+        const f32x4 v = {g0, g0, g1, g1};
+        *(f32x4*)d = v;
+        *(f32x4*)(d + W) = v;
+      } else {
+        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+        *(f32x4*)d = z;
+      }
+    } else if (PAIR) {
+      const float g0 = r < H2 ? 0.25f * g[0] : 0.f;
+      const f32x2 v = {g0, g0};
+      *(f32x2*)d = v;
+      if (r < H2) *(f32x2*)(d + W) = v;
+    } else if (r < H2 && j < W2) {
+      const float g0 = 0.25f * g[0];
+      d[0] = g0;
+      d[1] = g0;
+      d[W] = g0;
+      d[W + 1] = g0;
+    } else {
+      const bool has_c = 2 * j + 1 < W, has_r = 2 * r + 1 < H;
+      d[0] = 0.f;
+      if (has_c) d[1] = 0.f;
+      if (has_r) d[W] = 0.f;
+      if (has_r && has_c) d[W + 1] = 0.f;
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void upsample2_fwd_kernel(const float* __restrict__ x, float* __restrict__ y,
                                                             long long planes, int H, int W) {
   const long long total = planes * H * W;
@@ -859,6 +966,67 @@ int dlwp_maxpool2_bwd(dlwp_handle_t h, const void* x, const void* dy, void* dx, 
   maxpool2_bwd_kernel<<<grid_for(total, 256, h->cu_count), 256, 0, (hipStream_t)stream>>>(
       (const float*)x, (const float*)dy, (float*)dx, planes, xs.h, xs.w);
   DLWP_LAUNCH_CHECK("maxpool2_bwd_kernel");
+  return DLWP_OK;
+}
+
+// access route of the float32 average-pooling kernels: `wide` is the tensor at input resolution (x / dx: 16- or 8-byte
+// accesses), `narrow` the pooled one (y / dy: 8-byte accesses on the two-window route only).  2 = two windows per thread,
+// 1 = one window with 8-byte accesses, 0 = scalar.  W decides first: plane and row starts are multiples of W only.
+static inline int avgpool_route(int W, const void* wide, const void* narrow) {
+  if (W % 4 == 0 && aligned16(wide) && (((uintptr_t)narrow) & 7) == 0) return 2;
+  if (W % 2 == 0 && (((uintptr_t)wide) & 7) == 0) return 1;
+  return 0;
+}
+
+int dlwp_avgpool2_fwd(dlwp_handle_t h, const void* x, void* y, dlwp_shape4 xs, int dtype, void* stream) {
+  DLWP_TAPE(h, stream, dlwp_avgpool2_fwd, h, x, y, xs, dtype);
+  const bool x_ok = x && (y || xs.h < 2 || xs.w < 2);  // a map of one row or column pools to an empty tensor: null data pointer
+  const bool bf16 = dtype == DLWP_BF16;
+  if (bf16) dtype = DLWP_F32;  // the shared argument check knows fp32 only; this entry point also stores bf16
+  POOL_ARGS_OK("dlwp_avgpool2_fwd");
+  const long long planes = (long long)xs.n * xs.c;
+  const long long total = planes * (xs.h / 2) * (xs.w / 2);
+  if (total == 0) return DLWP_OK;
+  hipStream_t s = (hipStream_t)stream;
+  if (bf16) {
+    avgpool2_fwd_bf16_kernel<<<grid_for(total, 256, h->cu_count), 256, 0, s>>>((const unsigned short*)x, (unsigned short*)y,
+                                                                               planes, xs.h, xs.w);
+    DLWP_LAUNCH_CHECK("avgpool2_fwd_bf16_kernel");
+    return DLWP_OK;
+  }
+  const int route = avgpool_route(xs.w, x, y);
+  if (route == 2)
+    avgpool2_fwd_kernel<2, false><<<grid_for(total / 2, 256, h->cu_count), 256, 0, s>>>((const float*)x, (float*)y, planes,
+                                                                                        xs.h, xs.w);
+  else if (route == 1)
+    avgpool2_fwd_kernel<1, true><<<grid_for(total, 256, h->cu_count), 256, 0, s>>>((const float*)x, (float*)y, planes, xs.h,
+                                                                                   xs.w);
+  else
+    avgpool2_fwd_kernel<1, false><<<grid_for(total, 256, h->cu_count), 256, 0, s>>>((const float*)x, (float*)y, planes, xs.h,
+                                                                                    xs.w);
+  DLWP_LAUNCH_CHECK("avgpool2_fwd_kernel");
+  return DLWP_OK;
+}
+
+// xs = shape of dx; dy is (n, c, h/2, w/2).  Every element of dx is written: no x, no accumulation.
+int dlwp_avgpool2_bwd(dlwp_handle_t h, const void* dy, void* dx, dlwp_shape4 xs, int dtype, void* stream) {
+  DLWP_TAPE(h, stream, dlwp_avgpool2_bwd, h, dy, dx, xs, dtype);
+  const bool x_ok = dx && (dy || xs.h < 2 || xs.w < 2);  // (an empty pooled gradient: every dx element is zero)
+  POOL_ARGS_OK("dlwp_avgpool2_bwd");
+  const long long planes = (long long)xs.n * xs.c;
+  const long long total = planes * ((xs.h + 1) / 2) * ((xs.w + 1) / 2);
+  hipStream_t s = (hipStream_t)stream;
+  const int route = avgpool_route(xs.w, dx, dy);
+  if (route == 2)
+    avgpool2_bwd_kernel<2, false><<<grid_for(total / 2, 256, h->cu_count), 256, 0, s>>>((const float*)dy, (float*)dx, planes,
+                                                                                        xs.h, xs.w);
+  else if (route == 1)
+    avgpool2_bwd_kernel<1, true><<<grid_for(total, 256, h->cu_count), 256, 0, s>>>((const float*)dy, (float*)dx, planes, xs.h,
+                                                                                   xs.w);
+  else
+    avgpool2_bwd_kernel<1, false><<<grid_for(total, 256, h->cu_count), 256, 0, s>>>((const float*)dy, (float*)dx, planes,
+                                                                                    xs.h, xs.w);
+  DLWP_LAUNCH_CHECK("avgpool2_bwd_kernel");
   return DLWP_OK;
 }
 

@@ -327,6 +327,8 @@ class Executor(object):
                     ops.pad2d(src, d, out=dst)
             elif op.kind == 'maxpool':
                 ops.maxpool2(src, out=dst)
+            elif op.kind == 'avgpool':
+                ops.avgpool2(src, out=dst)
             elif op.kind == 'upsample':
                 ops.upsample2(src, out=dst)
             elif op.kind == 'copy':
@@ -531,7 +533,7 @@ class Executor(object):
                 'upsample': _lib.OP_UPSAMPLE2, 'copy': _lib.OP_COPYCH, 'lstm': _lib.OP_LSTM_GATES,
                 'phasew': _lib.OP_PHASE_WEIGHTS, 'd2s': _lib.OP_DEPTH2SPACE, 'rowconv': _lib.OP_ROWCONV2D,
                 'bn': _lib.OP_BATCHNORM, 'dense': _lib.OP_DENSE, 'scale': _lib.OP_SCALE, 'act': _lib.OP_ACTIVATION,
-                'merge': _lib.OP_MERGE}
+                'merge': _lib.OP_MERGE, 'avgpool': _lib.OP_AVGPOOL2}
         arr = (_lib.Op * len(self.plan.ops))()
         for k, (op, d) in enumerate(zip(self.plan.ops, self._descriptors())):
             o = arr[k]
@@ -587,7 +589,7 @@ class Executor(object):
                 o.aux[0] = f_i if (f_i >= 0 and op.role == 'head') else _lib.BUF_NONE
                 o.aux[1] = ops.SCALE_KINDS[self.transform[op.role].kind]
                 o.aux[2] = 0 if op.role == 'head' else 1
-            elif op.kind == 'maxpool':
+            elif op.kind in ('maxpool', 'avgpool'):
                 o.aux[0] = _lib.BF16 if op.src in self._bf16 else _lib.F32
             elif op.kind == 'pad':
                 o.pad = d

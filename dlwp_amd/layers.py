@@ -732,6 +732,31 @@ class MaxPooling2D(Layer):
         return (s[0], s[1] // 2, s[2] // 2)
 
 
+class AveragePooling2D(Layer):
+    """keras.layers.AveragePooling2D(2): 2x2 / stride 2 / 'valid' (the reference's average-pooling U-Net, examples/validate.py:35-44).
+    An odd last row / column belongs to no window.  No weights, no state."""
+
+    def __init__(self, pool_size=(2, 2), strides=None, padding='valid', data_format=None, **kwargs):
+        super(AveragePooling2D, self).__init__(**kwargs)
+        ps = (pool_size, pool_size) if isinstance(pool_size, (int, np.integer)) else tuple(pool_size)
+        st = ps if strides is None else ((strides, strides) if isinstance(strides, (int, np.integer)) else tuple(strides))
+        if tuple(ps) != (2, 2) or tuple(st) != (2, 2) or padding != 'valid':
+            raise NotImplementedError("AveragePooling2D: only pool_size=2, strides=2, padding='valid' is implemented")
+        self.pool_size, self.strides, self.padding = (2, 2), (2, 2), 'valid'
+        self.data_format = normalize_data_format(data_format)
+        if self.data_format != 'channels_first':
+            raise NotImplementedError("AveragePooling2D: data_format='channels_first' is required")
+
+    def compute_output_shape(self, s):
+        return (s[0], s[1] // 2, s[2] // 2)
+
+    def get_config(self):
+        cfg = super(AveragePooling2D, self).get_config()
+        cfg.update({'pool_size': self.pool_size, 'strides': self.strides, 'padding': self.padding,
+                    'data_format': self.data_format})
+        return cfg
+
+
 class UpSampling2D(Layer):
     """keras.layers.UpSampling2D(2), nearest (examples/train.py:191,201)."""
 

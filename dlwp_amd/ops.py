@@ -300,6 +300,32 @@ def maxpool2_bwd(x, dy):
     return dx
 
 
+def avgpool2(x, out=None):
+    """keras AveragePooling2D(2): ((a + b) + (c + d)) * 0.25 per 2x2 window, float32 or bfloat16 storage (dlwp_avgpool2_fwd)."""
+    _check_act(x, out)
+    n, c, h, w = x.shape
+    y = out if out is not None else torch.empty((n, c, h // 2, w // 2), dtype=x.dtype, device=x.device)
+    if y.dtype != x.dtype:
+        raise ValueError('avgpool2: input %s and output %s storage differ' % (x.dtype, y.dtype))
+    if y.numel() != n * c * (h // 2) * (w // 2):
+        raise ValueError('avgpool2: output %r for an input %r' % (tuple(y.shape), tuple(x.shape)))
+    _lib.check(_lib.lib.dlwp_avgpool2_fwd(_lib.handle(_dev(x)), _ptr(x), _ptr(y), Shape4(n, c, h, w), storage_code(x),
+                                          _stream(x)))
+    return y
+
+
+def avgpool2_bwd(dy, shape, out=None):
+    """dx of the given (n, c, h, w) shape from dy (n, c, h//2, w//2): every element written, an odd last row / column +0."""
+    _check_f32(dy, out)
+    n, c, h, w = (int(v) for v in shape)
+    if dy.numel() != n * c * (h // 2) * (w // 2) or (out is not None and out.numel() != n * c * h * w):
+        raise ValueError('avgpool2_bwd: gradient %r for an input %r' % (tuple(dy.shape), (n, c, h, w)))
+    dx = out if out is not None else torch.empty((n, c, h, w), dtype=dy.dtype, device=dy.device)
+    _lib.check(_lib.lib.dlwp_avgpool2_bwd(_lib.handle(_dev(dy)), _ptr(dy), _ptr(dx), Shape4(n, c, h, w), _lib.F32,
+                                          _stream(dy)))
+    return dx
+
+
 def upsample2(x, out=None):
     _check_f32(x)
     n, c, h, w = x.shape

@@ -65,8 +65,8 @@ class View(object):
 
 
 class PlanOp(object):
-    """One launch.  kind in {'conv','rowconv','pad','maxpool','upsample','copy','lstm','phasew','d2s','bn','dense','dropout',
-    'scale','act','merge'}."""
+    """One launch.  kind in {'conv','rowconv','pad','maxpool','avgpool','upsample','copy','lstm','phasew','d2s','bn','dense',
+    'dropout','scale','act','merge'}."""
 
     def __init__(self, kind, src, dst, xs, **kw):
         self.kind, self.src, self.dst = kind, src, dst
@@ -191,13 +191,13 @@ class Plan(object):
     def bf16_buffers(self):
         """Scratch buffers that may be stored as bfloat16 (config 4: bf16 activations between the layers): written by a
         convolution (Conv2D output, ConvLSTM2D gate pre-activations), by the ConvLSTM2D cell update (the h sequence) or
-        by a max-pooling of such a buffer, and read only by convolutions / max-pooling / the cell update.  Model inputs
+        by a max- or average-pooling of such a buffer, and read only by convolutions / pooling / the cell update.  Model inputs
         and outputs, the ConvLSTM2D cell state, and anything a copy / pad / up-sampling kernel touches stay float32."""
         ok = {}
         for op in self.ops:
             for b, role in ((op.src, 'r'), (op.dst, 'w')):
                 if b >= 0:
-                    ok[b] = ok.get(b, True) and op.kind in ('conv', 'maxpool', 'lstm') and not (role == 'w' and op.out_d2s)
+                    ok[b] = ok.get(b, True) and op.kind in ('conv', 'maxpool', 'avgpool', 'lstm') and not (role == 'w' and op.out_d2s)
             if op.kind == 'merge':                                                # (float32 kernels)
                 for b in op.aux:
                     if b >= 0:
@@ -217,10 +217,10 @@ class Plan(object):
         while changed:                  # a pooled copy is bf16 only if its source is (and vice versa)
             changed = False
             for op in self.ops:
-                if op.kind == 'maxpool' and op.src >= 0 and op.dst >= 0 and ok.get(op.src, False) != ok.get(op.dst, False):
+                if op.kind in ('maxpool', 'avgpool') and op.src >= 0 and op.dst >= 0 and ok.get(op.src, False) != ok.get(op.dst, False):
                     ok[op.src] = ok[op.dst] = False
                     changed = True
-                if op.kind == 'maxpool' and (op.src < 0 or op.dst < 0):
+                if op.kind in ('maxpool', 'avgpool') and (op.src < 0 or op.dst < 0):
                     for b in (op.src, op.dst):
                         if b >= 0 and ok.get(b, False):
                             ok[b] = False
@@ -592,6 +592,24 @@ def build_plan(inputs, outputs, inference=False, fuse_d2s=True, fuse_lstm=False,
                 views[t.uid] = View(v.buf, 0, c, c, h2, w2)
             else:
                 views[t.uid] = v.copy(src_mode=SRC_MAXPOOL2 if isinstance(lay, L.MaxPooling2D) else SRC_UPSAMPLE2)
+        elif isinstance(lay, L.AveragePooling2D):
+            # keras AveragePooling2D(2) (csrc/halo.hip): always one launch of its own on a whole stored buffer -- anything lazy in
+            # front is materialised, a channel window is extracted first -- into a new buffer or the model's output slot.  Never a
+            # lazy source mode and never a convolution's epilogue: the convolution kernels know max-pooling only.
+            v = ins[0]
+            if v.shape is not None:
+                raise NotImplementedError('%s on a reshaped tensor' % lay.name)
+            v = materialize(v)
+            if not v.full:
+                v = materialize(v, dst=plan.new_buffer(*v.logical))
+            h2, w2 = v.h // 2, v.w // 2
+            if outs:
+                dst = OUT(outs[0])
+                plan.output_store[outs[0]] = (v.c, h2, w2)
+            else:
+                dst = plan.new_buffer(v.c, h2, w2)
+            emit(PlanOp('avgpool', v.buf, dst, (v.c, v.h, v.w), out_c_total=v.c, out_shape=(v.c, h2, w2)))
+            views[t.uid] = View(dst, 0, v.c, v.c, h2, w2)
         elif isinstance(lay, L.ChannelSlice):
             v = ins[0]
             if v.shape is not None:

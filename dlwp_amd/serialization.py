@@ -56,7 +56,7 @@ def _layer_config(lay):
         cfg.update(data_format=lay.data_format)
     elif isinstance(lay, L.Dropout):       # (the seed the masks are keyed with: a loaded model continues the same sequence)
         cfg.update(rate=lay.rate, seed=lay.mask_seed)
-    elif isinstance(lay, (L.MaxPooling2D, L.UpSampling2D)):
+    elif isinstance(lay, (L.MaxPooling2D, L.AveragePooling2D, L.UpSampling2D)):
         cfg.update(data_format=lay.data_format)
     elif isinstance(lay, L.Reshape):
         cfg.update(target_shape=list(lay.target_shape))
@@ -220,7 +220,7 @@ def _keras_layer_spec(lay):
         c.update(data_format=lay.data_format)
     elif isinstance(lay, L.Dropout):       # (the seed the masks are keyed with: a loaded model continues the same sequence)
         c.update(rate=lay.rate, noise_shape=None, seed=lay.mask_seed)
-    elif isinstance(lay, L.MaxPooling2D):
+    elif isinstance(lay, (L.MaxPooling2D, L.AveragePooling2D)):
         c.update(pool_size=[2, 2], padding='valid', strides=[2, 2], data_format=lay.data_format)
     elif isinstance(lay, L.UpSampling2D):
         c.update(size=[2, 2], data_format=lay.data_format, interpolation='nearest')

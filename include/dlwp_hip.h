@@ -528,6 +528,17 @@ int dlwp_maxpool2_bwd (dlwp_handle_t, const void* x, const void* dy, void* dx, d
 int dlwp_upsample2_fwd(dlwp_handle_t, const void* x, void* y, dlwp_shape4 xs, int dtype, void* stream);
 int dlwp_upsample2_bwd(dlwp_handle_t, const void* dy, void* dx, dlwp_shape4 xs, int dtype, void* stream);
 
+/* ---- keras AveragePooling2D(2) standalone: 2x2 / stride 2 / 'valid', x (n, c, h, w) -> y (n, c, h/2, w/2).  A window
+ *      a b / c d gives ((a + b) + (c + d)) * 0.25f in float32; with DLWP_BF16 storage the same expression on the widened values,
+ *      rounded to nearest-even once at the store.  An odd last row / column belongs to no window.  The backward (DLWP_F32; xs =
+ *      shape of dx, dy is (n, c, h/2, w/2)) WRITES every element of dx -- 0.25f * dy inside a window, +0 on an odd last row /
+ *      column -- and needs no x.  n == 0 is a no-op; a map of one row or column pools to an empty tensor (y / dy may be null; the
+ *      backward still zero-fills dx).  Access width by w and the pointers: w % 4 == 0 with 16-byte aligned x / dx and 8-byte
+ *      aligned y / dy: two windows per thread; w even with 8-byte aligned x / dx: one window, 8-byte accesses; else scalar.  All
+ *      routes give the same bits.                                                                                              */
+int dlwp_avgpool2_fwd (dlwp_handle_t, const void* x, void* y, dlwp_shape4 xs, int dtype, void* stream);   /* DLWP_F32 | DLWP_BF16 */
+int dlwp_avgpool2_bwd (dlwp_handle_t, const void* dy, void* dx, dlwp_shape4 xs, int dtype, void* stream); /* DLWP_F32 */
+
 /* ---- slice_layer (custom.py:675-692) / keras concatenate(axis=1): copy c channels between buffers of different
  *      channel counts.  src (n, src_c_total, h, w) channels [src_off, src_off+c) -> dst channels [dst_off, dst_off+c). */
 int dlwp_copy_channels(dlwp_handle_t, const void* src, void* dst, int n, int c, int hw, int src_c_off, int src_c_total,
@@ -763,6 +774,7 @@ int dlwp_scale_inv(dlwp_handle_t, const void* x, void* y, const void* shift, con
                                    * aux[0..2] = the bits of alpha, max_value, theta (floats)                               */
 #define DLWP_OP_MERGE     13      /* dlwp_merge_fwd: src = the first source, aux[0..2] = the others | -1000, dst, xs as above;
                                    * conv.act = DLWP_MERGE_*                                                                */
+#define DLWP_OP_AVGPOOL2  14      /* dlwp_avgpool2_fwd: src, dst, xs = (n, c, h, w) of src; aux[0] = storage dtype of both tensors */
 typedef struct {
   int kind;                 /* DLWP_OP_*                                                                */
   int src, dst;             /* buffer indices                                                              */
@@ -773,7 +785,7 @@ typedef struct {
   int aux[4];               /* DLWP_OP_LSTM_GATES: src = zx, dst = h buffer (window conv.out_c_off/out_c_total), xs =
                              * (n, F, h, w), aux = {zh | -1000, c_prev | -1000, c_out, rec_act + 256 * (h buffer stored as
                              * bfloat16) + 512 * (zx / zh stored as bfloat16)}, conv.act = activation.
-                             * DLWP_OP_CONV2D / DLWP_OP_MAXPOOL2: aux[0] = storage dtype of this op's tensors (DLWP_F32,
+                             * DLWP_OP_CONV2D / DLWP_OP_MAXPOOL2 / DLWP_OP_AVGPOOL2: aux[0] = storage dtype of this op's tensors (DLWP_F32,
                              * DLWP_BF16 or DLWP_DTYPE_IO(in, out)); the rollout's own dtype describes state and series.
                              * DLWP_OP_CONV2D with conv.lstm_f > 0 (dlwp_convlstm_conv_fwd): dst = h buffer, aux[1..3] =
                              * {z_add | -1000, c_prev | -1000, c_out}                                                  */
