@@ -38,6 +38,7 @@ OP_SCALE = 11
 OP_ACTIVATION = 12
 OP_MERGE = 13
 OP_AVGPOOL2 = 14
+OP_BILINEAR2 = 15
 ELT_RELU, ELT_ELU, ELT_SELU, ELT_SIGMOID, ELT_HARD_SIGMOID, ELT_SOFTPLUS, ELT_SOFTSIGN, ELT_TANH = 0, 1, 2, 3, 4, 5, 6, 7   # dlwp_activation kinds
 MERGE_ADD, MERGE_SUBTRACT, MERGE_MULTIPLY, MERGE_AVERAGE, MERGE_MAXIMUM, MERGE_MINIMUM = 0, 1, 2, 3, 4, 5            # dlwp_merge kinds
 SCALE_STANDARD, SCALE_MINMAX = 0, 1                 # dlwp_scale kinds
@@ -261,6 +262,8 @@ _sig('dlwp_avgpool2_fwd', [_vp, _vp, _vp, Shape4, _i, _vp])
 _sig('dlwp_avgpool2_bwd', [_vp, _vp, _vp, Shape4, _i, _vp])
 _sig('dlwp_upsample2_fwd', [_vp, _vp, _vp, Shape4, _i, _vp])
 _sig('dlwp_upsample2_bwd', [_vp, _vp, _vp, Shape4, _i, _vp])
+_sig('dlwp_upsample2_bilinear_fwd', [_vp, _vp, _vp, Shape4, _i, _vp])
+_sig('dlwp_upsample2_bilinear_bwd', [_vp, _vp, _vp, Shape4, _i, _vp])
 _sig('dlwp_convlstm_gates', [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp])
 _sig('dlwp_convlstm_conv_fwd', [_vp] * 9 + [Shape4, _P(Conv2d), _i, _vp])
 _sig('dlwp_convlstm_conv_supported', [_vp, Shape4, _P(Conv2d), _i])

@@ -561,6 +561,11 @@ class BackwardPass(object):
         if c.op.src != P.STATE_IN:
             self.book.deposit(c.op.src, 0, c.src.shape[1], ops.upsample2_bwd(c.gD))
 
+    def _bilinear(self, c):
+        """UpSampling2D(2, interpolation='bilinear'): the adjoint of the interpolation in gather form, written in one pass."""
+        if c.op.src != P.STATE_IN:
+            self.book.deposit(c.op.src, 0, c.src.shape[1], ops.upsample2_bilinear_bwd(c.gD, c.src.shape))
+
     adjoints = {'d2s': _d2s, 'conv': _conv, 'rowconv': _rowconv, 'dense': _dense, 'dropout': _dropout, 'bn': _bn,
                 'lstm': _lstm, 'copy': _copy, 'pad': _pad, 'maxpool': _maxpool, 'avgpool': _avgpool, 'upsample': _upsample,
-                'act': _act, 'merge': _merge}
+                'bilinear': _bilinear, 'act': _act, 'merge': _merge}

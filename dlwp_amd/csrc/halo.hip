@@ -4,6 +4,7 @@
 //                  ZeroPadding2D -- one pass instead of the reference's 2-3 concat copies per layer
 //   pad2d_bwd      adjoint (halo fold-back), gather form, deterministic
 //   maxpool2 / upsample2 fwd+bwd   keras MaxPooling2D(2) / UpSampling2D(2)  (examples/train.py:171,181,191,201)
+//   upsample2_bilinear fwd+bwd     keras UpSampling2D(2, interpolation='bilinear')
 //   copy_channels  slice_layer (custom.py:675-692) / keras concatenate(axis=1)
 //   series_merge_time  the final reshape/transpose of predict_timeseries (DLWP/model/models.py:294-300)
 //
@@ -737,6 +738,150 @@ __global__ __launch_bounds__(256) void upsample2_bwd_kernel(const float* __restr
 }
 
 // ------------------------------------------------------------------------------------------------------------------ //
+// 2x bilinear up-sampling (keras UpSampling2D(2, interpolation='bilinear') = tf.image.resize_bilinear, align_corners=False,
+// no half-pixel centres): even outputs copy the source, odd outputs are a + (b - a) * 0.5f of the two neighbours, the last one
+// clamped onto itself; rows first, then columns.  Every operation is rounded on its own on every route, so the routes agree to
+// the bit.  ROUTE: 2 = W even, a thread takes two source columns (8-byte accesses on x / dx, 16-byte on y / dy); 1 = one source
+// element with 8-byte (even, odd) accesses on y / dy; 0 = scalar.  The host picks it from W and the pointers: a row of y / dy
+// starts at a multiple of 2W floats, a row of x / dx at a multiple of W.
+// ------------------------------------------------------------------------------------------------------------------ //
+// the three operations stay apart: a contracted a + d * 0.5f would round once
+__device__ __forceinline__ float mid2(float a, float b) {
+#pragma clang fp contract(off)
+  const float d = b - a;
+  const float m = d * 0.5f;
+  return a + m;
+}
+
+template <int ROUTE>
+__global__ __launch_bounds__(256) void upsample2_bilinear_fwd_kernel(const float* __restrict__ x, float* __restrict__ y,
+                                                                     long long planes, int H, int W) {
+  const int V = ROUTE == 2 ? 2 : 1, Wt = W / V, W2 = 2 * W;
+  const long long total = planes * H * Wt;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+    const int j = V * (int)(i % Wt);
+    const long long q = i / Wt;   // = p*H + r
+    const int r = (int)(q % H);
+    const float* s = x + q * W;
+    const float* sn = r + 1 < H ? s + W : s;   // the row below, the last row clamped onto itself
+    float* d = y + (2 * q) * W2 + 2 * j;
+    if (ROUTE == 2) {
+      const int j2 = j + 2 < W ? j + 2 : W - 1;
+      const f32x2 a = *(const f32x2*)(s + j), c = *(const f32x2*)(sn + j);
+      const float a2 = s[j2], c2 = sn[j2];
+      const float ta = mid2(a[0], a[1]), tb = mid2(a[1], a2), ua = mid2(c[0], c[1]), ub = mid2(c[1], c2);
+      const f32x4 top = {a[0], ta, a[1], tb};
+      const f32x4 bot = {mid2(a[0], c[0]), mid2(ta, ua), mid2(a[1], c[1]), mid2(tb, ub)};
+      *(f32x4*)d = top;
+      *(f32x4*)(d + W2) = bot;
+    } else {
+      const int j1 = j + 1 < W ? j + 1 : W - 1;
+      const float a = s[j], b = s[j1], c = sn[j], e = sn[j1];
+      const float t = mid2(a, b), u = mid2(c, e);
+      const float lo0 = mid2(a, c), lo1 = mid2(t, u);
+      if (ROUTE == 1) {
+        const f32x2 top = {a, t}, bot = {lo0, lo1};
+        *(f32x2*)d = top;
+        *(f32x2*)(d + W2) = bot;
+      } else {
+        d[0] = a;
+        d[1] = t;
+        d[W2] = lo0;
+        d[W2 + 1] = lo1;
+      }
+    }
+  }
+}
+
+// bfloat16 storage: the float32 expression on the widened values, every output rounded to nearest-even once at the store (the
+// even/even output is the source's own bits).  PAIR = y is 4-byte aligned: an (even, odd) pair is one 32-bit store.
+__device__ __forceinline__ float bf16_widen(unsigned short v) { return __builtin_bit_cast(float, (unsigned)v << 16); }
+__device__ __forceinline__ unsigned bf16_round(float v) { return (unsigned)__builtin_bit_cast(unsigned short, (__bf16)v); }
+
+template <bool PAIR>
+__global__ __launch_bounds__(256) void upsample2_bilinear_fwd_bf16_kernel(const unsigned short* __restrict__ x,
+                                                                          unsigned short* __restrict__ y, long long planes,
+                                                                          int H, int W) {
+  const int W2 = 2 * W;
+  const long long total = planes * H * W;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+    const int j = (int)(i % W);
+    const long long q = i / W;
+    const int r = (int)(q % H);
+    const unsigned short* s = x + q * W;
+    const unsigned short* sn = r + 1 < H ? s + W : s;
+    const int j1 = j + 1 < W ? j + 1 : W - 1;
+    const float a = bf16_widen(s[j]), b = bf16_widen(s[j1]), c = bf16_widen(sn[j]), e = bf16_widen(sn[j1]);
+    const float t = mid2(a, b), u = mid2(c, e);
+    const unsigned o00 = s[j], o01 = bf16_round(t), o10 = bf16_round(mid2(a, c)), o11 = bf16_round(mid2(t, u));
+    unsigned short* d = y + (2 * q) * W2 + 2 * j;
+    if (PAIR) {
+      *(unsigned*)d = o00 | (o01 << 16);
+      *(unsigned*)(d + W2) = o10 | (o11 << 16);
+    } else {
+      d[0] = (unsigned short)o00;
+      d[1] = (unsigned short)o01;
+      d[W2] = (unsigned short)o10;
+      d[W2 + 1] = (unsigned short)o11;
+    }
+  }
+}
+
+// the adjoint along one axis: (v0 + 0.5f * vm) + 0.5f * vp.  The vm term is absent at the first source position (skipped, not
+// added as a zero); at the last one vp has weight 1, because the clamped odd output is the source itself.
+__device__ __forceinline__ float bilinear_gather(float vm, float v0, float vp, bool first, bool last) {
+#pragma clang fp contract(off)
+  float s = v0;
+  if (!first) {
+    const float m = 0.5f * vm;
+    s = s + m;
+  }
+  const float e = last ? vp : 0.5f * vp;
+  return s + e;
+}
+
+// gather form: one lane per dx element (ROUTE 2: per pair), which reads the 3x3 block of dy around (2i, 2j) -- the three row
+// sums first, then their combination down the column -- and writes it once.  No atomics, no x.
+template <int ROUTE>
+__global__ __launch_bounds__(256) void upsample2_bilinear_bwd_kernel(const float* __restrict__ dy, float* __restrict__ dx,
+                                                                     long long planes, int H, int W) {
+  const int V = ROUTE == 2 ? 2 : 1, Wt = W / V, W2 = 2 * W;
+  const long long total = planes * H * Wt;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+    const int j = V * (int)(i % Wt);
+    const long long q = i / Wt;   // = p*H + r
+    const int r = (int)(q % H);
+    const bool top = r == 0, bottom = r == H - 1, left = j == 0;
+    const float* g = dy + (2 * q) * W2 + 2 * j;   // dy[2r][2j]
+    float t0[3], t1[3];                             // row sums of the rows 2r-1, 2r, 2r+1 (t1: the second column of a pair)
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      t0[k] = t1[k] = 0.f;
+      if (k == 0 && top) continue;
+      const float* row = g + (k - 1) * W2;
+      const float vm = left ? 0.f : row[-1];
+      if (ROUTE == 2) {
+        const f32x4 v = *(const f32x4*)row;
+        t0[k] = bilinear_gather(vm, v[0], v[1], left, false);          // (W even: the first of a pair is never the last column)
+        t1[k] = bilinear_gather(v[1], v[2], v[3], false, j + 1 == W - 1);
+      } else if (ROUTE == 1) {
+        const f32x2 v = *(const f32x2*)row;
+        t0[k] = bilinear_gather(vm, v[0], v[1], left, j == W - 1);
+      } else {
+        t0[k] = bilinear_gather(vm, row[0], row[1], left, j == W - 1);
+      }
+    }
+    const float o0 = bilinear_gather(t0[0], t0[1], t0[2], top, bottom);
+    if (ROUTE == 2) {
+      const f32x2 o = {o0, bilinear_gather(t1[0], t1[1], t1[2], top, bottom)};
+      *(f32x2*)(dx + q * W + j) = o;
+    } else {
+      dx[i] = o0;
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------ //
 // strided block copies
 // ------------------------------------------------------------------------------------------------------------------ //
 // copy runs of `run` contiguous floats; run (a, b, c) starts at src + a*s_sa + b*s_sb + c*s_sc and lands at
@@ -1064,6 +1209,73 @@ int dlwp_upsample2_bwd(dlwp_handle_t h, const void* dy, void* dx, dlwp_shape4 xs
     upsample2_bwd_kernel<<<grid_for(total, 256, h->cu_count), 256, 0, (hipStream_t)stream>>>((const float*)dy, (float*)dx,
                                                                                              planes, xs.h, xs.w);
   DLWP_LAUNCH_CHECK("upsample2_bwd_kernel");
+  return DLWP_OK;
+}
+
+// access route of the float32 bilinear kernels: `wide` is the tensor at output resolution (y / dy, rows of 2W floats), `narrow`
+// the one at source resolution (x / dx).  2 = two source columns per thread (16-byte accesses on wide, 8-byte on narrow),
+// 1 = one source element with 8-byte (even, odd) accesses on wide, 0 = scalar.
+static inline int bilinear_route(int W, const void* wide, const void* narrow) {
+  if (W % 2 == 0 && aligned16(wide) && (((uintptr_t)narrow) & 7) == 0) return 2;
+  if ((((uintptr_t)wide) & 7) == 0) return 1;
+  return 0;
+}
+
+int dlwp_upsample2_bilinear_fwd(dlwp_handle_t h, const void* x, void* y, dlwp_shape4 xs, int dtype, void* stream) {
+  DLWP_TAPE(h, stream, dlwp_upsample2_bilinear_fwd, h, x, y, xs, dtype);
+  const bool x_ok = x && y;
+  const bool bf16 = dtype == DLWP_BF16;
+  if (bf16) dtype = DLWP_F32;  // the shared argument check knows fp32 only; this entry point also stores bf16
+  POOL_ARGS_OK("dlwp_upsample2_bilinear_fwd");
+  const long long planes = (long long)xs.n * xs.c;
+  const long long total = planes * xs.h * xs.w;
+  hipStream_t s = (hipStream_t)stream;
+  if (bf16) {
+    DLWP_CHECK_ARG(((((uintptr_t)x) | ((uintptr_t)y)) & 1) == 0, "dlwp_upsample2_bilinear_fwd: bfloat16 tensors must be 2-byte aligned");
+    if ((((uintptr_t)y) & 3) == 0)
+      upsample2_bilinear_fwd_bf16_kernel<true><<<grid_for(total, 256, h->cu_count), 256, 0, s>>>(
+          (const unsigned short*)x, (unsigned short*)y, planes, xs.h, xs.w);
+    else
+      upsample2_bilinear_fwd_bf16_kernel<false><<<grid_for(total, 256, h->cu_count), 256, 0, s>>>(
+          (const unsigned short*)x, (unsigned short*)y, planes, xs.h, xs.w);
+    DLWP_LAUNCH_CHECK("upsample2_bilinear_fwd_bf16_kernel");
+    return DLWP_OK;
+  }
+  DLWP_CHECK_ARG(((((uintptr_t)x) | ((uintptr_t)y)) & 3) == 0, "dlwp_upsample2_bilinear_fwd: float32 tensors must be 4-byte aligned");
+  const int route = bilinear_route(xs.w, y, x);
+  if (route == 2)
+    upsample2_bilinear_fwd_kernel<2><<<grid_for(total / 2, 256, h->cu_count), 256, 0, s>>>((const float*)x, (float*)y, planes,
+                                                                                           xs.h, xs.w);
+  else if (route == 1)
+    upsample2_bilinear_fwd_kernel<1><<<grid_for(total, 256, h->cu_count), 256, 0, s>>>((const float*)x, (float*)y, planes, xs.h,
+                                                                                       xs.w);
+  else
+    upsample2_bilinear_fwd_kernel<0><<<grid_for(total, 256, h->cu_count), 256, 0, s>>>((const float*)x, (float*)y, planes, xs.h,
+                                                                                       xs.w);
+  DLWP_LAUNCH_CHECK("upsample2_bilinear_fwd_kernel");
+  return DLWP_OK;
+}
+
+// xs = shape of dx (the low-resolution tensor); dy is (n, c, 2h, 2w).  Every element of dx is written by one lane.
+int dlwp_upsample2_bilinear_bwd(dlwp_handle_t h, const void* dy, void* dx, dlwp_shape4 xs, int dtype, void* stream) {
+  DLWP_TAPE(h, stream, dlwp_upsample2_bilinear_bwd, h, dy, dx, xs, dtype);
+  const bool x_ok = dy && dx;
+  POOL_ARGS_OK("dlwp_upsample2_bilinear_bwd");
+  DLWP_CHECK_ARG(((((uintptr_t)dy) | ((uintptr_t)dx)) & 3) == 0, "dlwp_upsample2_bilinear_bwd: float32 tensors must be 4-byte aligned");
+  const long long planes = (long long)xs.n * xs.c;
+  const long long total = planes * xs.h * xs.w;
+  hipStream_t s = (hipStream_t)stream;
+  const int route = bilinear_route(xs.w, dy, dx);
+  if (route == 2)
+    upsample2_bilinear_bwd_kernel<2><<<grid_for(total / 2, 256, h->cu_count), 256, 0, s>>>((const float*)dy, (float*)dx, planes,
+                                                                                           xs.h, xs.w);
+  else if (route == 1)
+    upsample2_bilinear_bwd_kernel<1><<<grid_for(total, 256, h->cu_count), 256, 0, s>>>((const float*)dy, (float*)dx, planes,
+                                                                                       xs.h, xs.w);
+  else
+    upsample2_bilinear_bwd_kernel<0><<<grid_for(total, 256, h->cu_count), 256, 0, s>>>((const float*)dy, (float*)dx, planes,
+                                                                                       xs.h, xs.w);
+  DLWP_LAUNCH_CHECK("upsample2_bilinear_bwd_kernel");
   return DLWP_OK;
 }
 

@@ -54,6 +54,8 @@ int enqueue_op(dlwp_handle_t h, const dlwp_op& op, const void* src, void* dst, c
       return dlwp_maxpool2_fwd(h, src, dst, op.xs, op.aux[0], (void*)s);
     case DLWP_OP_AVGPOOL2:
       return dlwp_avgpool2_fwd(h, src, dst, op.xs, op.aux[0], (void*)s);
+    case DLWP_OP_BILINEAR2:
+      return dlwp_upsample2_bilinear_fwd(h, src, dst, op.xs, op.aux[0], (void*)s);
     case DLWP_OP_UPSAMPLE2:
       return dlwp_upsample2_fwd(h, src, dst, op.xs, dtype, (void*)s);
     case DLWP_OP_DEPTH2SPACE:

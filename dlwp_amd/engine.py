@@ -331,6 +331,8 @@ class Executor(object):
                 ops.avgpool2(src, out=dst)
             elif op.kind == 'upsample':
                 ops.upsample2(src, out=dst)
+            elif op.kind == 'bilinear':
+                ops.upsample2_bilinear(src, out=dst)
             elif op.kind == 'copy':
                 if tuple(dst.shape[2:]) != tuple(src.shape[2:]) and dst.numel() == src.numel():
                     dst = dst.view(src.shape)          # a Reshape relabelled the target: the same contiguous block
@@ -533,7 +535,7 @@ class Executor(object):
                 'upsample': _lib.OP_UPSAMPLE2, 'copy': _lib.OP_COPYCH, 'lstm': _lib.OP_LSTM_GATES,
                 'phasew': _lib.OP_PHASE_WEIGHTS, 'd2s': _lib.OP_DEPTH2SPACE, 'rowconv': _lib.OP_ROWCONV2D,
                 'bn': _lib.OP_BATCHNORM, 'dense': _lib.OP_DENSE, 'scale': _lib.OP_SCALE, 'act': _lib.OP_ACTIVATION,
-                'merge': _lib.OP_MERGE, 'avgpool': _lib.OP_AVGPOOL2}
+                'merge': _lib.OP_MERGE, 'avgpool': _lib.OP_AVGPOOL2, 'bilinear': _lib.OP_BILINEAR2}
         arr = (_lib.Op * len(self.plan.ops))()
         for k, (op, d) in enumerate(zip(self.plan.ops, self._descriptors())):
             o = arr[k]
@@ -589,7 +591,7 @@ class Executor(object):
                 o.aux[0] = f_i if (f_i >= 0 and op.role == 'head') else _lib.BUF_NONE
                 o.aux[1] = ops.SCALE_KINDS[self.transform[op.role].kind]
                 o.aux[2] = 0 if op.role == 'head' else 1
-            elif op.kind in ('maxpool', 'avgpool'):
+            elif op.kind in ('maxpool', 'avgpool', 'bilinear'):
                 o.aux[0] = _lib.BF16 if op.src in self._bf16 else _lib.F32
             elif op.kind == 'pad':
                 o.pad = d

@@ -758,20 +758,30 @@ class AveragePooling2D(Layer):
 
 
 class UpSampling2D(Layer):
-    """keras.layers.UpSampling2D(2), nearest (examples/train.py:191,201)."""
+    """keras.layers.UpSampling2D(2): 'nearest' (examples/train.py:191,201) or 'bilinear' (Keras 2.2.4's
+    tf.image.resize_bilinear with align_corners=False and no half-pixel centres: even outputs copy the source, odd outputs are the
+    mean of two neighbours, the last one clamped).  No weights, no state."""
 
     def __init__(self, size=(2, 2), data_format=None, interpolation='nearest', **kwargs):
         super(UpSampling2D, self).__init__(**kwargs)
         sz = (size, size) if isinstance(size, (int, np.integer)) else tuple(size)
-        if tuple(sz) != (2, 2) or interpolation != 'nearest':
-            raise NotImplementedError("UpSampling2D: only size=2, interpolation='nearest' is implemented")
+        if interpolation not in ('nearest', 'bilinear'):
+            raise ValueError('`interpolation` argument should be one of `"nearest"` or `"bilinear"`.')
+        if tuple(sz) != (2, 2):
+            raise NotImplementedError('UpSampling2D: only size=2 is implemented')
         self.size = (2, 2)
+        self.interpolation = interpolation
         self.data_format = normalize_data_format(data_format)
         if self.data_format != 'channels_first':
             raise NotImplementedError("UpSampling2D: data_format='channels_first' is required")
 
     def compute_output_shape(self, s):
         return (s[0], s[1] * 2, s[2] * 2)
+
+    def get_config(self):
+        cfg = super(UpSampling2D, self).get_config()
+        cfg.update({'size': self.size, 'data_format': self.data_format, 'interpolation': self.interpolation})
+        return cfg
 
 
 class Reshape(Layer):

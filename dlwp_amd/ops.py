@@ -344,6 +344,33 @@ def upsample2_bwd(dy):
     return dx
 
 
+def upsample2_bilinear(x, out=None):
+    """keras UpSampling2D(2, interpolation='bilinear'): even outputs copy x, odd ones are a + (b - a) * 0.5 of two neighbours
+    (the last clamped), rows then columns; float32 or bfloat16 storage (dlwp_upsample2_bilinear_fwd)."""
+    _check_act(x, out)
+    n, c, h, w = x.shape
+    y = out if out is not None else torch.empty((n, c, 2 * h, 2 * w), dtype=x.dtype, device=x.device)
+    if y.dtype != x.dtype:
+        raise ValueError('upsample2_bilinear: input %s and output %s storage differ' % (x.dtype, y.dtype))
+    if y.numel() != n * c * 2 * h * 2 * w:
+        raise ValueError('upsample2_bilinear: output %r for an input %r' % (tuple(y.shape), tuple(x.shape)))
+    _lib.check(_lib.lib.dlwp_upsample2_bilinear_fwd(_lib.handle(_dev(x)), _ptr(x), _ptr(y), Shape4(n, c, h, w), storage_code(x),
+                                                    _stream(x)))
+    return y
+
+
+def upsample2_bilinear_bwd(dy, shape, out=None):
+    """dx of the given (n, c, h, w) shape from dy (n, c, 2h, 2w): the adjoint in gather form, every element written once."""
+    _check_f32(dy, out)
+    n, c, h, w = (int(v) for v in shape)
+    if dy.numel() != n * c * 2 * h * 2 * w or (out is not None and out.numel() != n * c * h * w):
+        raise ValueError('upsample2_bilinear_bwd: gradient %r for an input %r' % (tuple(dy.shape), (n, c, h, w)))
+    dx = out if out is not None else torch.empty((n, c, h, w), dtype=dy.dtype, device=dy.device)
+    _lib.check(_lib.lib.dlwp_upsample2_bilinear_bwd(_lib.handle(_dev(dy)), _ptr(dy), _ptr(dx), Shape4(n, c, h, w), _lib.F32,
+                                                    _stream(dy)))
+    return dx
+
+
 def copy_channels(src, dst, c, src_c_off=0, dst_c_off=0):
     _check_f32(src, dst)
     n, sc, h, w = src.shape

@@ -65,8 +65,8 @@ class View(object):
 
 
 class PlanOp(object):
-    """One launch.  kind in {'conv','rowconv','pad','maxpool','avgpool','upsample','copy','lstm','phasew','d2s','bn','dense',
-    'dropout','scale','act','merge'}."""
+    """One launch.  kind in {'conv','rowconv','pad','maxpool','avgpool','upsample','bilinear','copy','lstm','phasew','d2s','bn',
+    'dense','dropout','scale','act','merge'}."""
 
     def __init__(self, kind, src, dst, xs, **kw):
         self.kind, self.src, self.dst = kind, src, dst
@@ -191,13 +191,14 @@ class Plan(object):
     def bf16_buffers(self):
         """Scratch buffers that may be stored as bfloat16 (config 4: bf16 activations between the layers): written by a
         convolution (Conv2D output, ConvLSTM2D gate pre-activations), by the ConvLSTM2D cell update (the h sequence) or
-        by a max- or average-pooling of such a buffer, and read only by convolutions / pooling / the cell update.  Model inputs
-        and outputs, the ConvLSTM2D cell state, and anything a copy / pad / up-sampling kernel touches stay float32."""
+        by a max- or average-pooling or a bilinear up-sampling of such a buffer, and read only by convolutions / pooling /
+        bilinear up-sampling / the cell update.  Model inputs and outputs, the ConvLSTM2D cell state, and anything a copy / pad /
+        nearest up-sampling kernel touches stay float32."""
         ok = {}
         for op in self.ops:
             for b, role in ((op.src, 'r'), (op.dst, 'w')):
                 if b >= 0:
-                    ok[b] = ok.get(b, True) and op.kind in ('conv', 'maxpool', 'avgpool', 'lstm') and not (role == 'w' and op.out_d2s)
+                    ok[b] = ok.get(b, True) and op.kind in ('conv', 'maxpool', 'avgpool', 'bilinear', 'lstm') and not (role == 'w' and op.out_d2s)
             if op.kind == 'merge':                                                # (float32 kernels)
                 for b in op.aux:
                     if b >= 0:
@@ -214,13 +215,13 @@ class Plan(object):
                 both = ok.get(op.src, False) and ok.get(op.aux[0], False)
                 ok[op.src] = ok[op.aux[0]] = both
         changed = True
-        while changed:                  # a pooled copy is bf16 only if its source is (and vice versa)
+        while changed:                  # a pooled / interpolated copy is bf16 only if its source is (and vice versa)
             changed = False
             for op in self.ops:
-                if op.kind in ('maxpool', 'avgpool') and op.src >= 0 and op.dst >= 0 and ok.get(op.src, False) != ok.get(op.dst, False):
+                if op.kind in ('maxpool', 'avgpool', 'bilinear') and op.src >= 0 and op.dst >= 0 and ok.get(op.src, False) != ok.get(op.dst, False):
                     ok[op.src] = ok[op.dst] = False
                     changed = True
-                if op.kind in ('maxpool', 'avgpool') and (op.src < 0 or op.dst < 0):
+                if op.kind in ('maxpool', 'avgpool', 'bilinear') and (op.src < 0 or op.dst < 0):
                     for b in (op.src, op.dst):
                         if b >= 0 and ok.get(b, False):
                             ok[b] = False
@@ -574,6 +575,25 @@ def build_plan(inputs, outputs, inference=False, fuse_d2s=True, fuse_lstm=False,
                 views[t.uid] = View(hbuf, 0, t_len * f, t_len * f, ho, wo, shape=(t_len, f, ho, wo))
             else:
                 views[t.uid] = View(hbuf, (t_len - 1) * f, f, t_len * f, ho, wo)
+        elif isinstance(lay, L.UpSampling2D) and lay.interpolation == 'bilinear':
+            # keras UpSampling2D(2, interpolation='bilinear') (csrc/halo.hip): always one launch of its own on a whole stored
+            # buffer -- anything lazy in front is materialised, a channel window is extracted first -- into a new buffer or the
+            # model's output slot.  Never SRC_UPSAMPLE2, never a restated decoder layer and never a convolution's epilogue: the
+            # convolution kernels know nearest up-sampling only.
+            v = ins[0]
+            if v.shape is not None:
+                raise NotImplementedError('%s on a reshaped tensor' % lay.name)
+            v = materialize(v)
+            if not v.full:
+                v = materialize(v, dst=plan.new_buffer(*v.logical))
+            h2, w2 = 2 * v.h, 2 * v.w
+            if outs:
+                dst = OUT(outs[0])
+                plan.output_store[outs[0]] = (v.c, h2, w2)
+            else:
+                dst = plan.new_buffer(v.c, h2, w2)
+            emit(PlanOp('bilinear', v.buf, dst, (v.c, v.h, v.w), out_c_total=v.c, out_shape=(v.c, h2, w2)))
+            views[t.uid] = View(dst, 0, v.c, v.c, h2, w2)
         elif isinstance(lay, (L.MaxPooling2D, L.UpSampling2D)):
             v = ins[0]
             if v.shape is not None:

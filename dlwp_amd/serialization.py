@@ -58,6 +58,8 @@ def _layer_config(lay):
         cfg.update(rate=lay.rate, seed=lay.mask_seed)
     elif isinstance(lay, (L.MaxPooling2D, L.AveragePooling2D, L.UpSampling2D)):
         cfg.update(data_format=lay.data_format)
+        if getattr(lay, 'interpolation', 'nearest') != 'nearest':      # (a nearest layer's spec stays as it always was)
+            cfg.update(interpolation=lay.interpolation)
     elif isinstance(lay, L.Reshape):
         cfg.update(target_shape=list(lay.target_shape))
     elif isinstance(lay, L.ChannelSlice):
@@ -223,7 +225,7 @@ def _keras_layer_spec(lay):
     elif isinstance(lay, (L.MaxPooling2D, L.AveragePooling2D)):
         c.update(pool_size=[2, 2], padding='valid', strides=[2, 2], data_format=lay.data_format)
     elif isinstance(lay, L.UpSampling2D):
-        c.update(size=[2, 2], data_format=lay.data_format, interpolation='nearest')
+        c.update(size=[2, 2], data_format=lay.data_format, interpolation=lay.interpolation)
     elif isinstance(lay, L.Reshape):
         c.update(target_shape=list(lay.target_shape))
     elif isinstance(lay, L.ChannelSlice):

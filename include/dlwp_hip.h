@@ -539,6 +539,19 @@ int dlwp_upsample2_bwd(dlwp_handle_t, const void* dy, void* dx, dlwp_shape4 xs, 
 int dlwp_avgpool2_fwd (dlwp_handle_t, const void* x, void* y, dlwp_shape4 xs, int dtype, void* stream);   /* DLWP_F32 | DLWP_BF16 */
 int dlwp_avgpool2_bwd (dlwp_handle_t, const void* dy, void* dx, dlwp_shape4 xs, int dtype, void* stream); /* DLWP_F32 */
 
+/* ---- keras UpSampling2D(2, interpolation='bilinear') standalone: x (n, c, h, w) -> y (n, c, 2h, 2w), the legacy
+ *      tf.image.resize_bilinear scaling (align_corners=False, no half-pixel centres).  In float32, every operation rounded once,
+ *      rows first: r[i][2j] = x[i][j] (bits copied), r[i][2j+1] = a + (b - a) * 0.5f with a = x[i][j], b = x[i][min(j+1, w-1)];
+ *      then y[2i] = r[i], y[2i+1][s] = t + (u - t) * 0.5f with t = r[i][s], u = r[min(i+1, h-1)][s].  With DLWP_BF16 storage the
+ *      same expression on the widened values, rounded to nearest-even once at the store.  The backward (DLWP_F32; xs = shape of
+ *      dx, dy is (n, c, 2h, 2w)) is the adjoint in gather form: along one axis g(v)[j] = (v[2j] + 0.5f*v[2j-1]) + 0.5f*v[2j+1],
+ *      without the v[2j-1] term at j = 0 and with weight 1 on v[2w-1] at j = w-1; dx = g down the columns of g along the rows of
+ *      dy.  It WRITES every element of dx once, without atomics.  n == 0 is a no-op.  Access width by w and the pointers: w even
+ *      with 16-byte aligned y / dy and 8-byte aligned x / dx: two source columns per thread; 8-byte aligned y / dy: (even, odd)
+ *      pairs; else scalar.  All routes give the same bits.                                                                      */
+int dlwp_upsample2_bilinear_fwd(dlwp_handle_t, const void* x, void* y, dlwp_shape4 xs, int dtype, void* stream);   /* DLWP_F32 | DLWP_BF16 */
+int dlwp_upsample2_bilinear_bwd(dlwp_handle_t, const void* dy, void* dx, dlwp_shape4 xs, int dtype, void* stream); /* DLWP_F32 */
+
 /* ---- slice_layer (custom.py:675-692) / keras concatenate(axis=1): copy c channels between buffers of different
  *      channel counts.  src (n, src_c_total, h, w) channels [src_off, src_off+c) -> dst channels [dst_off, dst_off+c). */
 int dlwp_copy_channels(dlwp_handle_t, const void* src, void* dst, int n, int c, int hw, int src_c_off, int src_c_total,
@@ -775,6 +788,7 @@ int dlwp_scale_inv(dlwp_handle_t, const void* x, void* y, const void* shift, con
 #define DLWP_OP_MERGE     13      /* dlwp_merge_fwd: src = the first source, aux[0..2] = the others | -1000, dst, xs as above;
                                    * conv.act = DLWP_MERGE_*                                                                */
 #define DLWP_OP_AVGPOOL2  14      /* dlwp_avgpool2_fwd: src, dst, xs = (n, c, h, w) of src; aux[0] = storage dtype of both tensors */
+#define DLWP_OP_BILINEAR2 15      /* dlwp_upsample2_bilinear_fwd: src, dst, xs = (n, c, h, w) of src; aux[0] = storage dtype of both tensors */
 typedef struct {
   int kind;                 /* DLWP_OP_*                                                                */
   int src, dst;             /* buffer indices                                                              */
@@ -785,7 +799,7 @@ typedef struct {
   int aux[4];               /* DLWP_OP_LSTM_GATES: src = zx, dst = h buffer (window conv.out_c_off/out_c_total), xs =
                              * (n, F, h, w), aux = {zh | -1000, c_prev | -1000, c_out, rec_act + 256 * (h buffer stored as
                              * bfloat16) + 512 * (zx / zh stored as bfloat16)}, conv.act = activation.
-                             * DLWP_OP_CONV2D / DLWP_OP_MAXPOOL2 / DLWP_OP_AVGPOOL2: aux[0] = storage dtype of this op's tensors (DLWP_F32,
+                             * DLWP_OP_CONV2D / DLWP_OP_MAXPOOL2 / DLWP_OP_AVGPOOL2 / DLWP_OP_BILINEAR2: aux[0] = storage dtype of this op's tensors (DLWP_F32,
                              * DLWP_BF16 or DLWP_DTYPE_IO(in, out)); the rollout's own dtype describes state and series.
                              * DLWP_OP_CONV2D with conv.lstm_f > 0 (dlwp_convlstm_conv_fwd): dst = h buffer, aux[1..3] =
                              * {z_add | -1000, c_prev | -1000, c_out}                                                  */
