@@ -320,6 +320,10 @@ _sig('dlwp_xchg_allreduce_adam', [_vp, _vp, _sz, _sz, _vp, _vp, _vp] + [ctypes.c
 _sig('dlwp_xchg_status', [_vp, _P(_i)])
 _sig('dlwp_xchg_info', [_vp, _P(_i), _P(_i)])
 _sig('dlwp_xchg_destroy', [_vp])
+_sig('dlwp_verify_error_workspace', [_vp, _i, _i], _sz)
+_sig('dlwp_verify_error_sums', [_vp, _vp, ctypes.c_longlong, ctypes.c_longlong, _i, _vp, ctypes.c_longlong, ctypes.c_longlong, _i,
+                                _i, _i, _i, _i, ctypes.c_longlong, _vp, _vp, _sz, _vp])
+_sig('dlwp_verify_nanmean_samples', [_vp, _vp, _i, ctypes.c_longlong, _vp, _vp])
 
 
 def check(rc):

@@ -1447,3 +1447,51 @@ def merge_bwd(kind, xs, dy, outs=None, want=None):
     _lib.check(_lib.lib.dlwp_merge_bwd(_lib.handle(_dev(dy)), p[0], p[1], p[2], p[3], _ptr(dy), q[0], q[1], q[2], q[3],
                                        dy.numel(), d, _stream(dy)))
     return outs
+
+
+def verify_extent(strides, leads, count0, count_dec, groups, run):
+    """Elements an operand of dlwp_verify_error_sums must hold: one past the last offset a lead with pairs addresses (0: none)."""
+    ls, ss, shift = (int(v) for v in strides)
+    need = 0
+    for f in range(int(leads)):
+        cnt = int(count0) - f * int(count_dec)
+        if cnt <= 0:
+            break
+        need = max(need, f * ls + (cnt - 1 + f * shift) * ss + int(groups) * int(run))
+    return need
+
+
+def verify_error_sums(a, a_strides, b, b_strides, leads, count0, count_dec, groups, run):
+    """include/dlwp_hip.h: dlwp_verify_error_sums.  a, b: contiguous float32 device tensors read as flat arrays through
+    x_strides = (lead_stride, sample_stride, shift) in elements.  Returns a NEW (leads, groups, 3) float64 device tensor: sum d^2,
+    sum |d| and the pairs counted (d = a - b; NaN pairs skipped) per lead and group, enqueued on the current stream."""
+    _check_f32(a, b)
+    d = _dev(a)
+    if _dev(b) != d:
+        raise ValueError('verify_error_sums: operands on devices %d and %d' % (d, _dev(b)))
+    leads, count0, count_dec, groups, run = int(leads), int(count0), int(count_dec), int(groups), int(run)
+    if leads < 1 or groups < 1 or run < 1 or count_dec < 0 or min(a_strides) < 0 or min(b_strides) < 0:
+        raise ValueError('verify_error_sums: leads, groups, run must be >= 1; strides, shifts and count_dec >= 0')
+    for name, t, st in (('a', a, a_strides), ('b', b, b_strides)):
+        need = verify_extent(st, leads, count0, count_dec, groups, run)
+        if need > t.numel():
+            raise ValueError('verify_error_sums: operand %s holds %d elements, the strides address %d' % (name, t.numel(), need))
+    h = _lib.handle(d)
+    ws = torch.empty(max(int(_lib.lib.dlwp_verify_error_workspace(h, leads, groups)), 8), dtype=torch.uint8, device=a.device)
+    sums = torch.empty((leads, groups, 3), dtype=torch.float64, device=a.device)
+    _lib.check(_lib.lib.dlwp_verify_error_sums(h, _ptr(a), int(a_strides[0]), int(a_strides[1]), int(a_strides[2]),
+                                               _ptr(b), int(b_strides[0]), int(b_strides[1]), int(b_strides[2]),
+                                               leads, count0, count_dec, groups, run, _ptr(sums), _ptr(ws), ws.numel(), _stream(a)))
+    return sums
+
+
+def verify_nanmean_samples(x):
+    """include/dlwp_hip.h: dlwp_verify_nanmean_samples.  x: (count, ...) contiguous float32 device tensor -> a NEW float32 tensor
+    of x.shape[1:], the NaN-skipping mean over the first axis (float64 sums in sample order; NaN where no sample is finite-or-inf)."""
+    _check_f32(x)
+    if x.dim() < 2 or x.shape[0] < 1 or x[0].numel() < 1:
+        raise ValueError('verify_nanmean_samples: expected (count >= 1, ...) with a non-empty row, got %r' % (tuple(x.shape),))
+    mean = torch.empty(tuple(x.shape[1:]), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib.dlwp_verify_nanmean_samples(_lib.handle(_dev(x)), _ptr(x), int(x.shape[0]), mean.numel(), _ptr(mean),
+                                                    _stream(x)))
+    return mean

@@ -946,6 +946,37 @@ int dlwp_xchg_status(dlwp_xchg_t, int* timed_out);
 int dlwp_xchg_info(dlwp_xchg_t, int* memory_kind, int* max_blocks);
 int dlwp_xchg_destroy(dlwp_xchg_t);
 
+/* ---- forecast verification on the device (csrc/verify.hip; DLWP/model/verify.py:17-102: forecast_error, persistence_error,
+ *      climo_error of the series predict_timeseries(..., return_device=True) leaves in HBM).  dlwp_verify_error_sums reduces the
+ *      pairs of two float32 operands described by strides (all in ELEMENTS, all >= 0): at lead f < leads there are
+ *      count_f = max(count0 - f * count_dec, 0) pairs of sample rows, row i of operand x starts at
+ *      x + f * x_lead_stride + (i + f * x_shift) * x_sample_stride, and a sample row is groups x run contiguous floats.
+ *      d = a - b is rounded in float32 (as numpy does on float32 arrays), widened to float64; a NaN d is skipped and not counted
+ *      (nanmean; inf - inf included), infinities follow IEEE.  sums (device, (leads, groups, 3) float64) <- sum d^2, sum |d|,
+ *      pairs counted; a lead without pairs launches no work and reports three zeros.  With row = groups * run, as
+ *      (lead_stride, sample_stride, shift):
+ *        forecast_error, valid (F, N, ..):  a = forecast (N*row, row, 0), b = valid (N*row, row, 0), count0 = N,  count_dec = 0
+ *        forecast_error, valid (Nv, ..):    a = valid (0, row, 1),        b = forecast (N*row, row, 0), count0 = Nv, count_dec = 1
+ *        persistence_error:                 a = valid (0, row, 1),        b = predictors (0, row, 0),   count0 = Nv, count_dec = 1
+ *        climo_error:                       a = valid (0, row, 0),        b = mean (0, 0, 0),           count0 = Nv, count_dec = 1
+ *      Two launches with a fixed tree (per-thread float64 sums and a 64-bit count; lanes, waves through LDS, one partial per
+ *      block in ws; a second kernel sums the partials of each (lead, group) cell), no atomics, no host synchronisation: repeated
+ *      calls give identical bits.  16-byte loads when run, all four strides are multiples of 4 and a, b are 16-byte aligned,
+ *      scalar loads otherwise (the two routes need not agree in the last float64 bits).  The grid is sized from the handle's
+ *      CU count: max(1, 8 * CUs / cells) blocks per cell over the cells of the leads that have pairs, and
+ *      dlwp_verify_error_workspace returns leads * groups * B * 24 bytes with B = ceil(8 * CUs / (leads * groups)), enough for
+ *      every count0 / count_dec (a NULL handle counts 256 CUs).  Refused without a launch: sizes < 1, negative strides,
+ *      null pointers, more than 2^20 cells, a workspace smaller than the launch needs, a null handle (checked in that order).
+ *      The caller guarantees that every addressed element exists (dlwp_amd.ops.verify_error_sums checks it).
+ *      dlwp_verify_nanmean_samples: x (count, row) contiguous -> mean (row) float32, the NaN-skipping mean over samples,
+ *      accumulated in float64 in sample order; a column without a non-NaN sample stores NaN.
+ *      Neither is part of a training step: both mark a recording tape foreign.                                             */
+size_t dlwp_verify_error_workspace(dlwp_handle_t, int leads, int groups);
+int dlwp_verify_error_sums(dlwp_handle_t, const void* a, long long a_lead_stride, long long a_sample_stride, int a_shift,
+                           const void* b, long long b_lead_stride, long long b_sample_stride, int b_shift, int leads, int count0,
+                           int count_dec, int groups, long long run, void* sums, void* ws, size_t ws_bytes, void* stream);
+int dlwp_verify_nanmean_samples(dlwp_handle_t, const void* x, int count, long long row, void* mean, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
