@@ -8,7 +8,15 @@
 // fixed tree -- lanes, waves through LDS, one partial per block, a second kernel over the partials of a cell -- without atomics
 // and without a "last block" scheme: repeated launches give identical bits.  No launch kernel reads a size from the device and
 // the entry points never synchronise.  Every offset is 64-bit: one lead of a 256-member series is 16 M floats, the series 3.6 GB.
+//
+// The second half of the reference module (DLWP/model/verify.py:105-273) adds three entry points with the same conventions:
+// dlwp_verify_label_nanmean (the mean per calendar month over the whole predictor record: a block owns a label, a chunk of that
+// label's sample list and a column tile, a second launch adds the chunks in order), dlwp_verify_label_error_sums (the error of
+// selected rows against that table: one cell of the tree above, with an optional anomaly output) and dlwp_gather_rows_fill (the
+// verification windows: rows copied by index, NaN rows where the record has no state).
 #include "common.h"
+
+#include <type_traits>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -162,6 +170,217 @@ inline int verify_bpc_cap(dlwp_handle_t h, long long cells) {
 
 inline bool mult4(long long v) { return (v & 3) == 0; }
 
+// ---- means per label (calendar month) over a long record, and the error of selected rows against such a table -------------------- //
+constexpr int VERIFY_MAX_LABELS = 64;
+
+struct LabelMeanArgs {
+  const float* x;
+  const int* index;                      // sample indices grouped by label, ascending inside a label
+  long long row;
+  int count, split, tiles;
+  int off[VERIFY_MAX_LABELS + 1];        // list of label l: index[off[l] .. off[l + 1])
+};
+
+__device__ __forceinline__ void nan_add(float v, double& s, int& n) {
+  const bool ok = v == v;
+  s += ok ? (double)v : 0.0;
+  n += ok ? 1 : 0;
+}
+
+// stage 1.  A block owns (label, chunk k of that label's list, column tile): list positions [len * k / split, len * (k + 1) / split),
+// 256 threads x (VEC: four adjacent columns, one 16-byte load per sample; else one).  The sample index is the same in every lane;
+// four rows are in flight per thread and are added in list order.  An index outside the record is skipped, never read.
+template <bool VEC>
+__global__ __launch_bounds__(VERIFY_THREADS) void verify_label_partial_kernel(LabelMeanArgs p, double* __restrict__ psum,
+                                                                              int* __restrict__ pcnt) {
+  constexpr int W = VEC ? 4 : 1;
+  const unsigned cell = blockIdx.x / (unsigned)p.tiles;
+  const unsigned tile = blockIdx.x - cell * (unsigned)p.tiles;
+  const unsigned label = cell / (unsigned)p.split, chunk = cell - label * (unsigned)p.split;
+  const long long c = ((long long)tile * VERIFY_THREADS + threadIdx.x) * W;
+  if (c >= p.row) return;
+  const long long lo = p.off[label], len = p.off[label + 1] - lo;
+  long long i = lo + len * chunk / p.split;
+  const long long end = lo + len * (chunk + 1) / p.split;
+  const float* px = p.x + c;
+  double s[W];
+  int n[W];
+#pragma unroll
+  for (int k = 0; k < W; ++k) s[k] = 0.0, n[k] = 0;
+  const float qnan = __builtin_nanf("");
+  for (; i + 4 <= end; i += 4) {
+    float v[4][W];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int r = p.index[i + u];
+      const bool in = (unsigned)r < (unsigned)p.count;
+      const float* q = px + (long long)(in ? r : 0) * p.row;
+      if (VEC) {
+        const f32x4 t = *reinterpret_cast<const f32x4*>(q);
+#pragma unroll
+        for (int k = 0; k < W; ++k) v[u][k] = in ? t[k] : qnan;
+      } else {
+        v[u][0] = in ? q[0] : qnan;
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+      for (int k = 0; k < W; ++k) nan_add(v[u][k], s[k], n[k]);
+  }
+  for (; i < end; ++i) {
+    const int r = p.index[i];
+    if ((unsigned)r >= (unsigned)p.count) continue;
+    const float* q = px + (long long)r * p.row;
+    if (VEC) {
+      const f32x4 t = *reinterpret_cast<const f32x4*>(q);
+#pragma unroll
+      for (int k = 0; k < W; ++k) nan_add(t[k], s[k], n[k]);
+    } else {
+      nan_add(q[0], s[0], n[0]);
+    }
+  }
+  const long long o = (long long)cell * p.row + c;
+#pragma unroll
+  for (int k = 0; k < W; ++k) psum[o + k] = s[k], pcnt[o + k] = n[k];
+}
+
+// stage 2: one thread per (label, column) adds the chunks in chunk order, divides once and rounds once
+__global__ __launch_bounds__(VERIFY_THREADS) void verify_label_final_kernel(const double* __restrict__ psum, const int* __restrict__ pcnt,
+                                                                            long long row, int split, int tiles,
+                                                                            float* __restrict__ mean) {
+  const unsigned label = blockIdx.x / (unsigned)tiles;
+  const long long c = (long long)(blockIdx.x - label * (unsigned)tiles) * VERIFY_THREADS + threadIdx.x;
+  if (c >= row) return;
+  double s = 0.0;
+  long long n = 0;
+  for (int k = 0; k < split; ++k) {
+    const long long o = ((long long)label * split + k) * row + c;
+    s += psum[o];
+    n += pcnt[o];
+  }
+  mean[(long long)label * row + c] = n > 0 ? (float)(s / (double)n) : __builtin_nanf("");
+}
+
+struct LabelErrorArgs {
+  const float* x;
+  const int* rows;
+  const int* labels;
+  const float* table;
+  float* anomaly;                        // may be null
+  long long row;                         // floats of a row
+  int count_x, m, n_labels, bpc;
+  long long step_row, step_col;
+};
+
+// d = x[rows[i]] - table[labels[i]] over i < m as ONE cell of verify_partial_kernel's tree: units, steps and partials as there.  A row
+// index or label outside its range makes the whole row NaN (skipped, not counted, NaN in `anomaly`) and is never used as an address.
+template <bool VEC>
+__global__ __launch_bounds__(VERIFY_THREADS) void verify_label_error_kernel(LabelErrorArgs p, double* __restrict__ partial) {
+  const long long units = VEC ? p.row / 4 : p.row;
+  const long long total = (long long)p.m * units;
+  const long long step = (long long)p.bpc * VERIFY_THREADS;
+  const float qnan = __builtin_nanf("");
+  double s2 = 0.0, s1 = 0.0;
+  unsigned long long n = 0;
+  long long q = (long long)blockIdx.x * VERIFY_THREADS + threadIdx.x;
+  long long i = q / units, col = q - i * units;
+  for (; q < total; q += step) {
+    const int r = p.rows[i], l = p.labels[i];
+    const bool in = (unsigned)r < (unsigned)p.count_x && (unsigned)l < (unsigned)p.n_labels;
+    const float* px = p.x + (long long)(in ? r : 0) * p.row;
+    const float* pt = p.table + (long long)(in ? l : 0) * p.row;
+    if (VEC) {
+      const f32x4 x = *reinterpret_cast<const f32x4*>(px + 4 * col);
+      const f32x4 y = *reinterpret_cast<const f32x4*>(pt + 4 * col);
+      f32x4 d;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const float xv = in ? x[k] : qnan;
+        d[k] = xv - y[k];
+        pair_add(xv, y[k], s2, s1, n);
+      }
+      if (p.anomaly) *reinterpret_cast<f32x4*>(p.anomaly + i * p.row + 4 * col) = d;
+    } else {
+      const float xv = in ? px[col] : qnan, yv = pt[col];
+      pair_add(xv, yv, s2, s1, n);
+      if (p.anomaly) p.anomaly[i * p.row + col] = xv - yv;
+    }
+    i += p.step_row;
+    col += p.step_col;
+    if (col >= units) {
+      col -= units;
+      ++i;
+    }
+  }
+  double nd = (double)n;
+  block_sum3(s2, s1, nd);
+  if (threadIdx.x == 0) {
+    double* o = partial + 3ll * blockIdx.x;
+    o[0] = s2;
+    o[1] = s1;
+    o[2] = nd;
+  }
+}
+
+// ---- dst[j] = src[rows[j]], a quiet NaN row where rows[j] is no row of src -------------------------------------------------------- //
+struct GatherArgs {
+  const unsigned* src;
+  const long long* rows;
+  unsigned* dst;
+  long long src_rows, row, total;        // total: n * units
+  long long step, step_row, step_col;
+};
+
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+// bits are moved as unsigned words, so NaN payloads survive.  A thread carries four units (one 16-byte word or one float each) per
+// turn: the four loads are issued before the four stores.
+template <bool VEC>
+__global__ __launch_bounds__(VERIFY_THREADS) void gather_rows_fill_kernel(GatherArgs p) {
+  typedef typename std::conditional<VEC, u32x4, unsigned>::type word_t;
+  constexpr int W = VEC ? 4 : 1;
+  const long long units = p.row / W;
+  const unsigned qnan = 0x7fc00000u;
+  long long q = (long long)blockIdx.x * VERIFY_THREADS + threadIdx.x;
+  long long j = q / units, col = q - j * units;
+  while (q < p.total) {
+    word_t v[4];
+    long long at[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      at[u] = -1;
+      if (q < p.total) {
+        const long long r = p.rows[j];
+        const bool in = r >= 0 && r < p.src_rows;
+        const word_t t = *reinterpret_cast<const word_t*>(p.src + (in ? r : 0) * p.row + col * W);
+        v[u] = in ? t : (word_t)qnan;
+        at[u] = j * p.row + col * W;
+      }
+      q += p.step;
+      j += p.step_row;
+      col += p.step_col;
+      if (col >= units) {
+        col -= units;
+        ++j;
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (at[u] >= 0) *reinterpret_cast<word_t*>(p.dst + at[u]) = v[u];
+  }
+}
+
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+inline long long label_tiles(long long row, bool vec) { return ((vec ? row / 4 : row) + VERIFY_THREADS - 1) / VERIFY_THREADS; }
+
+// chunks per label: 8 blocks per CU over the (label, column tile) cells, and never more chunks than samples
+inline int label_split(dlwp_handle_t h, int count, long long row, int n_labels, bool vec) {
+  const long long cap = verify_bpc_cap(h, (long long)n_labels * label_tiles(row, vec));
+  return (int)(cap < count ? cap : count);
+}
+
 }  // namespace
 
 extern "C" {
@@ -234,6 +453,115 @@ int dlwp_verify_nanmean_samples(dlwp_handle_t h, const void* x, int count, long 
   const unsigned grid = (unsigned)((row + VERIFY_THREADS - 1) / VERIFY_THREADS);
   verify_nanmean_kernel<<<grid, VERIFY_THREADS, 0, (hipStream_t)stream>>>((const float*)x, count, row, (float*)mean);
   DLWP_LAUNCH_CHECK("verify_nanmean_samples kernel");
+  return DLWP_OK;
+}
+
+size_t dlwp_verify_label_nanmean_workspace(dlwp_handle_t h, int count, long long row, int n_labels) {
+  if (count < 1 || row < 1 || n_labels < 1 || n_labels > VERIFY_MAX_LABELS) return 0;
+  // the 16-byte route has the fewer cells and therefore the larger split: enough for either route
+  const int split = label_split(h, count, row, n_labels, mult4(row));
+  return (size_t)n_labels * (size_t)split * (size_t)row * (sizeof(double) + sizeof(int));
+}
+
+int dlwp_verify_label_nanmean(dlwp_handle_t h, const void* x, int count, long long row, const int* offsets, const void* index,
+                              int n_labels, void* mean, void* ws, size_t ws_bytes, void* stream) {
+  DLWP_UNTAPED(dlwp_verify_label_nanmean);
+  DLWP_CHECK_ARG(count >= 1 && row >= 1, "dlwp_verify_label_nanmean: count %d and row %lld must be >= 1", count, row);
+  DLWP_CHECK_ARG(n_labels >= 1 && n_labels <= VERIFY_MAX_LABELS, "dlwp_verify_label_nanmean: n_labels %d, expected 1 .. %d", n_labels,
+                 VERIFY_MAX_LABELS);
+  DLWP_CHECK_ARG(x && offsets && index && mean && ws, "dlwp_verify_label_nanmean: null pointer");
+  DLWP_CHECK_ARG(offsets[0] == 0 && offsets[n_labels] == count,
+                 "dlwp_verify_label_nanmean: offsets must run from 0 to count %d, got %d .. %d", count, offsets[0], offsets[n_labels]);
+  for (int l = 0; l < n_labels; ++l)
+    DLWP_CHECK_ARG(offsets[l] <= offsets[l + 1], "dlwp_verify_label_nanmean: offsets decrease at label %d", l);
+  const bool vec = mult4(row) && aligned16(x);
+  const long long tiles = label_tiles(row, vec);
+  const int split = label_split(h, count, row, n_labels, vec);
+  const long long ftiles = label_tiles(row, false);
+  DLWP_CHECK_ARG((long long)n_labels * split * tiles < (1ll << 31) && n_labels * ftiles < (1ll << 31),
+                 "dlwp_verify_label_nanmean: row %lld too long", row);
+  const size_t cells = (size_t)n_labels * (size_t)split * (size_t)row;
+  const size_t ws_need = cells * (sizeof(double) + sizeof(int));
+  DLWP_CHECK_ARG(ws_bytes >= ws_need, "dlwp_verify_label_nanmean: workspace too small (%zu < %zu)", ws_bytes, ws_need);
+  DLWP_CHECK_ARG(((uintptr_t)ws & 7) == 0, "dlwp_verify_label_nanmean: workspace must be 8-byte aligned");
+  DLWP_CHECK_ARG(h, "dlwp_verify_label_nanmean: null handle");
+  LabelMeanArgs p;
+  p.x = (const float*)x;
+  p.index = (const int*)index;
+  p.row = row;
+  p.count = count, p.split = split, p.tiles = (int)tiles;
+  for (int l = 0; l <= VERIFY_MAX_LABELS; ++l) p.off[l] = offsets[l < n_labels ? l : n_labels];
+  double* psum = (double*)ws;
+  int* pcnt = (int*)(psum + cells);
+  hipStream_t s = (hipStream_t)stream;
+  const unsigned grid = (unsigned)((long long)n_labels * split * tiles);
+  if (vec)
+    verify_label_partial_kernel<true><<<grid, VERIFY_THREADS, 0, s>>>(p, psum, pcnt);
+  else
+    verify_label_partial_kernel<false><<<grid, VERIFY_THREADS, 0, s>>>(p, psum, pcnt);
+  verify_label_final_kernel<<<(unsigned)(n_labels * ftiles), VERIFY_THREADS, 0, s>>>(psum, pcnt, row, split, (int)ftiles, (float*)mean);
+  DLWP_LAUNCH_CHECK("verify_label_nanmean kernels");
+  return DLWP_OK;
+}
+
+int dlwp_verify_label_error_sums(dlwp_handle_t h, const void* x, int count_x, long long row, const void* rows, const void* labels, int m,
+                                 const void* table, int n_labels, void* anomaly, void* sums, void* ws, size_t ws_bytes, void* stream) {
+  DLWP_UNTAPED(dlwp_verify_label_error_sums);
+  DLWP_CHECK_ARG(count_x >= 1 && m >= 1 && row >= 1, "dlwp_verify_label_error_sums: count_x %d, m %d, row %lld must all be >= 1", count_x,
+                 m, row);
+  DLWP_CHECK_ARG(n_labels >= 1 && n_labels <= VERIFY_MAX_LABELS, "dlwp_verify_label_error_sums: n_labels %d, expected 1 .. %d", n_labels,
+                 VERIFY_MAX_LABELS);
+  DLWP_CHECK_ARG(x && rows && labels && table && sums && ws, "dlwp_verify_label_error_sums: null pointer");
+  const bool vec = mult4(row) && aligned16(x) && aligned16(table) && aligned16(anomaly);
+  const long long units = vec ? row / 4 : row;
+  const long long need = ((long long)m * units + VERIFY_THREADS - 1) / VERIFY_THREADS;
+  const long long cap = verify_bpc_cap(h, 1);
+  const int bpc = (int)(need < cap ? need : cap);
+  const size_t ws_need = (size_t)bpc * 3 * sizeof(double);
+  DLWP_CHECK_ARG(ws_bytes >= ws_need, "dlwp_verify_label_error_sums: workspace too small (%zu < %zu)", ws_bytes, ws_need);
+  DLWP_CHECK_ARG(h, "dlwp_verify_label_error_sums: null handle");
+  LabelErrorArgs p;
+  p.x = (const float*)x, p.rows = (const int*)rows, p.labels = (const int*)labels, p.table = (const float*)table;
+  p.anomaly = (float*)anomaly;
+  p.row = row;
+  p.count_x = count_x, p.m = m, p.n_labels = n_labels, p.bpc = bpc;
+  const long long step = (long long)bpc * VERIFY_THREADS;
+  p.step_row = step / units, p.step_col = step % units;
+  hipStream_t s = (hipStream_t)stream;
+  if (vec)
+    verify_label_error_kernel<true><<<(unsigned)bpc, VERIFY_THREADS, 0, s>>>(p, (double*)ws);
+  else
+    verify_label_error_kernel<false><<<(unsigned)bpc, VERIFY_THREADS, 0, s>>>(p, (double*)ws);
+  verify_final_kernel<<<1, 64, 0, s>>>((const double*)ws, bpc, 1, (double*)sums);
+  DLWP_LAUNCH_CHECK("verify_label_error_sums kernels");
+  return DLWP_OK;
+}
+
+int dlwp_gather_rows_fill(dlwp_handle_t h, const void* src, long long src_rows, long long row, const void* rows, long long n, void* dst,
+                          void* stream) {
+  DLWP_UNTAPED(dlwp_gather_rows_fill);
+  DLWP_CHECK_ARG(src_rows >= 1 && row >= 1 && n >= 0, "dlwp_gather_rows_fill: src_rows %lld, row %lld must be >= 1 and n %lld >= 0",
+                 src_rows, row, n);
+  DLWP_CHECK_ARG(n <= 0x7fffffffffffffffll / row / 4, "dlwp_gather_rows_fill: n %lld rows of %lld floats overflow", n, row);
+  if (n == 0) return DLWP_OK;
+  DLWP_CHECK_ARG(src && rows && dst, "dlwp_gather_rows_fill: null pointer");
+  DLWP_CHECK_ARG(h, "dlwp_gather_rows_fill: null handle");
+  const bool vec = mult4(row) && aligned16(src) && aligned16(dst);
+  const long long units = vec ? row / 4 : row;
+  GatherArgs p;
+  p.src = (const unsigned*)src, p.rows = (const long long*)rows, p.dst = (unsigned*)dst;
+  p.src_rows = src_rows, p.row = row, p.total = n * units;
+  // a block moves 4 x 256 units a turn
+  const long long need = (p.total + 4 * VERIFY_THREADS - 1) / (4 * VERIFY_THREADS);
+  const long long cap = verify_bpc_cap(h, 1);
+  const long long grid = need < cap ? need : cap;
+  p.step = grid * VERIFY_THREADS;
+  p.step_row = p.step / units, p.step_col = p.step % units;
+  if (vec)
+    gather_rows_fill_kernel<true><<<(unsigned)grid, VERIFY_THREADS, 0, (hipStream_t)stream>>>(p);
+  else
+    gather_rows_fill_kernel<false><<<(unsigned)grid, VERIFY_THREADS, 0, (hipStream_t)stream>>>(p);
+  DLWP_LAUNCH_CHECK("gather_rows_fill kernel");
   return DLWP_OK;
 }
 

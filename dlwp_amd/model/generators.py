@@ -15,6 +15,7 @@ Batch feed for fit_generator.
 """
 import ctypes
 import os
+import sys
 import threading
 
 import numpy as np
@@ -211,6 +212,11 @@ class DataGenerator(object):
             yield self[i]
 
 
+def _is_device_tensor(values):
+    torch = sys.modules.get('torch')
+    return torch is not None and isinstance(values, torch.Tensor) and values.is_cuda and values.dtype == torch.float32
+
+
 class LabeledArray(object):
     """The part of xarray.DataArray the series generator uses: `values`, `shape`, named dimensions with coordinate
     labels, `.sel(dim=[labels])`, `.isel(dim=index)`, `.load()`, and coordinates as attributes (`.sample.values` ...)."""
@@ -220,7 +226,8 @@ class LabeledArray(object):
             self.values = values
 
     def __init__(self, values, coords, dims):
-        self.values = np.asarray(values)
+        # a CUDA float32 tensor stays where it is (model.verify reduces it on the device); everything else becomes a numpy array
+        self.values = values if _is_device_tensor(values) else np.asarray(values)
         self.dims = tuple(dims)
         if len(self.dims) != self.values.ndim:
             raise ValueError('dims %r do not match an array of rank %d' % (self.dims, self.values.ndim))
@@ -284,9 +291,18 @@ class SeriesDataset(object):
     """A predictor file holding ONE continuous time series: `predictors` (sample, [time_step,] selection dims..., lat,
     lon) with coordinates sample (timestamps), lat, lon and the labels of the selection dimensions."""
 
-    def __init__(self, predictors, coords, dims):
+    def __init__(self, predictors, coords, dims, targets=None):
         self.predictors = predictors if isinstance(predictors, LabeledArray) else LabeledArray(predictors, coords, dims)
         self.dims = dict(zip(self.predictors.dims, self.predictors.shape))
+        if targets is not None:        # a file of samples (Preprocessor.data_to_samples) has them: verify.verification_from_samples
+            self.targets = targets if isinstance(targets, LabeledArray) else LabeledArray(targets, coords, dims)
+
+    def __getattr__(self, name):
+        """coordinates as attributes (`ds.sample.values`), as on the xarray Dataset"""
+        predictors = self.__dict__.get('predictors')
+        if predictors is not None and name in predictors.coords:
+            return LabeledArray._Coord(predictors.coords[name])
+        raise AttributeError(name)
 
     def load(self):
         return self

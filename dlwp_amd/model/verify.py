@@ -1,5 +1,5 @@
 """
-Forecast error measures of the validation scripts (reference DLWP/model/verify.py:17-102, called from
+Forecast error measures of the validation scripts (reference DLWP/model/verify.py, called from
 examples/validate.py / plot_forecasts.py on the output of predict_timeseries).
 
 Two paths, one definition:
@@ -20,6 +20,13 @@ Two paths, one definition:
   pairwise mean, and therefore not bit-equal to that one.
   The device path covers axis=None and the axis tuple that keeps the lead and the first inner axis ((0, 2, 3) for a 4-D
   `valid`, (1, 3, 4) for the per-lead form; any rank); every other `axis` runs the numpy code on downloaded arrays.
+
+The rest of the reference module (DLWP/model/verify.py:105-273) follows the same rule, on LabeledArray / SeriesDataset objects
+(model/generators.py) where the reference takes xarray objects: monthly_climo_error (the mean per calendar month over the whole
+record by dlwp_verify_label_nanmean, the anomaly of the validation times by dlwp_verify_label_error_sums),
+verification_from_samples / verification_from_series (one int64 row array from window_rows, executed by numpy take or by
+dlwp_gather_rows_fill with the same bits; verification_tensor keeps the result in HBM for forecast_error), and the two host
+reshapes predictors_to_time_series / add_metadata_to_forecast.  DESIGN.md 5.30 has the kernels and the measurements.
 
 A caveat of return_device=True: the tensor may alias the cached series buffer of the model's captured rollout, which the next
 rollout of that model overwrites -- verify it (or clone it) before rolling the model out again.
@@ -250,3 +257,238 @@ def climo_error(valid, n_fhour, method='mse', axis=None, device=None):
     n = valid.shape[0]
     mean = np.nanmean(valid, axis=0)
     return np.array([_error(valid[:n - f] - mean, method, axis) for f in range(n_fhour)])
+
+
+# -- month-aware climatology (reference DLWP/model/verify.py:105-132) --------------------------------------------------------------- #
+def _cuda_device(values, device):
+    """the device of the device path, or None for the host path"""
+    if isinstance(values, torch.Tensor):
+        _wants_device((('da', values),), device)
+        dev = _common_device([values.device], device)
+    elif device is None:
+        return None
+    else:
+        dev = _common_device([], device)
+    if dev.index is None:
+        dev = torch.device('cuda', torch.cuda.current_device())
+    return dev
+
+
+def _find_times(times, wanted):
+    """int64 positions of `wanted` in the time coordinate `times` (any order), -1 where a time is absent: np.searchsorted on the sorted
+    times plus an equality check"""
+    times, wanted = np.asarray(times), np.asarray(wanted)
+    if times.dtype.kind == 'M' and wanted.dtype.kind == 'M':
+        common = np.promote_types(times.dtype, wanted.dtype)
+        times, wanted = times.astype(common), wanted.astype(common)
+    if times.size == 0:
+        return np.full(wanted.shape, -1, np.int64)
+    order = np.argsort(times, kind='stable')
+    ordered = times[order]
+    pos = np.minimum(np.searchsorted(ordered, wanted), ordered.size - 1)
+    return np.where(ordered[pos] == wanted, order[pos], -1).astype(np.int64)
+
+
+def _months(times):
+    """calendar month - 1 of a datetime64 coordinate"""
+    times = np.asarray(times)
+    if times.dtype.kind != 'M':
+        raise TypeError('the time coordinate must be datetime64, got %s' % times.dtype)
+    return (times.astype('datetime64[M]').astype(np.int64) % 12).astype(np.int32)
+
+
+def label_nanmean_host(x, labels, n_labels):
+    """(n_labels,) + x.shape[1:] float32: per label the NaN-skipping mean of its rows, summed in float64 in sample order, divided once
+    and rounded once; NaN where a label has no non-NaN sample"""
+    out = np.full((n_labels,) + x.shape[1:], np.nan, np.float32)
+    for l in range(n_labels):
+        rows = np.flatnonzero(labels == l)
+        s, n = np.zeros(x.shape[1:], np.float64), np.zeros(x.shape[1:], np.int64)
+        for r in rows:
+            ok = ~np.isnan(x[r])
+            with np.errstate(invalid='ignore'):
+                s += np.where(ok, x[r], np.float32(0)).astype(np.float64)
+            n += ok
+        with np.errstate(divide='ignore', invalid='ignore'):
+            out[l] = np.where(n > 0, s / n, np.nan).astype(np.float32)
+    return out
+
+
+def monthly_climo_error(da, val_set, n_fhour=None, method='mse', return_da=False, device=None):
+    """Month-aware climatology error: the NaN-skipping mean per calendar month over ALL of `da` (a LabeledArray with a datetime64
+    'sample' or 'time' coordinate) is the forecast for the times in `val_set`; one number over everything, repeated n_fhour times if
+    that is given, and with return_da the anomaly da.sel(time=val_set) - climatology as a LabeledArray.
+    Host path (numpy values): the climatology in float64 rounded once to float32, d in float32, the final mean in float64.  Device
+    path (device='cuda', or da.values a CUDA float32 tensor): the record is uploaded once, dlwp_verify_label_nanmean and
+    dlwp_verify_label_error_sums reduce it there; only the month labels and the row indices are computed here."""
+    _check(method)
+    time_dim = 'sample' if 'sample' in da.dims else 'time'
+    ax = da.dims.index(time_dim)
+    times = np.asarray(da.coords[time_dim])
+    months = _months(times)
+    wanted = np.asarray(list(val_set) if not isinstance(val_set, np.ndarray) else val_set).reshape(-1)
+    rows = _find_times(times, wanted)
+    if wanted.size == 0 or (rows < 0).any():
+        raise KeyError('time(s) %r not found on dimension %r' % (wanted[rows < 0].tolist() if wanted.size else [], time_dim))
+    dev = _cuda_device(da.values, device)
+    if dev is None:
+        x = np.moveaxis(da.values, ax, 0)
+        if x.dtype != np.float32:
+            x = x.astype(np.float32)
+        climo = label_nanmean_host(x, months, 12)
+        with np.errstate(invalid='ignore'):
+            anomaly = x[rows] - climo[months[rows]]
+        ok = ~np.isnan(anomaly)
+        z = np.where(ok, anomaly, np.float32(0)).astype(np.float64)
+        count = int(ok.sum())
+        with np.errstate(over='ignore', invalid='ignore'):
+            total = float(np.abs(z).sum()) if method == 'mae' else float((z * z).sum())
+        me = total / count if count else float('nan')
+        if method == 'rmse':
+            me = float(np.sqrt(me))
+        anomaly = np.moveaxis(anomaly, 0, ax)
+    else:
+        from .. import ops
+        if not isinstance(da.values, torch.Tensor) and np.asarray(da.values).dtype != np.float32:
+            raise TypeError("'da' must be float32 on the device path, got %s" % np.asarray(da.values).dtype)
+        with torch.cuda.device(dev):
+            x = _to_device(da.values, dev)
+            if ax:
+                x = x.movedim(ax, 0).contiguous()
+            table = ops.verify_label_nanmean(x, months, 12)
+            out = ops.verify_label_error_sums(x, rows, months[rows], table, anomaly=return_da)
+            sums, anomaly = out if return_da else (out, None)
+            me = float(finish(sums.cpu().numpy().reshape(1, 1, 3), method, False)[0])
+            if return_da:
+                anomaly = anomaly.movedim(0, ax) if ax else anomaly
+                if not isinstance(da.values, torch.Tensor):
+                    anomaly = anomaly.cpu().numpy()
+    if n_fhour is not None:
+        me = np.array([me] * n_fhour)
+    if not return_da:
+        return me
+    from .generators import LabeledArray
+    coords = dict(da.coords)
+    coords[time_dim] = times[rows]
+    return me, LabeledArray(anomaly, coords, da.dims)
+
+
+# -- reshaping helpers (reference DLWP/model/verify.py:135-198) ---------------------------------------------------------------------- #
+def _meta_coord(meta_ds, name):
+    c = getattr(meta_ds, name)
+    return np.asarray(getattr(c, 'values', c))
+
+
+def predictors_to_time_series(predictors, time_steps, has_time_dim=True, use_first_step=False, meta_ds=None):
+    """Predictors of a model with several input time steps as one continuous series: the last step of every sample (the first with
+    use_first_step).  has_time_dim=False: axis 1 is time_steps * channels.  With meta_ds (a SeriesDataset-like object: `dims` and
+    coordinates) the result is a LabeledArray over ('time', 'variable', 'level', 'lat', 'lon') or ('time', 'varlev', 'lat', 'lon')."""
+    idx = 0 if use_first_step else -1
+    if not has_time_dim:
+        predictors = predictors.reshape((predictors.shape[0], time_steps, -1) + tuple(predictors.shape[2:]))
+    result = predictors[:, idx]
+    if meta_ds is None:
+        return result
+    from .generators import LabeledArray
+    if 'level' in meta_ds.dims:
+        dims = ('variable', 'level', 'lat', 'lon')
+        result = result.reshape((meta_ds.dims['sample'],) + tuple(meta_ds.dims[d] for d in dims))
+    else:
+        dims = ('varlev', 'lat', 'lon')
+    coords = {d: _meta_coord(meta_ds, d) for d in dims}
+    coords['time'] = _meta_coord(meta_ds, 'sample')
+    return LabeledArray(result, coords, ('time',) + dims)
+
+
+def add_metadata_to_forecast(forecast, f_hour, meta_ds):
+    """A forecast (forecast_hour, time, variable, lat, lon) as a LabeledArray with the initialisation times and coordinates of meta_ds"""
+    nf = len(f_hour)
+    if nf != forecast.shape[0]:
+        raise ValueError("'f_hour' coordinate must have same size as the first axis of 'forecast'")
+    from .generators import LabeledArray
+    if 'level' in meta_ds.dims:
+        dims = ('variable', 'level', 'lat', 'lon')
+        forecast = forecast.reshape((nf, meta_ds.dims['sample']) + tuple(meta_ds.dims[d] for d in dims))
+    else:
+        dims = ('varlev', 'lat', 'lon')
+    coords = {d: _meta_coord(meta_ds, d) for d in dims}
+    coords['f_hour'] = np.asarray(f_hour)
+    coords['time'] = _meta_coord(meta_ds, 'sample')
+    return LabeledArray(forecast, coords, ('f_hour', 'time') + dims)
+
+
+# -- verification windows (reference DLWP/model/verify.py:201-273) ------------------------------------------------------------------- #
+def window_rows(times, init_dates, forecast_steps, dt, first):
+    """(forecast_steps, n) int64: the row of the record (time coordinate `times`) that holds init_dates[i] + (first + f) * dt hours,
+    -1 where the record has no state at that time -- reindex(method=None) as an index array"""
+    init_dates = np.asarray(init_dates)
+    lead = (np.arange(int(forecast_steps), dtype=np.int64) + int(first)) * int(dt)
+    wanted = init_dates[None, :] + lead[:, None].astype('timedelta64[h]')
+    return _find_times(times, wanted)
+
+
+def take_rows_fill_host(record, rows):
+    """record[rows] as float32 with NaN rows where rows < 0 (the host executor of window_rows)"""
+    out = np.take(record, np.maximum(rows, 0), axis=0).astype(np.float32, copy=False)
+    out[rows < 0] = np.nan
+    return out
+
+
+def _verification(ds, all_ds, forecast_steps, dt, first, source, device, as_tensor):
+    forecast_steps = int(forecast_steps)
+    if forecast_steps < 1:
+        raise ValueError("'forecast_steps' must be an integer >= 1")
+    dt = int(dt)
+    if dt < 1:
+        raise ValueError("'dt' must be an integer >= 1")
+    dims = [d for d in ds.predictors.dims if d.lower() != 'time_step']
+    if not dims or dims[0] != 'sample':
+        raise ValueError("the first dimension of 'ds.predictors' must be 'sample', got %r" % (ds.predictors.dims,))
+    valid_da = getattr(all_ds if all_ds is not None else ds, source)
+    if source == 'targets':
+        valid_da = valid_da.isel(time_step=0)
+    if valid_da.dims[0] != 'sample' or tuple(valid_da.shape[1:]) != tuple(ds.dims[d] for d in dims[1:]):
+        raise ValueError('the verification record %r %r does not match the dataset %r' % (valid_da.dims, tuple(valid_da.shape), ds.dims))
+    rows = window_rows(valid_da.coords['sample'], ds.predictors.coords['sample'], forecast_steps, dt, first)
+    record = valid_da.values
+    on_device = as_tensor or device is not None or isinstance(record, torch.Tensor)
+    dev = _cuda_device(record, device or 'cuda') if on_device else None
+    if dev is None:
+        values = take_rows_fill_host(record, rows)
+    else:
+        from .. import ops
+        if not isinstance(record, torch.Tensor) and np.asarray(record).dtype != np.float32:
+            record = np.asarray(record).astype(np.float32)
+        with torch.cuda.device(dev):
+            values = ops.gather_rows_fill(_to_device(record, dev), rows)
+        if as_tensor:
+            return values
+        values = values.cpu().numpy()
+    from .generators import LabeledArray
+    coords = {d: ds.predictors.coords[d] for d in dims[1:] if d in ds.predictors.coords}
+    coords['time'] = np.asarray(ds.predictors.coords['sample'])
+    coords['f_hour'] = np.arange(dt, dt * forecast_steps + 1, dt).astype('timedelta64[h]')
+    return LabeledArray(values, coords, ['f_hour', 'time'] + dims[1:])
+
+
+def verification_from_samples(ds, all_ds=None, forecast_steps=1, dt=6, device=None):
+    """Forecast verification (f_hour, time, ...) float32 for a dataset of samples: lead f of initialisation date t is
+    targets.isel(time_step=0) of `all_ds` (or `ds`) at t + f * dt hours, f = 0 .. forecast_steps - 1, NaN where there is no such
+    state.  device='cuda' gathers on the device (dlwp_gather_rows_fill): the same bits."""
+    return _verification(ds, all_ds, forecast_steps, dt, 0, 'targets', device, False)
+
+
+def verification_from_series(ds, all_ds=None, forecast_steps=1, dt=6, device=None):
+    """Forecast verification (f_hour, time, ...) float32 for a series dataset: lead f of initialisation date t is the predictors of
+    `all_ds` (or `ds`) at t + (f + 1) * dt hours, NaN where there is no such state.  device='cuda' gathers on the device."""
+    return _verification(ds, all_ds, forecast_steps, dt, 1, 'predictors', device, False)
+
+
+def verification_tensor(ds, all_ds=None, forecast_steps=1, dt=6, kind='series', device='cuda'):
+    """The values of verification_from_series (kind='series') or verification_from_samples (kind='samples') as a CUDA float32 tensor
+    (forecast_steps, n, ...), never downloaded: forecast_error scores a predict_timeseries(..., return_device=True) rollout against
+    it without a host array."""
+    if kind not in ('series', 'samples'):
+        raise ValueError("'kind' must be 'series' or 'samples'")
+    first, source = (1, 'predictors') if kind == 'series' else (0, 'targets')
+    return _verification(ds, all_ds, forecast_steps, dt, first, source, device, True)

@@ -4,6 +4,7 @@ current HIP stream, and device indices.  Every arithmetic / data-movement operat
 """
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1495,3 +1496,115 @@ def verify_nanmean_samples(x):
     _lib.check(_lib.lib.dlwp_verify_nanmean_samples(_lib.handle(_dev(x)), _ptr(x), int(x.shape[0]), mean.numel(), _ptr(mean),
                                                     _stream(x)))
     return mean
+
+
+VERIFY_MAX_LABELS = 64
+
+
+def label_lists(labels, n_labels):
+    """Host side of dlwp_verify_label_nanmean: int labels[count] in [0, n_labels) -> (offsets int32 (n_labels + 1,), index int32
+    (count,)): the samples of label l are index[offsets[l]:offsets[l + 1]], ascending.  ValueError for a label out of range."""
+    labels = np.asarray(labels)
+    n_labels = int(n_labels)
+    if labels.ndim != 1 or labels.dtype.kind not in 'iu':
+        raise ValueError('label_lists: expected a 1-D integer array, got %s of rank %d' % (labels.dtype, labels.ndim))
+    if not 1 <= n_labels <= VERIFY_MAX_LABELS:
+        raise ValueError('label_lists: n_labels %d, expected 1 .. %d' % (n_labels, VERIFY_MAX_LABELS))
+    if labels.size and (int(labels.min()) < 0 or int(labels.max()) >= n_labels):
+        raise ValueError('label_lists: labels must lie in [0, %d), got %d .. %d' % (n_labels, labels.min(), labels.max()))
+    index = np.argsort(labels, kind='stable').astype(np.int32)
+    offsets = np.zeros(n_labels + 1, np.int32)
+    np.cumsum(np.bincount(labels.astype(np.int64), minlength=n_labels), out=offsets[1:])
+    return offsets, index
+
+
+def _rows_of(x, who):
+    if x.dim() < 2 or x.shape[0] < 1 or x[0].numel() < 1:
+        raise ValueError('%s: expected (count >= 1, ...) with a non-empty row, got %r' % (who, tuple(x.shape)))
+    if x.shape[0] > 0x7fffffff:
+        raise ValueError('%s: %d rows, at most 2^31 - 1' % (who, x.shape[0]))
+    return int(x.shape[0]), int(x[0].numel())
+
+
+def verify_label_nanmean_workspace(x, n_labels):
+    """bytes of workspace dlwp_verify_label_nanmean needs for x (count, ...) on x's device"""
+    count, row = _rows_of(x, 'verify_label_nanmean')
+    return int(_lib.lib.dlwp_verify_label_nanmean_workspace(_lib.handle(_dev(x)), count, row, int(n_labels)))
+
+
+def verify_label_nanmean(x, labels, n_labels, ws=None):
+    """include/dlwp_hip.h: dlwp_verify_label_nanmean.  x: (count, ...) contiguous float32 device tensor; labels: HOST integer array
+    (count,) in [0, n_labels), checked here before anything is uploaded.  Returns a NEW float32 tensor (n_labels,) + x.shape[1:]: the
+    NaN-skipping mean of the rows of each label (NaN for a label without a non-NaN sample).  ws: a uint8 workspace, or None."""
+    _check_f32(x)
+    count, row = _rows_of(x, 'verify_label_nanmean')
+    offsets, index = label_lists(labels, n_labels)
+    if index.size != count:
+        raise ValueError('verify_label_nanmean: %d labels for %d samples' % (index.size, count))
+    h = _lib.handle(_dev(x))
+    if ws is None:
+        ws = torch.empty(max(verify_label_nanmean_workspace(x, n_labels), 8), dtype=torch.uint8, device=x.device)
+    index_d = torch.from_numpy(index).to(x.device)
+    mean = torch.empty((int(n_labels),) + tuple(x.shape[1:]), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib.dlwp_verify_label_nanmean(h, _ptr(x), count, row, offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                                                  _ptr(index_d), int(n_labels), _ptr(mean), _ptr(ws), ws.numel(), _stream(x)))
+    return mean
+
+
+def verify_label_error_sums(x, rows, labels, table, anomaly=False, ws=None):
+    """include/dlwp_hip.h: dlwp_verify_label_error_sums.  x: (count_x, ...) and table: (n_labels, ...) contiguous float32 device
+    tensors with equal rows; rows, labels: HOST integer arrays (m,), checked here against count_x and n_labels before they are
+    uploaded.  Returns a NEW (3,) float64 device tensor (sum d^2, sum |d|, pairs counted; d = x[rows[i]] - table[labels[i]], NaN pairs
+    skipped) -- and, with anomaly=True, a NEW (m,) + x.shape[1:] float32 tensor of every d."""
+    _check_f32(x, table)
+    d = _dev(x)
+    if _dev(table) != d:
+        raise ValueError('verify_label_error_sums: operands on devices %d and %d' % (d, _dev(table)))
+    count_x, row = _rows_of(x, 'verify_label_error_sums')
+    n_labels, trow = _rows_of(table, 'verify_label_error_sums')
+    if trow != row:
+        raise ValueError('verify_label_error_sums: rows of %d and %d floats' % (row, trow))
+    if n_labels > VERIFY_MAX_LABELS:
+        raise ValueError('verify_label_error_sums: %d labels, at most %d' % (n_labels, VERIFY_MAX_LABELS))
+    rows, labels = np.asarray(rows), np.asarray(labels)
+    if rows.ndim != 1 or labels.shape != rows.shape or rows.size < 1 or rows.dtype.kind not in 'iu' or labels.dtype.kind not in 'iu':
+        raise ValueError('verify_label_error_sums: rows and labels must be 1-D integer arrays of one length >= 1')
+    if int(rows.min()) < 0 or int(rows.max()) >= count_x:
+        raise ValueError('verify_label_error_sums: rows must lie in [0, %d), got %d .. %d' % (count_x, rows.min(), rows.max()))
+    if int(labels.min()) < 0 or int(labels.max()) >= n_labels:
+        raise ValueError('verify_label_error_sums: labels must lie in [0, %d), got %d .. %d' % (n_labels, labels.min(), labels.max()))
+    m = int(rows.size)
+    h = _lib.handle(d)
+    if ws is None:
+        ws = torch.empty(max(int(_lib.lib.dlwp_verify_error_workspace(h, 1, 1)), 8), dtype=torch.uint8, device=x.device)
+    rows_d = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int32)).to(x.device)
+    labels_d = torch.from_numpy(np.ascontiguousarray(labels, dtype=np.int32)).to(x.device)
+    out = torch.empty((m,) + tuple(x.shape[1:]), dtype=torch.float32, device=x.device) if anomaly else None
+    sums = torch.empty((3,), dtype=torch.float64, device=x.device)
+    _lib.check(_lib.lib.dlwp_verify_label_error_sums(h, _ptr(x), count_x, row, _ptr(rows_d), _ptr(labels_d), m, _ptr(table), n_labels,
+                                                     _ptr(out), _ptr(sums), _ptr(ws), ws.numel(), _stream(x)))
+    return (sums, out) if anomaly else sums
+
+
+def gather_rows_fill(src, rows, out=None):
+    """include/dlwp_hip.h: dlwp_gather_rows_fill.  src: (src_rows, ...) contiguous float32 device tensor; rows: HOST integer array of
+    any shape, -1 (any negative) for "no such row"; an index >= src_rows is refused here, before the upload.  Returns a NEW float32
+    tensor rows.shape + src.shape[1:] (or fills `out` of that size): the rows of src with their bits, NaN rows for the negatives."""
+    _check_f32(src, out)
+    src_rows, row = _rows_of(src, 'gather_rows_fill')
+    rows = np.ascontiguousarray(rows)
+    if rows.dtype.kind not in 'iu':
+        raise ValueError('gather_rows_fill: rows must be integers, got %s' % rows.dtype)
+    rows = rows.astype(np.int64, copy=False)
+    if rows.size and int(rows.max()) >= src_rows:
+        raise ValueError('gather_rows_fill: row index %d, the source has %d rows' % (rows.max(), src_rows))
+    shape = tuple(rows.shape) + tuple(src.shape[1:])
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=src.device)
+    elif out.numel() != rows.size * row or out.device != src.device:
+        raise ValueError('gather_rows_fill: out holds %d elements on %s, expected %d on %s' % (out.numel(), out.device, rows.size * row,
+                                                                                               src.device))
+    rows_d = torch.from_numpy(rows.reshape(-1)).to(src.device)
+    _lib.check(_lib.lib.dlwp_gather_rows_fill(_lib.handle(_dev(src)), _ptr(src), src_rows, row, _ptr(rows_d), int(rows.size), _ptr(out),
+                                              _stream(src)))
+    return out

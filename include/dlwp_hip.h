@@ -977,6 +977,41 @@ int dlwp_verify_error_sums(dlwp_handle_t, const void* a, long long a_lead_stride
                            int count_dec, int groups, long long run, void* sums, void* ws, size_t ws_bytes, void* stream);
 int dlwp_verify_nanmean_samples(dlwp_handle_t, const void* x, int count, long long row, void* mean, void* stream);
 
+/* ---- month-aware climatology and verification windows (csrc/verify.hip; DLWP/model/verify.py:105-273: monthly_climo_error,
+ *      verification_from_samples / _series).  Same conventions as above: float32 data, float64 sums on fixed trees, no atomics,
+ *      64-bit offsets, no synchronisation, grids sized from the handle's CU count, all three mark a recording tape foreign.
+ *      dlwp_verify_label_nanmean: x (count, row) contiguous float32 -> mean (n_labels, row) float32, the NaN-skipping mean of the
+ *      rows that carry each label, n_labels <= 64.  The caller hands the labels over as per-label lists: `offsets` is a HOST array
+ *      of n_labels + 1 ints (0 = offsets[0] <= ... <= offsets[n_labels] = count) and `index` a DEVICE array of count ints, the
+ *      sample indices of label l at index[offsets[l] .. offsets[l + 1]), ascending.  The list of a label is cut into `split` chunks
+ *      [len * k / split, len * (k + 1) / split); a block sums one (label, chunk, 256-thread column tile) in float64 in list order and
+ *      stores a (sum, count) pair per column in ws; a second launch adds the chunks in chunk order, divides once and rounds once to
+ *      float32 (NaN for a label without a non-NaN sample).  split = min(max(1, 8 * CUs / (n_labels * tiles)), count) with
+ *      tiles = ceil(units / 256) and units = row / 4 when row % 4 == 0 and x is 16-byte aligned (16-byte loads), else row: the
+ *      sample axis is split only when the column tiles alone do not fill the chip.  dlwp_verify_label_nanmean_workspace returns
+ *      n_labels * split * row * 12 bytes for the larger split of the two routes (a NULL handle counts 256 CUs); ws must be 8-byte
+ *      aligned.  An index outside [0, count) is skipped, never read.  Refused without a launch: sizes < 1, n_labels outside
+ *      1 .. 64, null pointers, offsets that do not run from 0 to count without decreasing, a row too long for one grid, a workspace
+ *      that is too small or misaligned, a null handle (in that order).
+ *      dlwp_verify_label_error_sums: sums (device, 3 float64) <- sum d^2, sum |d|, pairs counted over d = x[rows[i]] - table[labels[i]],
+ *      i < m, with x (count_x, row), table (n_labels, row), rows and labels DEVICE int arrays of m; d is rounded once in float32 and NaN
+ *      pairs are skipped, as in dlwp_verify_error_sums, of which this is one cell with the same partial / final tree.  anomaly, if not
+ *      NULL, is (m, row) float32 and receives every d, NaN included.  A row index or label outside its range gives a NaN row and is
+ *      never used as an address.  16-byte accesses when row % 4 == 0 and x, table and anomaly are 16-byte aligned.  ws: what
+ *      dlwp_verify_error_workspace(h, 1, 1) returns.
+ *      dlwp_gather_rows_fill: src (src_rows, row) float32, rows a DEVICE array of n int64 -> dst (n, row): dst[j] = src[rows[j]]
+ *      with the bits copied (NaN payloads included), or quiet NaNs (0x7fc00000) across the row where rows[j] < 0 -- reindex without a
+ *      fill method.  An index >= src_rows is the caller's error (dlwp_amd.ops.gather_rows_fill refuses it on the host array); the
+ *      kernel stores NaN for it and reads nothing.  16-byte accesses when row % 4 == 0 and src, dst are 16-byte aligned; n == 0 is a
+ *      no-op.                                                                                                                      */
+size_t dlwp_verify_label_nanmean_workspace(dlwp_handle_t, int count, long long row, int n_labels);
+int dlwp_verify_label_nanmean(dlwp_handle_t, const void* x, int count, long long row, const int* offsets, const void* index,
+                              int n_labels, void* mean, void* ws, size_t ws_bytes, void* stream);
+int dlwp_verify_label_error_sums(dlwp_handle_t, const void* x, int count_x, long long row, const void* rows, const void* labels, int m,
+                                 const void* table, int n_labels, void* anomaly, void* sums, void* ws, size_t ws_bytes, void* stream);
+int dlwp_gather_rows_fill(dlwp_handle_t, const void* src, long long src_rows, long long row, const void* rows, long long n, void* dst,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif
