@@ -330,6 +330,27 @@ _sig('dlwp_verify_label_error_sums', [_vp, _vp, _i, ctypes.c_longlong, _vp, _vp,
 _sig('dlwp_gather_rows_fill', [_vp, _vp, ctypes.c_longlong, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _vp])
 
 
+# csrc/series.hip: the descriptor tables of dlwp_series_window_gather (include/dlwp_hip.h)
+SERIES_MAX_SRCS, SERIES_MAX_DSTS, SERIES_MAX_SEGS = 4, 32, 64
+
+
+class SeriesSrc(ctypes.Structure):
+    _fields_ = [('base', _vp), ('rows', ctypes.c_longlong), ('row', ctypes.c_longlong)]
+
+
+class SeriesDst(ctypes.Structure):
+    _fields_ = [('base', _vp), ('row', ctypes.c_longlong)]
+
+
+class SeriesSeg(ctypes.Structure):
+    _fields_ = [('src', _i), ('dst', _i), ('shift', ctypes.c_longlong), ('src_at', ctypes.c_longlong),
+                ('dst_at', ctypes.c_longlong), ('len', ctypes.c_longlong)]
+
+
+_sig('dlwp_series_gather_grid_cap', [_vp], _i)
+_sig('dlwp_series_window_gather', [_vp, _P(SeriesSrc), _i, _P(SeriesDst), _i, _P(SeriesSeg), _i, _vp, ctypes.c_longlong, _vp])
+
+
 def check(rc):
     if rc != OK:
         raise DlwpError(rc, lib.dlwp_last_error().decode('utf-8', 'replace'))

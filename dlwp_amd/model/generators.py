@@ -11,7 +11,8 @@ Batch feed for fit_generator.
   SeriesDataset / LabeledArray   in-memory stand-ins for the xarray objects it reads (label selection, coordinates).
   DeviceLoader    what replaces Keras' worker *processes* + per-batch feed_dict copy: a background thread gathers batch
                   i+1 into a pinned host buffer and a copy stream moves it to HBM while batch i trains
-                  (pinned-host -> HBM double buffering).
+                  (pinned-host -> HBM double buffering).  Series generators with a window_plan() skip all of that: the
+                  series lives in HBM and one kernel launch cuts each batch out of it (WindowPlan, merge_segments).
 """
 import ctypes
 import os
@@ -311,6 +312,52 @@ class SeriesDataset(object):
         pass
 
 
+def merge_segments(pieces, src_rows):
+    """(src, dst, shift, src_at, dst_at, len) pieces in destination order -> int64 (n_seg, 6) table in which neighbours that
+    continue each other in the destination and in the flat source ((shift * row + src_at) + len, over the end of a source row into
+    the next time) are one segment.  src_rows[s]: floats of a row of source s."""
+    out = []
+    for p in pieces:
+        p = [int(v) for v in p]
+        if out:
+            q = out[-1]
+            row = int(src_rows[q[0]])
+            if (p[0] == q[0] and p[1] == q[1] and p[4] == q[4] + q[5] and
+                    p[2] * row + p[3] == q[2] * row + q[3] + q[5]):
+                q[5] += p[5]
+                continue
+        out.append(p)
+    return np.array(out, dtype=np.int64).reshape(-1, 6)
+
+
+class WindowPlan(object):
+    """What a batch of a series generator copies (SeriesDataGenerator.window_plan):
+      sources   2-D float32 (T, row) arrays, one row per time of the series
+      shapes    per-sample shapes of the destinations: X first, then the target or every target block
+      segments  int64 (n_seg, 6): src, dst, shift, src_at, dst_at, len in floats; for sample position s the floats
+                sources[src].flat[(s + shift) * row + src_at : ... + len] land at dst_at of that sample's row of destination dst
+      y_list    generate() returns the targets as a list (`sequence`)"""
+
+    def __init__(self, sources, shapes, segments, y_list=False):
+        self.sources = list(sources)
+        self.shapes = [tuple(int(v) for v in s) for s in shapes]
+        self.segments = np.ascontiguousarray(segments, dtype=np.int64).reshape(-1, 6)
+        self.y_list = bool(y_list)
+
+    @property
+    def rows(self):
+        """floats of one sample of every destination"""
+        return [int(np.prod(s)) for s in self.shapes]
+
+    @property
+    def nbytes(self):
+        return sum(int(a.size) * 4 for a in self.sources)
+
+    def as_batch(self, arrays):
+        """[X, y0, ...] -> what generate() returns: (X, y) or (X, [y0, ...])"""
+        return arrays[0], (list(arrays[1:]) if self.y_list else arrays[1])
+
+
 class SeriesDataGenerator(object):
     """Batches from a continuous series: inputs = `input_time_steps` consecutive states of the `input_sel` variables
     (+ insolation), targets = `output_time_steps` states of the `output_sel` variables starting `interval` steps after
@@ -542,6 +589,70 @@ class SeriesDataGenerator(object):
                           (self.output_dense_shape if self._keep_time_axis else (self.output_n_features,)))
         return p, t_shape
 
+    def window_plan(self):
+        """DeviceLoader's HBM path: what generate(samples) COPIES, as a WindowPlan -- the series as 2-D (T, row) sources, the
+        per-sample shapes of X and of every target (block), and the segment table that dlwp_series_window_gather
+        (include/dlwp_hip.h) and ops.series_window_gather_host execute -- or None when generate() is more than copies.  The rule is
+        DataGenerator.batch_sources': float32 C-contiguous numpy series, no imputer and no scaler in the model, remove_nan off or
+        no NaN anywhere in the series (one scan per array, cached against the arrays' identity as in generate_inputs), generate
+        and __getitem__ not overridden.  Pieces: per input step the variables of that step, then its insolation plane; per target
+        block its output steps.  Neighbours that are contiguous in the source AND in the destination are one segment: without
+        insolation X is one run of input_time_steps states, a target block one run of output_time_steps states.  The plan is
+        cached against what it was made from and handed out as the same object until that changes."""
+        if type(self).generate is not SeriesDataGenerator.generate or type(self).__getitem__ is not SeriesDataGenerator.__getitem__:
+            return None
+        arrays = [self.input_da.values, self.output_da.values] + ([self.insolation_da.values] if self._add_insolation else [])
+        if not all(isinstance(a, np.ndarray) for a in arrays):
+            return None
+        key = tuple((id(a), a.ctypes.data, a.shape, a.dtype.str) for a in arrays) + (
+            bool(self._impute_missing), getattr(self.model, 'scaler_type', None), bool(self._remove_nan), bool(self._is_convolutional),
+            bool(self._keep_time_axis), self._input_time_steps, self._output_time_steps, self._interval, self._sequence)
+        cached = self.__dict__.get('_window_plan')
+        if cached is not None and cached[0] == key:
+            return cached[1]
+        plan = None
+        ok = (all(a.dtype == np.float32 and a.flags['C_CONTIGUOUS'] and a.ndim >= 2 and a.size > 0 for a in arrays) and
+              all(a.shape[0] == arrays[0].shape[0] for a in arrays) and self._n_sample > 0 and
+              not self._impute_missing and getattr(self.model, 'scaler_type', None) is None)
+        if ok and self._remove_nan:
+            ids = tuple(id(a) for a in arrays)
+            if self.__dict__.get('_nan_free_key') != ids:
+                self._nan_free, self._nan_free_key = not any(_has_nan(a) for a in arrays), ids
+            ok = self._nan_free
+        if ok:
+            plan = self._make_window_plan(arrays)
+        self._window_plan = (key, plan)
+        return plan
+
+    def _make_window_plan(self, arrays):
+        t_in, t_out = self._input_time_steps, self._output_time_steps
+        sources = [arrays[0].reshape(arrays[0].shape[0], -1)]
+        s_out = 0
+        if arrays[1] is not arrays[0]:
+            sources.append(arrays[1].reshape(arrays[1].shape[0], -1))
+            s_out = 1
+        row_in, row_out = sources[0].shape[1], sources[s_out].shape[1]
+        pieces = []                                   # (src, dst, shift, src_at, dst_at, len), destinations in order
+        if self._add_insolation:
+            sources.append(arrays[2].reshape(arrays[2].shape[0], -1))
+            s_sol, hw = len(sources) - 1, sources[-1].shape[1]
+            for m in range(t_in):
+                pieces.append((0, 0, m, 0, m * (row_in + hw), row_in))
+                pieces.append((s_sol, 0, m, 0, m * (row_in + hw) + row_in, hw))
+        else:
+            pieces += [(0, 0, m, 0, m * row_in, row_in) for m in range(t_in)]
+        first = t_in + self._interval - 1
+        for k in range(self._sequence or 1):
+            pieces += [(s_out, 1 + k, first + t_out * k + m, 0, m * row_out, row_out) for m in range(t_out)]
+        if self._is_convolutional:
+            x_shape, y_shape = tuple(self.convolution_shape), tuple(self.output_convolution_shape)
+        elif self._keep_time_axis:
+            x_shape, y_shape = tuple(self.dense_shape), tuple(self.output_dense_shape)
+        else:
+            x_shape, y_shape = (self.n_features,), (self.output_n_features,)
+        shapes = [x_shape] + [y_shape] * (self._sequence or 1)
+        return WindowPlan(sources, shapes, merge_segments(pieces, [s.shape[1] for s in sources]), self._sequence is not None)
+
     def __len__(self):
         return int(np.ceil(self._n_sample / self._batch_size))
 
@@ -580,7 +691,13 @@ class DeviceLoader(object):
     keras.utils.multi_gpu_model makes inside one process, reference models.py:104-109).  Generators with the
     DataGenerator protocol (`_indices`, `_batch_size`, `generate(samples)`) gather just those samples; any other
     Sequence is asked for the whole batch and sliced on the host before the upload.  iter_batches() yields
-    (X, y, n_global) so the training step can weight ragged shards exactly."""
+    (X, y, n_global) so the training step can weight ragged shards exactly.
+
+    A series generator whose batches are plain windows (SeriesDataGenerator.window_plan) is not fed from the host at all on a
+    CUDA device: its series is uploaded once per loader (if it takes at most `resident_fraction` of the free memory), every pass
+    uploads the generator's index list once, and batch idx is ONE launch of dlwp_series_window_gather (csrc/series.hip) on the
+    consumer's stream into rotating device buffers -- no worker thread, no pinned copy, no transfer per batch.
+    DLWP_SERIES_HOST=1 keeps such a generator on the host path.  `mode` names the path that served the last batch."""
 
     #: host threads of a native row gather (dlwp_host_gather_rows)
     gather_threads = max(1, min(8, (os.cpu_count() or 2) // 2))
@@ -601,9 +718,65 @@ class DeviceLoader(object):
         else:
             self._copy_stream = torch.cuda.Stream(device=device)
         self._slots = [None] * self.depth
+        self.mode = None            # the path that served the last batch: 'resident', 'native' or 'generate'
+        self._resident = None
 
     def __len__(self):
         return len(self.order)
+
+    # -- the series in HBM: batches cut by one kernel launch, no host work and no transfer per batch --------------------------- #
+    #: the series is uploaded when it takes at most this share of the free device memory (Trainer.resident_fraction's rule)
+    resident_fraction = 0.5
+
+    def _resident_state(self):
+        """The uploaded sources and descriptor tables of the generator's window_plan (made on first use, once per loader and
+        plan), or None: no CUDA device, DLWP_SERIES_HOST=1, a generator without a plan, or a series larger than resident_fraction
+        of the free memory -- the host paths below serve those."""
+        if self.device.type != 'cuda' or os.environ.get('DLWP_SERIES_HOST') == '1' or not hasattr(self.gen, 'window_plan'):
+            return None
+        if not all(hasattr(self.gen, a) for a in ('_indices', '_batch_size')):
+            return None
+        plan = self.gen.window_plan()
+        if plan is None:
+            return None
+        st = self._resident
+        if st is not None and st['plan'] is plan:
+            return st if st['tables'] is not None else None
+        from .. import ops
+        torch = self._torch
+        st = self._resident = {'plan': plan, 'tables': None}
+        free, _ = torch.cuda.mem_get_info(self.device)
+        if self.resident_fraction <= 0 or plan.nbytes > self.resident_fraction * free:
+            return None
+        srcs = [torch.from_numpy(a).to(self.device) for a in plan.sources]
+        bs = max(1, int(self.gen._batch_size))
+        bufs = [[torch.empty((bs, r), dtype=torch.float32, device=self.device) for r in plan.rows] for _ in range(self.depth)]
+        st['bufs'] = bufs
+        st['tables'] = [ops.SeriesTables(srcs, b, plan.segments) for b in bufs]
+        return st
+
+    def _iter_resident(self, st):
+        from ..parallel import shard_bounds
+        torch = self._torch
+        gen, plan = self.gen, st['plan']
+        bs = int(gen._batch_size)
+        # this pass's index list, once: batch idx of this rank starts at idx * bs (+ its shard's offset) of it
+        index = torch.from_numpy(np.ascontiguousarray(gen._indices, dtype=np.int64)).to(self.device)
+        for k, idx in enumerate(self.order):
+            idx = int(idx)
+            if not -len(gen) <= idx < len(gen):
+                raise IndexError('batch index out of range')        # (what generator[idx] says on the host paths)
+            samples, n_global = self._samples(idx)
+            start = (len(gen) + idx if idx < 0 else idx) * bs
+            if self.shard is not None:
+                start += shard_bounds(n_global, *self.shard)[0]
+            n = len(samples)
+            slot = k % self.depth
+            if n > 0:
+                st['tables'][slot].launch(index, n, start)
+            ds = [b[:n].view((n,) + shp) for b, shp in zip(st['bufs'][slot], plan.shapes)]
+            self.mode = 'resident'
+            yield ds[0], (ds[1:] if plan.y_list else ds[1]), n_global
 
     # -- host side: this rank's rows of global batch `idx` -------------------------------------------------------------- #
     def _samples(self, idx):
@@ -685,7 +858,7 @@ class DeviceLoader(object):
                     _lib.check(_lib.lib.dlwp_host_gather_rows(ctypes.c_void_p(hbuf.data_ptr()), ctypes.c_void_p(arr.ctypes.data),
                                                               rows.ctypes.data_as(ctypes.c_void_p), len(rows), row_bytes,
                                                               arr.shape[0], int(self.gather_threads)))
-                return {'shapes': shapes, 'was_list': False, 'n_global': n_global, 'arrays': None}
+                return {'shapes': shapes, 'was_list': False, 'n_global': n_global, 'arrays': None, 'mode': 'native'}
         X, ys, was_list, n_global = self._fetch(idx)
         arrays = [X] + ys
         shapes = [a.shape for a in arrays]
@@ -693,7 +866,7 @@ class DeviceLoader(object):
             for a, hbuf in zip(arrays, slot['host']):
                 hbuf[:a.size].view(a.shape).numpy()[...] = a
             arrays = None
-        return {'shapes': shapes, 'was_list': was_list, 'n_global': n_global, 'arrays': arrays}
+        return {'shapes': shapes, 'was_list': was_list, 'n_global': n_global, 'arrays': arrays, 'mode': 'generate'}
 
     def iter_batches(self, order=None):
         """yields (X, y, n_global): device tensors of this rank's rows (y a list when the generator gives a list) and
@@ -702,6 +875,11 @@ class DeviceLoader(object):
         torch = self._torch
         if order is not None:
             self.order = list(order)
+        resident = self._resident_state()
+        if resident is not None:
+            for batch in self._iter_resident(resident):
+                yield batch
+            return
         n = len(self.order)
         lock = threading.Condition()
         state = {'filled': {}, 'free': set(range(self.depth)), 'error': None, 'stop': False}
@@ -770,7 +948,7 @@ class DeviceLoader(object):
             else:
                 for d, h in zip(ds, hs):
                     d.copy_(h)
-            return ds, slot, res['was_list'], res['n_global']
+            return ds, slot, res['was_list'], res['n_global'], res['mode']
 
         def release(k):
             """(consumer thread) batch k's pinned buffers may be refilled once its upload has drained"""
@@ -786,7 +964,7 @@ class DeviceLoader(object):
             for k in range(n):
                 cur = nxt
                 nxt = issue(k + 1) if k + 1 < n else None        # batch k + 1 uploads under batch k's step
-                ds, slot, was_list, n_global = cur
+                ds, slot, was_list, n_global, self.mode = cur
                 if slot['ev'] is not None:
                     torch.cuda.current_stream(self.device).wait_event(slot['ev'])
                 yield ds[0], (ds[1:] if was_list else ds[1]), n_global

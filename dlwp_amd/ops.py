@@ -1608,3 +1608,112 @@ def gather_rows_fill(src, rows, out=None):
     _lib.check(_lib.lib.dlwp_gather_rows_fill(_lib.handle(_dev(src)), _ptr(src), src_rows, row, _ptr(rows_d), int(rows.size), _ptr(out),
                                               _stream(src)))
     return out
+
+
+# -- batches of a series generator out of an HBM-resident series (csrc/series.hip) --------------------------------------------------- #
+SERIES_CHUNK_UNITS = 1024          # units (16 bytes, or one float on the scalar path) a block moves per turn
+
+
+def series_window_gather_host(plan, samples):
+    """The segment table of include/dlwp_hip.h: dlwp_series_window_gather restated in numpy -- the kernel's oracle and what the CPU
+    tests compare with SeriesDataGenerator.generate.  plan: sources (2-D float32 arrays), shapes, segments (model.generators.
+    WindowPlan); samples: integer start positions.  Returns [X, y0, ...] as float32 arrays (n,) + shape.  Bits are copied as words;
+    a run whose first or last time is no row of its source is filled with quiet NaNs (0x7fc00000)."""
+    samples = np.asarray(samples).reshape(-1).astype(np.int64)
+    n = samples.size
+    outs = [np.zeros((n, int(np.prod(s))), np.uint32) for s in plan.shapes]
+    for src, dst, shift, src_at, dst_at, ln in np.asarray(plan.segments, dtype=np.int64).reshape(-1, 6).tolist():
+        a = plan.sources[src]
+        rows, row = a.shape
+        flat = np.ascontiguousarray(a, dtype=np.float32).reshape(-1).view(np.uint32)
+        span = (src_at + ln - 1) // row
+        for i in range(n):
+            t = int(samples[i]) + shift
+            if t < 0 or t + span > rows - 1:
+                outs[dst][i, dst_at:dst_at + ln] = 0x7fc00000
+            else:
+                outs[dst][i, dst_at:dst_at + ln] = flat[t * row + src_at:t * row + src_at + ln]
+    return [o.view(np.float32).reshape((n,) + tuple(s)) for o, s in zip(outs, plan.shapes)]
+
+
+def series_chunks(segments, vec):
+    """chunks of SERIES_CHUNK_UNITS units that one sample of a segment table is cut into (the launch is n * this many block turns)"""
+    w = 4 if vec else 1
+    return sum((int(s[5]) // w + SERIES_CHUNK_UNITS - 1) // SERIES_CHUNK_UNITS for s in np.asarray(segments).reshape(-1, 6))
+
+
+def series_grid_cap(device=None):
+    """blocks the launch of dlwp_series_window_gather is capped at on `device` (the library's own figure)"""
+    idx = torch.cuda.current_device() if device is None or torch.device(device).index is None else torch.device(device).index
+    return int(_lib.lib.dlwp_series_gather_grid_cap(_lib.handle(idx)))
+
+
+class SeriesTables(object):
+    """The descriptor tables of one dlwp_series_window_gather call site, built once: sources and destinations are device tensors
+    that this object keeps alive; a launch only adds the sample positions.  dsts[d] is (capacity, row): a launch of n <= capacity
+    samples fills its first n rows."""
+
+    def __init__(self, srcs, dsts, segments):
+        srcs, dsts = list(srcs), list(dsts)
+        segments = np.ascontiguousarray(segments, dtype=np.int64).reshape(-1, 6)
+        if not 1 <= len(srcs) <= _lib.SERIES_MAX_SRCS or not 1 <= len(dsts) <= _lib.SERIES_MAX_DSTS or \
+                not 1 <= len(segments) <= _lib.SERIES_MAX_SEGS:
+            raise ValueError('series_window_gather: %d sources, %d destinations, %d segments; at most %d, %d, %d and at least one of each'
+                             % (len(srcs), len(dsts), len(segments), _lib.SERIES_MAX_SRCS, _lib.SERIES_MAX_DSTS, _lib.SERIES_MAX_SEGS))
+        _check_f32(*(srcs + dsts))
+        self.device = srcs[0].device
+        dev = _dev(srcs[0])
+        for t in srcs + dsts:
+            if _dev(t) != dev:
+                raise ValueError('series_window_gather: tensors on devices %d and %d' % (dev, _dev(t)))
+            if t.dim() != 2 or t.shape[1] < 1:
+                raise ValueError('series_window_gather: expected 2-D (rows, row) tensors, got %r' % (tuple(t.shape),))
+        if any(t.shape[0] < 1 for t in srcs):
+            raise ValueError('series_window_gather: a source without rows')
+        self.capacity = min(int(t.shape[0]) for t in dsts)
+        for g, (src, dst, shift, src_at, dst_at, ln) in enumerate(segments.tolist()):
+            if not (0 <= src < len(srcs) and 0 <= dst < len(dsts)):
+                raise ValueError('series_window_gather: segment %d names source %d, destination %d' % (g, src, dst))
+            if ln < 1 or not 0 <= src_at < srcs[src].shape[1] or dst_at < 0 or dst_at + ln > dsts[dst].shape[1]:
+                raise ValueError('series_window_gather: segment %d (src_at %d, dst_at %d, len %d) leaves its rows' % (g, src_at, dst_at, ln))
+        self.keep = (srcs, dsts)
+        self.n_src, self.n_dst, self.n_seg = len(srcs), len(dsts), len(segments)
+        self.srcs = (_lib.SeriesSrc * len(srcs))(*[_lib.SeriesSrc(t.data_ptr(), int(t.shape[0]), int(t.shape[1])) for t in srcs])
+        self.dsts = (_lib.SeriesDst * len(dsts))(*[_lib.SeriesDst(t.data_ptr(), int(t.shape[1])) for t in dsts])
+        self.segs = (_lib.SeriesSeg * len(segments))(*[_lib.SeriesSeg(*[int(v) for v in s]) for s in segments.tolist()])
+        self.handle = _lib.handle(dev)
+        self.vec = all(t.data_ptr() % 16 == 0 and t.shape[1] % 4 == 0 for t in srcs + dsts) and \
+            bool((segments[:, 3:] % 4 == 0).all())
+
+    def launch(self, samples, n=None, offset=0):
+        """samples: int64 device tensor; positions offset .. offset + n of it start the n samples.  Enqueued on the current stream."""
+        n = int(samples.numel() - offset if n is None else n)
+        offset = int(offset)
+        if samples.dtype != torch.int64 or not samples.is_contiguous() or samples.device != self.device:
+            raise ValueError('series_window_gather: samples must be a contiguous int64 tensor on %s' % (self.device,))
+        if n < 0 or offset < 0 or offset + n > samples.numel() or n > self.capacity:
+            raise ValueError('series_window_gather: %d samples from position %d of %d into destinations of %d rows'
+                             % (n, offset, samples.numel(), self.capacity))
+        _lib.check(_lib.lib.dlwp_series_window_gather(self.handle, self.srcs, self.n_src, self.dsts, self.n_dst, self.segs, self.n_seg,
+                                                      ctypes.c_void_p(samples.data_ptr() + 8 * offset), n, _stream(samples)))
+
+
+def series_window_gather(srcs, segments, shapes, samples, out=None):
+    """include/dlwp_hip.h: dlwp_series_window_gather.  srcs: float32 device tensors (rows, ...) (their rows flattened); segments:
+    HOST int64 (n_seg, 6) table of src, dst, shift, src_at, dst_at, len; shapes: per-sample shapes of the destinations; samples:
+    integer start positions, a host array (uploaded here) or an int64 device tensor.  Returns NEW float32 tensors (n,) + shape --
+    or fills `out`, 2-D (>= n, row) tensors -- on the current stream.  Times outside a source give quiet-NaN runs."""
+    if not isinstance(samples, torch.Tensor):
+        samples = np.ascontiguousarray(samples)
+        if samples.dtype.kind not in 'iu':
+            raise ValueError('series_window_gather: samples must be integers, got %s' % samples.dtype)
+        samples = torch.from_numpy(samples.reshape(-1).astype(np.int64)).to(srcs[0].device)
+    n = int(samples.numel())
+    rows = [int(np.prod(s)) for s in shapes]
+    made = out is None
+    if made:
+        out = [torch.empty((max(n, 1), r), dtype=torch.float32, device=srcs[0].device) for r in rows]
+    elif len(out) != len(rows) or any(o.dim() != 2 or o.shape[1] != r for o, r in zip(out, rows)):
+        raise ValueError('series_window_gather: out must hold one (n, row) tensor per destination')
+    SeriesTables([s.reshape(s.shape[0], -1) for s in srcs], out, segments).launch(samples, n)
+    return [o[:n].view((n,) + tuple(s)) for o, s in zip(out, shapes)] if made else out

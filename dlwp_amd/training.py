@@ -1434,11 +1434,33 @@ class Trainer(object):
         finally:
             self._loader_threads -= 1
 
+    def _eval_batches(self, generator, steps):
+        """(X, y) of batches 0 .. steps - 1.  A series generator whose batches are plain windows (window_plan) on a single CUDA
+        device goes through a DeviceLoader that keeps the series in HBM -- one loader per generator, kept with the trainer, so
+        the validation set of a fit_generator call is uploaded once and not after every epoch; everything else is generator[i]."""
+        loader = None
+        single = self.dp is None or self.dp.world <= 1
+        if self.device.type == 'cuda' and single and hasattr(generator, 'window_plan') and 0 < steps <= len(generator):
+            from .model.generators import DeviceLoader
+            cache = self.__dict__.setdefault('_eval_loaders', {})
+            ent = cache.get(id(generator))
+            if ent is None or ent[0]() is not generator:
+                import weakref
+                cache.clear()                 # (one validation generator at a time: an earlier one's series leaves HBM)
+                ent = cache[id(generator)] = (weakref.ref(generator), DeviceLoader(generator, self.device))
+            if ent[1]._resident_state() is not None:
+                loader = ent[1]
+        if loader is None:
+            for i in range(steps):
+                yield generator[i]
+        else:
+            for X, y, _ in loader.iter_batches(list(range(steps))):
+                yield X, y
+
     def evaluate_generator(self, generator, steps=None):
         steps = int(steps) if steps is not None else len(generator)
         sums, seen = None, 0
-        for i in range(steps):
-            X, y = generator[i]
+        for X, y in self._eval_batches(generator, steps):
             vals = np.asarray(self.test_on_batch(X, y), dtype=np.float64)
             bs = int(np.asarray(X).shape[0]) if not isinstance(X, torch.Tensor) else int(X.shape[0])
             sums = vals * bs if sums is None else sums + vals * bs

@@ -1012,6 +1012,37 @@ int dlwp_verify_label_error_sums(dlwp_handle_t, const void* x, int count_x, long
 int dlwp_gather_rows_fill(dlwp_handle_t, const void* src, long long src_rows, long long row, const void* rows, long long n, void* dst,
                           void* stream);
 
+/* ---- batches of a series generator cut out of an HBM-resident series (csrc/series.hip; DLWP/model/generators.py:323-629,
+ *      SeriesDataGenerator.generate).  One launch fills X and every target block of a batch:
+ *        dst[g.dst][i * row_d + g.dst_at + e] = src[g.src][(samples[i] + g.shift) * row_s + g.src_at + e],  e < g.len, i < n
+ *      for every segment g of the table.  srcs[s] = {base, rows, row}: a DEVICE float32 array (rows, row), one row per time (the
+ *      input series, the output series, the insolation series), at most 4.  dsts[d] = {base, row}: a DEVICE float32 array (n, row)
+ *      (X and each target block), at most 32.  segs: a HOST array of at most 64 segments, in floats; it is validated here and handed
+ *      to the kernel by value with the two descriptor tables (3.4 of the 4 KiB of kernel arguments).  samples: a DEVICE array of n
+ *      int64 start positions.  A segment is a run that is contiguous on both sides; src_at lies inside the source row and the run
+ *      may continue over the row's end into the following times (the consecutive states of a window are one run).  The bits are
+ *      copied as words, NaN payloads included.  A run whose first time samples[i] + shift or whose last time is no row of the source
+ *      is stored as quiet NaNs (0x7fc00000) over its whole length and is never used as an address.  16-byte accesses when every
+ *      row, src_at, dst_at and len is a multiple of 4 floats and every base is 16-byte aligned, one float at a time otherwise
+ *      (decided on the host).  A 256-thread block moves a chunk of 1024 units of one segment of one sample per turn (a unit = 16
+ *      bytes or one float; four loads in front of four stores per thread); the grid is min(n * chunks per sample,
+ *      dlwp_series_gather_grid_cap(h) = 8 * CUs) blocks, which stride over the (sample, chunk) list.  No atomics, no LDS, no
+ *      synchronisation; not part of a training step: it marks a recording tape foreign.  Refused without a launch, in this order:
+ *      n_src, n_dst, n_seg outside 1 .. 4 / 32 / 64 or n < 0; a null table; per source a null base, rows or row < 1, a size that
+ *      overflows; per destination a null base, row < 1, n * row overflowing; per segment a source or destination index outside
+ *      its table, len < 1, src_at outside [0, row_s), dst_at + len past row_d, a len or shift that overflows.  n == 0 is then a
+ *      no-op; otherwise a null `samples` and a null handle are refused.  The caller guarantees that the arrays hold what the
+ *      descriptors say (dlwp_amd.ops.series_window_gather checks it).                                                              */
+#define DLWP_SERIES_MAX_SRCS 4
+#define DLWP_SERIES_MAX_DSTS 32
+#define DLWP_SERIES_MAX_SEGS 64
+typedef struct dlwp_series_src { const void* base; long long rows, row; } dlwp_series_src;
+typedef struct dlwp_series_dst { void* base; long long row; } dlwp_series_dst;
+typedef struct dlwp_series_seg { int src, dst; long long shift, src_at, dst_at, len; } dlwp_series_seg;
+int dlwp_series_gather_grid_cap(dlwp_handle_t);
+int dlwp_series_window_gather(dlwp_handle_t, const dlwp_series_src* srcs, int n_src, const dlwp_series_dst* dsts, int n_dst,
+                              const dlwp_series_seg* segs, int n_seg, const void* samples, long long n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
