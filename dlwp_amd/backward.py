@@ -333,6 +333,9 @@ class BackwardPass(object):
         gv = self.trainer._grad_view
         n_out = op.conv_geometry[0]
         pp = self.plan.phase_params[op.wparam]
+        if pp.get('kind') == 'tconv':
+            self._conv_wgrad_tconv(c, dz, kern, xs, acc)
+            return
         dw2 = self.new(*kern.shape)
         have_db = c.k in self.phase_db
         db2 = self.phase_db[c.k] if have_db else (self.new(n_out) if lay.bias is not None else None)
@@ -351,6 +354,22 @@ class BackwardPass(object):
             self.post.append(fold_back)          # dw2 / db2 are final only behind the deferred sums
         else:
             fold_back()
+
+    def _conv_wgrad_tconv(self, c, dz, kern, xs, acc):
+        """Conv2DTranspose: the weight gradient of its phase convolution, gathered onto the layer's kernel (a permutation: no
+        sums).  The bias gradient was taken at full resolution by the interleave's adjoint (_d2sc)."""
+        op, lay, d, src = c.op, c.op.layer, c.d, c.src
+        gk = self.trainer._grad_view(lay, 'kernel')
+        dw2 = self.new(*kern.shape)
+        wkey = self.key('wgrad', c.k)
+        self.lanes.run(lambda: ops.conv2d_bwd_weight(src, dz, dw2, d, xs, ws_key=wkey))
+
+        def gather():
+            ops.tconv_weights_bwd(dw2, gk, accumulate=acc)
+        if self.prep is not None:
+            self.post.append(gather)             # dw2 is final only behind the deferred sums
+        else:
+            gather()
 
     def _conv_dgrad(self, c, dz, kern, xs):
         """The data gradient: its convolution, the pair's close behind it, then the adjoint of how the layer read its source."""
@@ -427,6 +446,30 @@ class BackwardPass(object):
         """adjoint of the depth-to-space interleave of a restated decoder layer"""
         op = c.op
         self.book.set(op.src, ops.space_to_depth2(c.gD, op.xs[0], c_off=op.out_c_off), 4 * op.xs[0])
+
+    def _d2sc(self, c):
+        """Conv2DTranspose behind its phase convolution: activation backward and the bias gradient on the layer's full-resolution
+        output (dz in place of dy), then the adjoint of the cropping interleave -- every element of the phase gradient is written,
+        +0 where the crop dropped it.  The convolution in front finds a pre-activation gradient and a finished bias gradient."""
+        op, lay, gD = c.op, c.op.layer, c.gD
+        y = self.book.tensor(op.dst)
+        f = op.xs[0]
+        if lay.bias is not None:
+            gb = self.trainer._grad_view(lay, 'bias')
+            if lay.activation != 'linear':
+                ops.act_bwd_bias_grad(y, gD, op.act, gb, f, c_off=op.out_c_off, out=gD, ws_key=self.key('bias', c.k))
+            else:
+                ops.bias_grad(gD, gb, f, c_off=op.out_c_off, ws_key=self.key('bias', c.k))
+        elif lay.activation != 'linear':
+            ops.act_bwd(y, gD, op.act, out=gD)
+        dph = ops.space_to_depth2_fill(gD, f, op.xs[1], op.xs[2], op.crop[0], op.crop[1], c_off=op.out_c_off)
+        self.book.set(op.src, dph, 4 * f)
+        self.preact.add(op.src)
+
+    def _crop(self, c):
+        """Cropping2D: the gradient is zero padding"""
+        if c.op.src != P.STATE_IN:
+            self.book.deposit(c.op.src, 0, c.src.shape[1], ops.pad2d(c.gD, c.d))
 
     def _rowconv(self, c):
         """RowConnected2D (reference custom.py:695-837): per-row filters"""
@@ -568,4 +611,4 @@ class BackwardPass(object):
 
     adjoints = {'d2s': _d2s, 'conv': _conv, 'rowconv': _rowconv, 'dense': _dense, 'dropout': _dropout, 'bn': _bn,
                 'lstm': _lstm, 'copy': _copy, 'pad': _pad, 'maxpool': _maxpool, 'avgpool': _avgpool, 'upsample': _upsample,
-                'bilinear': _bilinear, 'act': _act, 'merge': _merge}
+                'bilinear': _bilinear, 'act': _act, 'merge': _merge, 'd2sc': _d2sc, 'crop': _crop}

@@ -22,6 +22,9 @@ struct dlwp_rollout {
 
 namespace {
 
+// derived-kernel ops: parameter buffers only, run once at the head of the graph
+bool is_weight_op(const dlwp_op& op) { return op.kind == DLWP_OP_PHASE_WEIGHTS || op.kind == DLWP_OP_TCONV_WEIGHTS; }
+
 bool is_step(const dlwp_op& op) { return op.kind == DLWP_OP_CONV2D && op.conv.lstm_f > 0 && op.src2 != DLWP_BUF_NONE; }
 
 int enqueue_op(dlwp_handle_t h, const dlwp_op& op, const void* src, void* dst, const void* w, const void* b, int dtype,
@@ -64,6 +67,15 @@ int enqueue_op(dlwp_handle_t h, const dlwp_op& op, const void* src, void* dst, c
     case DLWP_OP_PHASE_WEIGHTS:   // src / dst / b / aux[0] are parameter buffers (resolved by the caller)
       return dlwp_phase_weights(h, src, b, dst, aux ? aux[0] : nullptr, op.conv.kh, op.conv.kw, op.xs.c, op.conv.cout,
                                 op.conv.halo.top, op.conv.halo.left, dtype, (void*)s);
+    case DLWP_OP_TCONV_WEIGHTS:   // (buffers as for DLWP_OP_PHASE_WEIGHTS)
+      return dlwp_tconv_weights(h, src, b, dst, aux ? aux[0] : nullptr, op.conv.kh, op.conv.kw, op.xs.c, op.conv.cout, op.aux[1],
+                                op.aux[2], dtype, (void*)s);
+    case DLWP_OP_DEPTH2SPACE_CROP:
+      return dlwp_depth_to_space2_crop(h, src, dst, op.xs.n, op.xs.c, op.xs.h, op.xs.w, op.aux[0], op.aux[1], op.aux[2], op.aux[3],
+                                       op.conv.out_c_off, op.conv.out_c_total > 0 ? op.conv.out_c_total : op.xs.c, dtype, (void*)s);
+    case DLWP_OP_CROP2D:          // keras Cropping2D: the adjoint of zero padding ("zero drops")
+      return dlwp_pad2d_bwd(h, src, dst, op.xs.n * op.xs.c, op.xs.h - op.pad.top - op.pad.bottom,
+                            op.xs.w - op.pad.left - op.pad.right, 1, op.pad, dtype, (void*)s);
     case DLWP_OP_BATCHNORM: {   // w / b = gamma / beta (nullable), aux = moving mean, moving variance; epsilon in op.aux[2]
       float eps;
       memcpy(&eps, &op.aux[2], sizeof(float));
@@ -139,7 +151,7 @@ size_t dlwp_rollout_workspace_bytes(dlwp_handle_t h, const dlwp_op* plan, int n_
   if (!h || !plan || n_ops <= 0 || groups < 1) return 0;
   int members = 0;
   for (int i = 0; i < n_ops && !members; ++i)
-    if (plan[i].kind != DLWP_OP_PHASE_WEIGHTS) members = plan[i].xs.n;
+    if (!is_weight_op(plan[i])) members = plan[i].xs.n;
   if (members <= 0 || members % groups) return 0;
   return (size_t)prepared_floats(h, plan, n_ops, members / groups, nullptr) * sizeof(float);
 }
@@ -176,7 +188,7 @@ static int create_impl(dlwp_handle_t h, const dlwp_op* plan_in, int n_ops, void*
   DLWP_CHECK_ARG(groups == 1 || buffer_sample_bytes, "dlwp_rollout_create: member groups need the per-member buffer sizes");
   int members = 0;
   for (int i = 0; i < n_ops; ++i)
-    if (plan_in[i].kind != DLWP_OP_PHASE_WEIGHTS) {
+    if (!is_weight_op(plan_in[i])) {
       members = plan_in[i].xs.n;
       break;
     }
@@ -186,7 +198,7 @@ static int create_impl(dlwp_handle_t h, const dlwp_op* plan_in, int n_ops, void*
   // the plan of ONE group: every member-indexed op runs on gn members (tile choice and prepared weights follow from that)
   std::vector<dlwp_op> gplan(plan_in, plan_in + n_ops);
   for (int i = 0; i < n_ops; ++i)
-    if (gplan[i].kind != DLWP_OP_PHASE_WEIGHTS) {
+    if (!is_weight_op(gplan[i])) {
       DLWP_CHECK_ARG(gplan[i].xs.n == members, "rollout op %d: batch %d differs from %d", i, gplan[i].xs.n, members);
       gplan[i].xs.n = gn;
     }
@@ -210,7 +222,7 @@ static int create_impl(dlwp_handle_t h, const dlwp_op* plan_in, int n_ops, void*
     if (op.kind == DLWP_OP_CONV2D || op.kind == DLWP_OP_ROWCONV2D || op.kind == DLWP_OP_DENSE)
       DLWP_CHECK_ARG(op.w >= 0 && op.w < n_buffers && op.b >= -1 && op.b < n_buffers,
                      "rollout op %d: weight/bias buffer out of range", i);
-    if (op.kind == DLWP_OP_PHASE_WEIGHTS)
+    if (is_weight_op(op))
       DLWP_CHECK_ARG(op.src >= 0 && op.dst >= 0 && op.b >= -1 && op.b < n_buffers &&
                          (op.aux[0] == DLWP_BUF_NONE || (op.aux[0] >= 0 && op.aux[0] < n_buffers)),
                      "rollout op %d: phase-weights buffers out of range", i);
@@ -285,7 +297,7 @@ static int create_impl(dlwp_handle_t h, const dlwp_op* plan_in, int n_ops, void*
   // derived (phase-summed) kernels first: the convolutions reading them may be prepared right behind
   auto prepare = [&](hipStream_t s) {
     for (int i = 0; i < n_ops && rc == DLWP_OK; ++i)
-      if (plan[i].kind == DLWP_OP_PHASE_WEIGHTS) {
+      if (is_weight_op(plan[i])) {
         const dlwp_op& op = plan[i];
         void* aux1[3] = {op.aux[0] == DLWP_BUF_NONE ? nullptr : buffers[op.aux[0]], nullptr, nullptr};
         rc = enqueue_op(h, op, buffers[op.src], buffers[op.dst], nullptr, op.b >= 0 ? buffers[op.b] : nullptr, dtype, s, aux1);
@@ -306,7 +318,7 @@ static int create_impl(dlwp_handle_t h, const dlwp_op* plan_in, int n_ops, void*
     for (int t = 0; t < ncalls && rc == DLWP_OK; ++t) {
       for (int i = 0; i < n_ops && rc == DLWP_OK; ++i) {
         const dlwp_op& op = plan[i];
-        if (op.kind == DLWP_OP_PHASE_WEIGHTS) continue;   // done once, at the head of the graph
+        if (is_weight_op(op)) continue;   // done once, at the head of the graph
         const bool weighted = op.kind == DLWP_OP_CONV2D || op.kind == DLWP_OP_ROWCONV2D || op.kind == DLWP_OP_DENSE;
         const bool scale = op.kind == DLWP_OP_SCALE;
         const bool bn = op.kind == DLWP_OP_BATCHNORM;

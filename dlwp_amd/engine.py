@@ -128,7 +128,7 @@ class Executor(object):
                     descs.append(ops.make_conv(f, kh, kw, dil, ops.make_pad(*op.halo), op.act,
                                                op.in_c_off, op.in_c_total, op.out_c_off, op.out_c_total, op.src_mode,
                                                op.out_pool, op.out_d2s, op.lstm_f, op.rec_act))
-                elif op.kind == 'pad':
+                elif op.kind in ('pad', 'crop'):
                     descs.append(ops.make_pad(*op.halo))
                 else:
                     descs.append(None)
@@ -279,7 +279,7 @@ class Executor(object):
         pooled_too = self._pooled_too() if prepared is not None or skip_ops else {}
         done = set()
         for k, (op, d) in enumerate(zip(self.plan.ops, self._descriptors())):
-            if (op.kind == 'phasew' and skip_phasew) or k in skip_ops or k in done:
+            if (op.kind in ('phasew', 'tphasew') and skip_phasew) or k in skip_ops or k in done:
                 continue
             src, dst = res(op.src), res(op.dst)
             if k in pooled_too:
@@ -319,6 +319,15 @@ class Executor(object):
                 continue
             elif op.kind == 'd2s':
                 ops.depth_to_space2(src, op.xs[0], out=dst, c_off=op.out_c_off)
+            elif op.kind == 'tphasew':        # Conv2DTranspose: kernel -> the kernel of its 4 F phase channels
+                w2, b2 = self.phase_buffers()[op.wparam]
+                ops.tconv_weights(op.layer.kernel, op.layer.bias, w2=w2, b2=b2)
+                continue
+            elif op.kind == 'd2sc':
+                ops.depth_to_space2_crop(src, op.xs[0], op.crop[0], op.crop[1], op.out_shape[1], op.out_shape[2], out=dst,
+                                         c_off=op.out_c_off)
+            elif op.kind == 'crop':
+                ops.crop2d(src, d, out=dst)
             elif op.kind == 'pad':
                 if op.inner > 1:
                     hh, ww = op.xs[1], op.xs[2]
@@ -535,7 +544,8 @@ class Executor(object):
                 'upsample': _lib.OP_UPSAMPLE2, 'copy': _lib.OP_COPYCH, 'lstm': _lib.OP_LSTM_GATES,
                 'phasew': _lib.OP_PHASE_WEIGHTS, 'd2s': _lib.OP_DEPTH2SPACE, 'rowconv': _lib.OP_ROWCONV2D,
                 'bn': _lib.OP_BATCHNORM, 'dense': _lib.OP_DENSE, 'scale': _lib.OP_SCALE, 'act': _lib.OP_ACTIVATION,
-                'merge': _lib.OP_MERGE, 'avgpool': _lib.OP_AVGPOOL2, 'bilinear': _lib.OP_BILINEAR2}
+                'merge': _lib.OP_MERGE, 'avgpool': _lib.OP_AVGPOOL2, 'bilinear': _lib.OP_BILINEAR2,
+                'tphasew': _lib.OP_TCONV_WEIGHTS, 'd2sc': _lib.OP_DEPTH2SPACE_CROP, 'crop': _lib.OP_CROP2D}
         arr = (_lib.Op * len(self.plan.ops))()
         for k, (op, d) in enumerate(zip(self.plan.ops, self._descriptors())):
             o = arr[k]
@@ -570,6 +580,18 @@ class Executor(object):
                 o.xs = _lib.Shape4(n, op.xs[0], 1, 1)
             elif op.kind == 'd2s':
                 o.conv.out_c_off, o.conv.out_c_total = op.out_c_off, op.out_c_total
+            elif op.kind == 'tphasew':                 # Conv2DTranspose kernel -> derived kernel, once at the head of the graph
+                o.src, o.b = widx[id(op.layer)]
+                o.dst, b2i = pidx[op.wparam]
+                o.aux[0] = b2i if b2i >= 0 else _lib.BUF_NONE
+                o.conv.cout, o.conv.kh, o.conv.kw = op.layer.filters, op.layer.kernel_size[0], op.layer.kernel_size[1]
+                o.aux[1], o.aux[2] = self.plan.phase_params[op.wparam]['w2_shape'][:2]      # the stored taps
+                o.xs = _lib.Shape4(n, op.xs[0], 1, 1)
+            elif op.kind == 'd2sc':                    # the cropping interleave: aux = top, left, out_h, out_w
+                o.conv.out_c_off, o.conv.out_c_total = op.out_c_off, op.out_c_total
+                o.aux[0], o.aux[1], o.aux[2], o.aux[3] = op.crop[0], op.crop[1], op.out_shape[1], op.out_shape[2]
+            elif op.kind == 'crop':
+                o.pad = d
             elif op.kind == 'dense':
                 o.w, o.b = didx[id(op.layer)]
                 o.conv.cout, o.conv.act = op.layer.units, op.act

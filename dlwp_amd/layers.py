@@ -784,6 +784,148 @@ class UpSampling2D(Layer):
         return cfg
 
 
+def _deconv_length(length, k, padding):
+    """Keras' deconv_length for stride 2 and no output_padding: 'valid' 2 n + max(k - 2, 0), 'same' 2 n."""
+    return 2 * int(length) + (max(int(k) - 2, 0) if padding == 'valid' else 0)
+
+
+class Conv2DTranspose(Layer):
+    """keras.layers.Conv2DTranspose with strides=2: the learned up-sampling of a decoder.  'valid' | 'same', bias, activation in
+    {None,'linear','tanh','relu'}, data_format='channels_first'.  y_full[o, 2i+u, 2j+v] += x[c, i, j] K[u, v, o, c] (no flip) on
+    2h + max(kh-2, 0) rows; 'same' keeps rows [pt, pt + 2h), pt = max(kh-2, 0) // 2 -- the gradient of a SAME-padded stride-2
+    convolution.  Weights: kernel (kh, kw, filters, cin) glorot_uniform (Keras' order: filters before input channels), bias
+    (filters,) zeros.  Runs as one stride-1 convolution with 4 x filters phase channels + a cropping interleave (csrc/tconv.hip)."""
+
+    def __init__(self, filters, kernel_size, strides=(2, 2), padding='valid', output_padding=None, data_format=None,
+                 dilation_rate=(1, 1), activation=None, use_bias=True, kernel_initializer='glorot_uniform',
+                 bias_initializer='zeros', kernel_regularizer=None, bias_regularizer=None, activity_regularizer=None,
+                 kernel_constraint=None, bias_constraint=None, **kwargs):
+        super(Conv2DTranspose, self).__init__(**kwargs)
+        self.filters = int(filters)
+        ks = (kernel_size, kernel_size) if isinstance(kernel_size, (int, np.integer)) else tuple(kernel_size)
+        st = (strides, strides) if isinstance(strides, (int, np.integer)) else tuple(strides)
+        dl = (dilation_rate, dilation_rate) if isinstance(dilation_rate, (int, np.integer)) else tuple(dilation_rate)
+        if len(ks) != 2 or len(st) != 2 or len(dl) != 2:
+            raise ValueError('kernel_size / strides / dilation_rate must be an int or a pair')
+        if any(int(k) <= 0 for k in ks):
+            raise ValueError('Conv2DTranspose: kernel_size %r' % (ks,))
+        if tuple(st) != (2, 2):
+            raise NotImplementedError('Conv2DTranspose: only strides=2 is implemented, got %r' % (tuple(st),))
+        if tuple(dl) != (1, 1):
+            raise NotImplementedError('Conv2DTranspose: dilation_rate %r is not implemented (1 is)' % (tuple(dl),))
+        if output_padding is not None:
+            raise NotImplementedError('Conv2DTranspose: output_padding=%r is not implemented (None is)' % (output_padding,))
+        if padding not in ('valid', 'same'):
+            raise ValueError("Conv2DTranspose padding must be 'valid' or 'same'")
+        if callable(activation):
+            activation = getattr(activation, '__name__', None)
+        if activation not in (None, 'linear', 'tanh', 'relu'):
+            raise NotImplementedError('Conv2DTranspose activation %r is not implemented (linear, tanh, relu are)' % (activation,))
+        if kernel_initializer not in ('glorot_uniform', 'zeros') or bias_initializer not in ('zeros',):
+            raise NotImplementedError('Conv2DTranspose initialisers: kernel glorot_uniform|zeros, bias zeros')
+        self.kernel_size = tuple(int(k) for k in ks)
+        self.strides = (2, 2)
+        self.padding = padding
+        self.output_padding = None
+        self.data_format = normalize_data_format(data_format)
+        if self.data_format != 'channels_first':
+            raise NotImplementedError("Conv2DTranspose: data_format='channels_first' is required (pass it explicitly; Keras' "
+                                      "default is channels_last)")
+        self.dilation_rate = (1, 1)
+        self.activation = activation or 'linear'
+        self.use_bias = bool(use_bias)
+        self.kernel_initializer = kernel_initializer
+        self.kernel_regularizer = kernel_regularizer   # l2 handled by the trainer when it is a dlwp_amd.regularizers.L2
+        self.kernel = None
+        self.bias = None
+
+    def compute_output_shape(self, s):
+        if len(s) != 3:
+            raise NotImplementedError('%s (Conv2DTranspose) expects a 4D input, got the per-sample shape %r' % (self.name, s))
+        c, h, w = s
+        return (self.filters, _deconv_length(h, self.kernel_size[0], self.padding),
+                _deconv_length(w, self.kernel_size[1], self.padding))
+
+    def build(self, input_shape, device, rng):
+        import torch
+        if self.built:
+            if self.kernel.shape[3] != input_shape[0]:
+                raise ValueError('%s was built for %d input channels, now called with %d' %
+                                 (self.name, self.kernel.shape[3], input_shape[0]))
+            return
+        kh, kw = self.kernel_size
+        cin = int(input_shape[0])
+        if self.kernel_initializer == 'glorot_uniform':      # Keras' fans of (kh, kw, filters, cin): the limit is symmetric in them
+            limit = math.sqrt(6.0 / (kh * kw * self.filters + kh * kw * cin))
+            k = rng.uniform(-limit, limit, size=(kh, kw, self.filters, cin)).astype(np.float32)
+        else:
+            k = np.zeros((kh, kw, self.filters, cin), dtype=np.float32)
+        self.kernel = torch.from_numpy(k).to(device)
+        self._weights = [('kernel', self.kernel)]
+        if self.use_bias:
+            self.bias = torch.zeros(self.filters, dtype=torch.float32, device=device)
+            self._weights.append(('bias', self.bias))
+        self.built = True
+
+    def get_config(self):
+        cfg = super(Conv2DTranspose, self).get_config()
+        cfg.update({'filters': self.filters, 'kernel_size': self.kernel_size, 'strides': self.strides, 'padding': self.padding,
+                    'output_padding': None, 'data_format': self.data_format, 'dilation_rate': self.dilation_rate,
+                    'activation': self.activation, 'use_bias': self.use_bias})
+        return cfg
+
+
+def _normalize_cropping(cropping):
+    """Keras Cropping2D: int | (ch, cw) | ((top, bottom), (left, right))  ->  ((top, bottom), (left, right))."""
+    if isinstance(cropping, (int, np.integer)):
+        out = ((int(cropping),) * 2,) * 2
+    else:
+        if not hasattr(cropping, '__len__') or len(cropping) != 2:
+            raise ValueError('`cropping` should have two elements. Found: %r' % (cropping,))
+        out = []
+        for c in cropping:
+            if isinstance(c, (int, np.integer)):
+                out.append((int(c), int(c)))
+            else:
+                c = tuple(int(v) for v in c)
+                if len(c) != 2:
+                    raise ValueError('`cropping` should be either an int, a tuple of 2 ints or a tuple of 2 tuples of 2 ints. '
+                                     'Found: %r' % (cropping,))
+                out.append(c)
+        out = tuple(out)
+    if any(v < 0 for c in out for v in c):
+        raise ValueError('negative cropping is not supported: %r' % (cropping,))
+    return out
+
+
+class Cropping2D(Layer):
+    """keras.layers.Cropping2D: drops rows / columns at the borders -- trims a decoder's output, or takes the pole row / the
+    periodic halo off again so that an odd grid (73 x 144) runs through a pool / up-sample stack.  data_format='channels_first'.
+    Its forward is the adjoint of zero padding (dlwp_pad2d_bwd, 'zero drops'), its gradient zero padding.  No weights."""
+
+    def __init__(self, cropping=((0, 0), (0, 0)), data_format=None, **kwargs):
+        super(Cropping2D, self).__init__(**kwargs)
+        self.cropping = _normalize_cropping(cropping)
+        self.data_format = normalize_data_format(data_format)
+        if self.data_format != 'channels_first':
+            raise NotImplementedError("Cropping2D: data_format='channels_first' is required (pass it explicitly; Keras' default "
+                                      "is channels_last)")
+
+    def compute_output_shape(self, s):
+        if len(s) != 3:
+            raise NotImplementedError('%s (Cropping2D) expects a 4D input, got the per-sample shape %r' % (self.name, s))
+        (t, b), (l, r) = self.cropping
+        h, w = s[1] - t - b, s[2] - l - r
+        if h <= 0 or w <= 0:
+            raise ValueError('%s (Cropping2D): cropping %r leaves nothing of the input %r' % (self.name, self.cropping, tuple(s)))
+        return (s[0], h, w)
+
+    def get_config(self):
+        cfg = super(Cropping2D, self).get_config()
+        cfg.update({'cropping': self.cropping, 'data_format': self.data_format})
+        return cfg
+
+
 class Reshape(Layer):
     """keras.layers.Reshape(target_shape): a relabelling of the contiguous per-sample block (examples/train.py:220)."""
 

@@ -648,6 +648,89 @@ def phase_weights_bwd(dw2, db2, dw, db, pad_top, pad_left, accumulate=False):
     return dw
 
 
+def tconv_geometry(k, padding, length):
+    """(T, crop, out_len) of one axis of Conv2DTranspose(k, strides=2, padding): T = ceil(k / 2) taps on the source, the output's
+    offset in the interleaved phase tensor (2 (length + T - 1) long) and the output length (include/dlwp_hip.h:
+    dlwp_tconv_geometry; host only)."""
+    t, crop, out = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    _lib.check(_lib.lib.dlwp_tconv_geometry(int(k), 1 if padding == 'same' else 0, int(length), ctypes.byref(t),
+                                            ctypes.byref(crop), ctypes.byref(out)))
+    return t.value, crop.value, out.value
+
+
+def tconv_weights(k_hwoi, bias, w2=None, b2=None, taps=None):
+    """Kernels of a Conv2DTranspose(strides=2) restated as a stride-1 convolution with 4 F phase channels: K (kh, kw, F, cin) ->
+    w2 (sh, sw, cin, 4F), and the bias once per phase (include/dlwp_hip.h: dlwp_tconv_weights).  taps = (sh, sw) >= (Th, Tw): the
+    stored taps (those of w2 when it is given, else Th x Tw), the Th x Tw block at ((sh - Th) // 2, (sw - Tw) // 2)."""
+    _check_f32(k_hwoi, bias, w2, b2)
+    kh, kw, f, cin = k_hwoi.shape
+    sh, sw = taps if taps is not None else (tuple(w2.shape[:2]) if w2 is not None else ((kh + 1) // 2, (kw + 1) // 2))
+    if w2 is None:
+        w2 = torch.empty((sh, sw, cin, 4 * f), dtype=torch.float32, device=k_hwoi.device)
+    if b2 is None and bias is not None:
+        b2 = torch.empty(4 * f, dtype=torch.float32, device=k_hwoi.device)
+    if tuple(w2.shape) != (sh, sw, cin, 4 * f) or (b2 is not None and b2.numel() != 4 * f):
+        raise ValueError('tconv_weights: derived kernel %r does not belong to a kernel %r' % (tuple(w2.shape), tuple(k_hwoi.shape)))
+    _lib.check(_lib.lib.dlwp_tconv_weights(_lib.handle(_dev(k_hwoi)), _ptr(k_hwoi), _ptr(bias), _ptr(w2), _ptr(b2), kh, kw, cin, f,
+                                           int(sh), int(sw), _lib.F32, _stream(k_hwoi)))
+    return w2, b2
+
+
+def tconv_weights_bwd(dw2, dk, accumulate=False):
+    """Adjoint of tconv_weights: dk (kh, kw, F, cin) (+)= the gather of dw2 (sh, sw, cin, 4F)."""
+    _check_f32(dw2, dk)
+    kh, kw, f, cin = dk.shape
+    sh, sw = int(dw2.shape[0]), int(dw2.shape[1])
+    if dw2.dim() != 4 or tuple(dw2.shape[2:]) != (cin, 4 * f) or sh < (kh + 1) // 2 or sw < (kw + 1) // 2:
+        raise ValueError('tconv_weights_bwd: derived gradient %r does not belong to a kernel %r' % (tuple(dw2.shape), tuple(dk.shape)))
+    _lib.check(_lib.lib.dlwp_tconv_weights_bwd(_lib.handle(_dev(dw2)), _ptr(dw2), _ptr(dk), kh, kw, cin, f, sh, sw,
+                                               1 if accumulate else 0, _lib.F32, _stream(dw2)))
+    return dk
+
+
+def depth_to_space2_crop(src, f, top, left, out_h, out_w, out=None, c_off=0):
+    """(n, 4F, hp, wp) phase-major -> (n, F, out_h, out_w): rows [top, top + out_h) and columns [left, left + out_w) of the
+    depth-to-space image, out[:, c_off + co, r, s] = src[:, (2((r+top)&1) + ((s+left)&1))*F + co, (r+top)>>1, (s+left)>>1]."""
+    _check_f32(src, out)
+    n, c4, hp, wp = src.shape
+    if c4 != 4 * f:
+        raise ValueError('depth_to_space2_crop: %d channels is not 4 x %d' % (c4, f))
+    if out is None:
+        out = torch.empty((n, f, int(out_h), int(out_w)), dtype=torch.float32, device=src.device)
+    if tuple(out.shape[2:]) != (int(out_h), int(out_w)) or out.shape[0] != n:
+        raise ValueError('depth_to_space2_crop: output shape %r' % (tuple(out.shape),))
+    _lib.check(_lib.lib.dlwp_depth_to_space2_crop(_lib.handle(_dev(src)), _ptr(src), _ptr(out), n, int(f), hp, wp, int(top),
+                                                  int(left), int(out_h), int(out_w), int(c_off), out.shape[1], _lib.F32,
+                                                  _stream(src)))
+    return out
+
+
+def space_to_depth2_fill(src, f, hp, wp, top, left, c_off=0, out=None):
+    """Adjoint of depth_to_space2_crop: (n, c_total, H, W)[c_off:+f] -> (n, 4f, hp, wp) phase-major; every element is written,
+    +0 where the crop dropped the pixel."""
+    _check_f32(src, out)
+    n, c_total, hh, ww = src.shape
+    if out is None:
+        out = torch.empty((n, 4 * f, int(hp), int(wp)), dtype=torch.float32, device=src.device)
+    if tuple(out.shape) != (n, 4 * f, int(hp), int(wp)):
+        raise ValueError('space_to_depth2_fill: output shape %r' % (tuple(out.shape),))
+    _lib.check(_lib.lib.dlwp_space_to_depth2_fill(_lib.handle(_dev(src)), _ptr(src), _ptr(out), n, int(f), int(hp), int(wp),
+                                                  int(top), int(left), hh, ww, int(c_off), c_total, _lib.F32, _stream(src)))
+    return out
+
+
+def crop2d(x, crop, out=None):
+    """keras Cropping2D on NCHW: the adjoint of zero padding (dlwp_pad2d_bwd with PAD_ZERO: 'zero drops').  crop: a Pad2d."""
+    _check_f32(x, out)
+    n, c, h, w = x.shape
+    ho, wo = h - crop.top - crop.bottom, w - crop.left - crop.right
+    if ho <= 0 or wo <= 0:
+        raise ValueError('crop2d: nothing is left of %d x %d' % (h, w))
+    y = out if out is not None else torch.empty((n, c, ho, wo), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib.dlwp_pad2d_bwd(_lib.handle(_dev(x)), _ptr(x), _ptr(y), n * c, ho, wo, 1, crop, _lib.F32, _stream(x)))
+    return y
+
+
 def uses_bf16_weights(xs, cd, dtype):
     """Does conv2d on an input of shape xs = (n, c, h, w) stored as `dtype` (a _lib.dtype_io code) multiply with weights
     rounded to bfloat16 (the bf16 matrix-core kernels)?  Host logic only."""

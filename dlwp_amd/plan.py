@@ -66,7 +66,7 @@ class View(object):
 
 class PlanOp(object):
     """One launch.  kind in {'conv','rowconv','pad','maxpool','avgpool','upsample','bilinear','copy','lstm','phasew','d2s','bn',
-    'dense','dropout','scale','act','merge'}."""
+    'dense','dropout','scale','act','merge','tphasew','d2sc','crop'}."""
 
     def __init__(self, kind, src, dst, xs, **kw):
         self.kind, self.src, self.dst = kind, src, dst
@@ -102,6 +102,9 @@ class PlanOp(object):
         # scale only (inference plans with an input / output transform): 'head' = imputer + scaler transform of the model input,
         # 'tail' = the scaler's inverse transform of the model output; the executor holds the parameters
         self.role = kw.pop('role', None)
+        # d2sc only (the cropping interleave of a Conv2DTranspose): (top, left) of the window [top, +ho) x [left, +wo) it takes of
+        # the depth-to-space image of its source; layer / act = the layer's, for the backward (bias gradient at full resolution)
+        self.crop = kw.pop('crop', None)
         assert not kw, kw
 
     @property
@@ -127,6 +130,10 @@ class PlanOp(object):
             extra = ' %s %r' % (self.layer.name, self.layer.eltwise)
         if self.kind == 'merge':
             extra = ' %s %s%r' % (self.layer.name, self.layer.kind, (self.src,) + tuple(self.aux))
+        if self.kind == 'd2sc':
+            extra = ' %s crop%r -> %r' % (self.layer.name, tuple(self.crop), tuple(self.out_shape))
+        if self.kind == 'crop':
+            extra = ' crop%r' % (tuple(self.halo[:4]),)
         return '<%s %s -> %s xs=%s%s>' % (self.kind, self.src, self.dst, self.xs, extra)
 
 
@@ -273,6 +280,17 @@ def _phase_geometry(k, pad):
     top / left halo of `pad` (csrc/phase.hip, ops.phase_geometry)."""
     offs = [(a + u - pad) // 2 for a in (0, 1) for u in range(k)]
     return max(offs) - min(offs) + 1, min(offs), max(offs)
+
+
+def tconv_taps(th, tw):
+    """(sh, sw): the taps the derived kernel of a Conv2DTranspose is STORED with -- 3 x 3 where T <= 3 (k <= 6), 5 x 5 where
+    T <= 5 (k <= 10): the sizes the matrix-core forward and weight-gradient kernels exist for (csrc/tconv.hip); T itself beyond that
+    (the forward then runs on the direct kernel and there is no weight gradient).  DLWP_TCONV_TAPS=exact keeps T x T (A/B runs of
+    the forward)."""
+    t = max(int(th), int(tw))
+    if os.environ.get('DLWP_TCONV_TAPS') == 'exact' or t > 5:
+        return int(th), int(tw)
+    return (3, 3) if t <= 3 else (5, 5)
 
 
 def toposort(outputs):
@@ -753,6 +771,98 @@ def build_plan(inputs, outputs, inference=False, fuse_d2s=True, fuse_lstm=False,
                         act=ACT[lay.activation], in_c_off=v.c_off, in_c_total=v.c_total, out_c_off=0,
                         out_c_total=lay.filters, out_shape=(lay.filters, ho, wo)))
               views[t.uid] = View(dst, 0, lay.filters, lay.filters, ho, wo)
+        elif isinstance(lay, L.Conv2DTranspose):
+            # keras Conv2DTranspose(strides=2) (csrc/tconv.hip): the 4 output phases are stride-1 cross-correlations of the layer's
+            # input (zero halo T - 1, T = ceil(k / 2)) with kernels that are a permutation of the layer's own (stored with the
+            # 3 x 3 / 5 x 5 taps the matrix-core kernels exist for, zero taps and a wider zero halo around: tconv_taps), so it runs as
+            # 'tphasew' (kernel -> derived kernel; plan.phase_params) + ONE convolution with 4 x filters channels (bias and
+            # activation in its epilogue) + 'd2sc', an interleave that also crops ('same' padding, the extra row / column of an odd
+            # kernel).  An inference plan lets the convolution store the phases interleaved where a kernel can and nothing is cropped.
+            if any(p['layer'] is lay for p in plan.phase_params):
+                raise NotImplementedError('%s: a Conv2DTranspose layer applied more than once is not implemented' % lay.name)
+            v = ins[0]
+            if v.shape is not None:
+                raise NotImplementedError('%s (Conv2DTranspose) on a reshaped (non-3D) tensor %r' % (lay.name, v.shape))
+            if v.src_mode != SRC_DIRECT:         # (its convolution reads a stored tensor; a halo in front may stay lazy)
+                v = materialize(v.copy(halo=NO_HALO)).copy(halo=v.halo)
+            kh, kw = lay.kernel_size
+            th, tw = (kh + 1) // 2, (kw + 1) // 2
+            sh, sw = tconv_taps(th, tw)
+            oh, ow = (sh - th) // 2, (sw - tw) // 2             # where the Th x Tw block sits in the stored taps
+            own = ((th - 1 + oh, th - 1 + sh - th - oh), (tw - 1 + ow, tw - 1 + sw - tw - ow))
+            halo = _compose_halo(v.halo, own, PAD_ZERO)
+            if halo is None:
+                v = materialize(v)
+                halo = Halo(own[0][0], own[0][1], own[1][0], own[1][1], PAD_ZERO, PAD_ZERO)
+            _, hl, wl = v.copy(halo=halo).logical
+            hp, wp = hl - sh + 1, wl - sw + 1                   # the phase tensor: (4F, h + Th - 1, w + Tw - 1)
+            hin, win = hp - th + 1, wp - tw + 1                 # what the layer sees as its input
+            same = lay.padding == 'same'
+            top, left = (max(kh - 2, 0) // 2, max(kw - 2, 0) // 2) if same else (0, 0)
+            ho = 2 * hin + (0 if same else max(kh - 2, 0))
+            wo = 2 * win + (0 if same else max(kw - 2, 0))
+            f = lay.filters
+            alg = 2 * hin * win * f * v.c * kh * kw
+            pidx = len(plan.phase_params)
+            plan.phase_params.append({'layer': lay, 'w2_shape': (sh, sw, v.c, 4 * f), 'bias': lay.use_bias, 'kind': 'tconv'})
+            emit(PlanOp('tphasew', STATE_IN, STATE_IN, (v.c, 0, 0), layer=lay, wparam=pidx, out_shape=(0, 0, 0)))
+            if outs:
+                dst = OUT(outs[0])
+                plan.output_store[outs[0]] = (f, ho, wo)
+            else:
+                dst = plan.new_buffer(f, ho, wo)
+            no_crop = top == 0 and left == 0 and ho == 2 * hp and wo == 2 * wp
+            fold = (inference and fuse_d2s and no_crop and
+                    _supports_out_d2s((v.c, v.h, v.w), 4 * f, (sh, sw), halo, ACT[lay.activation], v.c_off, v.c_total))
+            if fold:             # the convolution's epilogue stores the phases interleaved: no interleave pass
+                op = PlanOp('conv', v.buf, dst, (v.c, v.h, v.w), layer=lay, halo=halo, src_mode=SRC_DIRECT,
+                            act=ACT[lay.activation], in_c_off=v.c_off, in_c_total=v.c_total, out_c_off=0, out_c_total=f,
+                            out_shape=(f, ho, wo), dil=(1, 1), ksize=(sh, sw), filters=4 * f, wparam=pidx, alg_flops=alg,
+                            out_d2s=True)
+                op.conv_out_shape = (4 * f, hp, wp)
+                emit(op)
+            else:
+                tmp = plan.new_buffer(4 * f, hp, wp)
+                emit(PlanOp('conv', v.buf, tmp, (v.c, v.h, v.w), layer=lay, halo=halo, src_mode=SRC_DIRECT,
+                            act=ACT[lay.activation], in_c_off=v.c_off, in_c_total=v.c_total, out_c_off=0, out_c_total=4 * f,
+                            out_shape=(4 * f, hp, wp), dil=(1, 1), ksize=(sh, sw), filters=4 * f, wparam=pidx, alg_flops=alg))
+                emit(PlanOp('d2sc', tmp, dst, (f, hp, wp), layer=lay, act=ACT[lay.activation], crop=(top, left), out_c_off=0,
+                            out_c_total=f, out_shape=(f, ho, wo)))
+            views[t.uid] = View(dst, 0, f, f, ho, wo)
+        elif isinstance(lay, L.Cropping2D):
+            # keras Cropping2D: one launch of its own on a whole stored buffer (the adjoint of zero padding) -- or, directly behind
+            # a Conv2DTranspose whose interleave nothing else reads, a smaller window of that interleave (moves only: same bits)
+            v = ins[0]
+            if v.shape is not None:
+                raise NotImplementedError('%s (Cropping2D) on a reshaped (non-3D) tensor %r' % (lay.name, v.shape))
+            (ct, cb), (cl, cr) = lay.cropping
+            v = materialize(v)
+            if not v.full:
+                v = materialize(v, dst=plan.new_buffer(*v.logical))
+            ho, wo = v.h - ct - cb, v.w - cl - cr
+            if ho <= 0 or wo <= 0:
+                raise ValueError('%s (Cropping2D): cropping %r leaves nothing of %d x %d' % (lay.name, lay.cropping, v.h, v.w))
+            writers = [op for op in plan.ops if op.dst == v.buf]
+            w0 = writers[0] if len(writers) == 1 else None
+            if (w0 is not None and w0.kind == 'd2sc' and v.buf >= 0 and consumers[t.inputs[0].uid] == 1 and
+                    not out_index.get(t.inputs[0].uid) and not any(op.src == v.buf for op in plan.ops)):
+                w0.crop = (w0.crop[0] + ct, w0.crop[1] + cl)
+                w0.out_shape = (v.c, ho, wo)
+                if outs:                             # the interleave writes the model's output slot itself
+                    w0.dst = OUT(outs[0])
+                    plan.output_store[outs[0]] = (v.c, ho, wo)
+                else:
+                    plan.buffers[v.buf] = (v.c, ho, wo)
+                views[t.uid] = View(w0.dst, 0, v.c, v.c, ho, wo)
+            else:
+                if outs:
+                    dst = OUT(outs[0])
+                    plan.output_store[outs[0]] = (v.c, ho, wo)
+                else:
+                    dst = plan.new_buffer(v.c, ho, wo)
+                emit(PlanOp('crop', v.buf, dst, (v.c, v.h, v.w), halo=Halo(ct, cb, cl, cr, PAD_ZERO, PAD_ZERO), out_c_total=v.c,
+                            out_shape=(v.c, ho, wo)))
+                views[t.uid] = View(dst, 0, v.c, v.c, ho, wo)
         elif isinstance(lay, L.RowConnected2D):
             # DLWP.custom.RowConnected2D (reference custom.py:695-837): per-row filters, dlwp_rowconv2d_fwd.  Its kernels read a
             # stored float32 tensor, directly or 2x up-sampled (a lazy pooling in front is materialised); the halo stays in the

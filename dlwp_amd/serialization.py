@@ -45,6 +45,14 @@ def _layer_config(lay):
                    data_format=lay.data_format, activation=lay.activation, use_bias=lay.use_bias)
         if isinstance(lay.kernel_regularizer, L1L2):
             cfg['kernel_regularizer'] = {'l2': lay.kernel_regularizer.l2}
+    elif isinstance(lay, L.Conv2DTranspose):
+        from .regularizers import L1L2
+        cfg.update(filters=lay.filters, kernel_size=list(lay.kernel_size), strides=list(lay.strides), padding=lay.padding,
+                   data_format=lay.data_format, activation=lay.activation, use_bias=lay.use_bias)
+        if isinstance(lay.kernel_regularizer, L1L2):
+            cfg['kernel_regularizer'] = {'l2': lay.kernel_regularizer.l2}
+    elif isinstance(lay, L.Cropping2D):
+        cfg.update(cropping=[list(c) for c in lay.cropping], data_format=lay.data_format)
     elif isinstance(lay, L.BatchNormalization):
         cfg.update(axis=lay.axis, momentum=lay.momentum, epsilon=lay.epsilon, center=lay.center, scale=lay.scale)
     elif isinstance(lay, L.Dense):
@@ -210,6 +218,13 @@ def _keras_layer_spec(lay):
         c.update(filters=lay.filters, kernel_size=list(lay.kernel_size), strides=list(lay.strides), padding=lay.padding,
                  data_format=lay.data_format, activation=lay.activation or 'linear', use_bias=lay.use_bias,
                  kernel_initializer=_GLOROT, bias_initializer=_ZEROS, kernel_regularizer=reg(lay.kernel_regularizer), **tail)
+    elif isinstance(lay, L.Conv2DTranspose):        # keras.layers.Conv2DTranspose.get_config(): Conv2D's keys + output_padding
+        c.update(filters=lay.filters, kernel_size=list(lay.kernel_size), strides=list(lay.strides), padding=lay.padding,
+                 data_format=lay.data_format, dilation_rate=[1, 1], activation=lay.activation or 'linear', use_bias=lay.use_bias,
+                 kernel_initializer=_GLOROT, bias_initializer=_ZEROS, kernel_regularizer=reg(lay.kernel_regularizer),
+                 output_padding=None, **tail)
+    elif isinstance(lay, L.Cropping2D):
+        c.update(cropping=[list(p) for p in lay.cropping], data_format=lay.data_format)
     elif isinstance(lay, L.BatchNormalization):
         init = {'zeros': _ZEROS, 'ones': _ONES}
         c.update(axis=lay.axis, momentum=lay.momentum, epsilon=lay.epsilon, center=lay.center, scale=lay.scale,

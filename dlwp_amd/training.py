@@ -584,6 +584,9 @@ class Trainer(object):
             if op.kind == 'phasew':
                 w2, b2 = ex.phase_buffers()[op.wparam]
                 ops.phase_weights(op.layer.kernel, op.layer.bias, op.halo.top, op.halo.left, w2=w2, b2=b2)
+            elif op.kind == 'tphasew':
+                w2, b2 = ex.phase_buffers()[op.wparam]
+                ops.tconv_weights(op.layer.kernel, op.layer.bias, w2=w2, b2=b2)
         cache = self._prep_cache.get(n)
         if cache is None:
             if len(self._prep_cache) > 4:

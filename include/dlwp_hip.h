@@ -581,6 +581,33 @@ int dlwp_phase_weights_bwd(dlwp_handle_t, const void* dw2, const void* db2, void
 int dlwp_space_to_depth2(dlwp_handle_t, const void* src, void* dst, int n, int f, int h, int w, int c_off, int c_total,
                          int dtype, void* stream);
 
+/* ---- keras Conv2DTranspose(filters, k, strides=2, padding='valid'|'same', data_format='channels_first') (tconv.hip):
+ *      y_full[n][o][2i+u][2j+v] += x[n][c][i][j] K[u][v][o][c], K (kh, kw, F, cin), on 2h + max(kh-2, 0) rows; 'same' keeps rows
+ *      [pt, pt + 2h), pt = max(kh-2, 0) / 2 (columns alike).  With T = ceil(k / 2) per axis, phase (a, b) of y_full is a stride-1
+ *      cross-correlation of x (zero halo T-1 on every side) with w2[ti][tj][c][(2a+b) F + o] = K[a + 2(Th-1-ti)][b + 2(Tw-1-tj)][o][c]
+ *      (zero where that index is >= kh / kw): ONE dlwp_conv2d_fwd with 4 F phase-major channels + a cropping interleave.
+ *      dlwp_tconv_geometry (host only), per axis: *t = T, *crop = the offset of the output in the interleaved phase tensor
+ *      (2 (len + T - 1) long), *out_len = the layer's output length.
+ *      dlwp_tconv_weights: K, bias (nullable) -> w2 (sh, sw, cin, 4F), b2 (4F, nullable: the bias once per phase).  sh >= Th and
+ *          sw >= Tw taps are stored: the Th x Tw block at offset (oh, ow) = ((sh - Th) / 2, (sw - Tw) / 2), zeros around it (the
+ *          matrix-core kernels exist for 3 x 3 and 5 x 5 taps); the convolution's zero halo is then T-1 + oh above / left and
+ *          T-1 + (s - T - oh) below / right.  sh = Th, sw = Tw: the map as written above.
+ *      dlwp_tconv_weights_bwd: dK[u][v][o][c] (+)= dw2[oh + Th-1-u/2][ow + Tw-1-v/2][c][(2(u&1) + (v&1)) F + o]  (a gather, no sums).
+ *      dlwp_depth_to_space2_crop: src (n, 4F, hp, wp) -> dst (n, c_total, out_h, out_w)[c_off:+F],
+ *          dst[n][c_off+o][r][s] = src[n][(2((r+top)&1) + ((s+left)&1)) F + o][(r+top)>>1][(s+left)>>1];  top + out_h <= 2 hp,
+ *          left + out_w <= 2 wp.
+ *      dlwp_space_to_depth2_fill: its adjoint, src (n, c_total, in_h, in_w)[c_off:+F] -> dst (n, 4F, hp, wp): every element of dst
+ *          is written, +0 where the crop dropped the pixel.  All float32, bit-exact (they move and zero-fill). */
+int dlwp_tconv_geometry(int k, int same, int len, int* t, int* crop, int* out_len);
+int dlwp_tconv_weights(dlwp_handle_t, const void* w, const void* bias, void* w2, void* b2, int kh, int kw, int cin, int f,
+                       int sh, int sw, int dtype, void* stream);
+int dlwp_tconv_weights_bwd(dlwp_handle_t, const void* dw2, void* dw, int kh, int kw, int cin, int f, int sh, int sw,
+                           int accumulate, int dtype, void* stream);
+int dlwp_depth_to_space2_crop(dlwp_handle_t, const void* src, void* dst, int n, int f, int hp, int wp, int top, int left,
+                              int out_h, int out_w, int c_off, int c_total, int dtype, void* stream);
+int dlwp_space_to_depth2_fill(dlwp_handle_t, const void* src, void* dst, int n, int f, int hp, int wp, int top, int left,
+                              int in_h, int in_w, int c_off, int c_total, int dtype, void* stream);
+
 /* ---- ConvLSTM2D cell update (keras ConvLSTM2DCell.call; call sites examples/train.py:148-155,
  *      examples/train_functional.py:207-219).  zx / zh: (n, 4F, h*w) gate pre-activations i | f | c | o from the input
  *      convolution (+bias) and the recurrent 'same' convolution of h_{t-1}; zh and c_prev may be NULL on the first step
@@ -789,6 +816,12 @@ int dlwp_scale_inv(dlwp_handle_t, const void* x, void* y, const void* shift, con
                                    * conv.act = DLWP_MERGE_*                                                                */
 #define DLWP_OP_AVGPOOL2  14      /* dlwp_avgpool2_fwd: src, dst, xs = (n, c, h, w) of src; aux[0] = storage dtype of both tensors */
 #define DLWP_OP_BILINEAR2 15      /* dlwp_upsample2_bilinear_fwd: src, dst, xs = (n, c, h, w) of src; aux[0] = storage dtype of both tensors */
+#define DLWP_OP_TCONV_WEIGHTS 16  /* dlwp_tconv_weights: buffers as for DLWP_OP_PHASE_WEIGHTS (aux[0] = b2 | -1000); conv = {cout = F,
+                                   * kh, kw}, xs.c = cin, aux[1] / aux[2] = sh / sw.  Run ONCE at the head of the rollout graph. */
+#define DLWP_OP_DEPTH2SPACE_CROP 17 /* dlwp_depth_to_space2_crop: src (n, 4F, hp, wp) -> dst window [conv.out_c_off, +F) of
+                                   * conv.out_c_total channels; xs = (n, F, hp, wp), aux = {top, left, out_h, out_w} */
+#define DLWP_OP_CROP2D    18      /* keras Cropping2D = dlwp_pad2d_bwd with DLWP_PAD_ZERO: src (n, c, h, w) -> dst (n, c, h - top -
+                                   * bottom, w - left - right); xs = (n, c, h, w) of src, pad = the cropping */
 typedef struct {
   int kind;                 /* DLWP_OP_*                                                                */
   int src, dst;             /* buffer indices                                                              */
