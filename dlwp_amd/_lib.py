@@ -40,6 +40,7 @@ OP_MERGE = 13
 OP_AVGPOOL2 = 14
 OP_BILINEAR2 = 15
 OP_TCONV_WEIGHTS, OP_DEPTH2SPACE_CROP, OP_CROP2D = 16, 17, 18
+OP_SCONV_WEIGHTS, OP_SPACE2DEPTH_PAD = 19, 20
 ELT_RELU, ELT_ELU, ELT_SELU, ELT_SIGMOID, ELT_HARD_SIGMOID, ELT_SOFTPLUS, ELT_SOFTSIGN, ELT_TANH = 0, 1, 2, 3, 4, 5, 6, 7   # dlwp_activation kinds
 MERGE_ADD, MERGE_SUBTRACT, MERGE_MULTIPLY, MERGE_AVERAGE, MERGE_MAXIMUM, MERGE_MINIMUM = 0, 1, 2, 3, 4, 5            # dlwp_merge kinds
 SCALE_STANDARD, SCALE_MINMAX = 0, 1                 # dlwp_scale kinds
@@ -202,6 +203,11 @@ _sig('dlwp_tconv_weights', [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i,
 _sig('dlwp_tconv_weights_bwd', [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp])
 _sig('dlwp_depth_to_space2_crop', [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp])
 _sig('dlwp_space_to_depth2_fill', [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp])
+_sig('dlwp_sconv_geometry', [_i, _i, _i, _P(_i), _P(_i), _P(_i), _P(_i)])
+_sig('dlwp_sconv_weights', [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp])
+_sig('dlwp_sconv_weights_bwd', [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp])
+_sig('dlwp_space_to_depth2_pad', [_vp, _vp, _vp, _i, _i, _i, _i, Pad2d, _i, _i, _i, _i, _i, _vp])
+_sig('dlwp_space_to_depth2_pad_bwd', [_vp, _vp, _vp, _i, _i, _i, _i, Pad2d, _i, _i, _i, _i, _i, _vp])
 _sig('dlwp_conv2d_uses_bf16_weights', [_vp, Shape4, _P(Conv2d), _i])
 _sig('dlwp_conv2d_prefers_unfused_pool', [_vp, _i, _i, _i, _i, _i, _i])
 _sig('dlwp_conv2d_supports_out_pool', [_vp, Shape4, _P(Conv2d)])

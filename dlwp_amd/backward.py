@@ -53,6 +53,16 @@ class GradBook(object):
             g = self.grads[buf] = torch.empty_like(self.tensor(buf))
         return g
 
+    def claim_window(self, buf, c_off, c):
+        """The gradient tensor of `buf` for a kernel that WRITES every element of channels [c_off, +c) itself -- or None where some
+        channel of the window already holds a gradient (the caller then produces a dense tensor and deposits it)."""
+        self.materialise(buf)
+        if self.overlaps(buf, c_off, c):
+            return None
+        g = self.grad_of(buf)
+        self.written.setdefault(buf, []).append((c_off, c))
+        return g
+
     def deposit(self, buf, c_off, c, dense):
         """Put `dense` (n, c, h, w) into window [c_off, +c) of grad[buf]: overwrite on first touch, add after."""
         self.materialise(buf)
@@ -265,11 +275,12 @@ class BackwardPass(object):
             self.touch(lay)
             return
         dz, fused_bias = self._conv_act_bias(c, y, acc)
-        if op.src != P.STATE_IN:
+        dgrad = op.src != P.STATE_IN and not op.input_image     # (no gradient w.r.t. the model input, or its space-to-depth image)
+        if dgrad:
             self.pair_open()           # (closed behind the data gradient's convolution)
         self._conv_wgrad(c, dz, kern, xs, acc, fused_bias)
         self.touch(lay)
-        if op.src != P.STATE_IN:       # (no gradient w.r.t. the model input is needed)
+        if dgrad:
             self._conv_dgrad(c, dz, kern, xs)
 
     def _conv_pooled_first_layer(self, c, y, acc, xs):
@@ -312,7 +323,7 @@ class BackwardPass(object):
         op, lay, d, src = c.op, c.op.layer, c.d, c.src
         gv = self.trainer._grad_view
         if op.wparam is not None:          # the layer runs with phase-summed kernels (plan.phase_params)
-            self._conv_wgrad_derived(c, dz, kern, xs, acc)
+            self._conv_wgrad_derived(c, dz, kern, xs, acc, fused_bias)
             return
         gw, wkey = gv(lay, 'kernel'), self.key('wgrad', c.k)
         self.lanes.run(lambda: ops.conv2d_bwd_weight(src, dz, gw, d, xs, accumulate=acc, ws_key=wkey))
@@ -327,7 +338,7 @@ class BackwardPass(object):
             bkey = self.key('bias', c.k)
             self.lanes.run(lambda: ops.bias_grad(dz, gb, lay.filters, ws_key=bkey))
 
-    def _conv_wgrad_derived(self, c, dz, kern, xs, acc):
+    def _conv_wgrad_derived(self, c, dz, kern, xs, acc, fused_bias=False):
         """Gradients of the derived kernels, folded back onto the layer's own."""
         op, lay, d, src = c.op, c.op.layer, c.d, c.src
         gv = self.trainer._grad_view
@@ -335,6 +346,9 @@ class BackwardPass(object):
         pp = self.plan.phase_params[op.wparam]
         if pp.get('kind') == 'tconv':
             self._conv_wgrad_tconv(c, dz, kern, xs, acc)
+            return
+        if pp.get('kind') == 'sconv':
+            self._conv_wgrad_sconv(c, dz, kern, xs, acc, fused_bias)
             return
         dw2 = self.new(*kern.shape)
         have_db = c.k in self.phase_db
@@ -370,6 +384,33 @@ class BackwardPass(object):
             self.post.append(gather)             # dw2 is final only behind the deferred sums
         else:
             gather()
+
+    def _conv_wgrad_sconv(self, c, dz, kern, xs, acc, fused_bias):
+        """Conv2D(strides=2): the weight gradient of its convolution on the space-to-depth image, gathered onto the layer's kernel (a
+        permutation: no sums); the bias gradient is the ordinary one (the bias is the layer's own)."""
+        op, lay, d, src = c.op, c.op.layer, c.d, c.src
+        gv = self.trainer._grad_view
+        gk = gv(lay, 'kernel')
+        dw2 = self.new(*kern.shape)
+        wkey = self.key('wgrad', c.k)
+        self.lanes.run(lambda: ops.conv2d_bwd_weight(src, dz, dw2, d, xs, ws_key=wkey))
+
+        def gather():
+            ops.sconv_weights_bwd(dw2, gk, accumulate=acc)
+        if self.prep is not None:
+            self.post.append(gather)             # dw2 is final only behind the deferred sums
+        else:
+            gather()
+        if lay.bias is None or fused_bias:
+            return
+        gb = gv(lay, 'bias')
+        if acc:
+            tmp = torch.empty_like(gb)
+            ops.bias_grad(dz, tmp, lay.filters)
+            ops.axpby(tmp, gb, 1.0, 1.0)
+        else:
+            bkey = self.key('bias', c.k)
+            self.lanes.run(lambda: ops.bias_grad(dz, gb, lay.filters, ws_key=bkey))
 
     def _conv_dgrad(self, c, dz, kern, xs):
         """The data gradient: its convolution, the pair's close behind it, then the adjoint of how the layer read its source."""
@@ -465,6 +506,32 @@ class BackwardPass(object):
         dph = ops.space_to_depth2_fill(gD, f, op.xs[1], op.xs[2], op.crop[0], op.crop[1], c_off=op.out_c_off)
         self.book.set(op.src, dph, 4 * f)
         self.preact.add(op.src)
+
+    def _s2dp(self, c):
+        """The padded space-to-depth in front of a Conv2D(strides=2): its adjoint folds the halo back and re-interleaves in one
+        pass; every element of the layer's channel window is written."""
+        op = c.op
+        if op.src == P.STATE_IN:
+            return
+        cin, book = op.xs[0], self.book
+        hh, ww, (hp, wp), halo = op.xs[1], op.xs[2], op.out_shape[1:], op.halo
+        ph, pw = hh + halo.top + halo.bottom, ww + halo.left + halo.right
+        sums = ((halo.mode_h != P.PAD_ZERO and (halo.top or halo.bottom)) or
+                (halo.mode_w != P.PAD_ZERO and (halo.left or halo.right)))
+        if sums and 2 * hp >= ph and 2 * wp >= pw and os.environ.get('DLWP_SCONV_FUSED_ADJOINT', '0') != '1':
+            # a halo that folds back (wrap, edge, mirror) over a phase tensor that covers the padded image: the two existing launches
+            # -- interleave to the padded gradient, then the halo's adjoint -- are 1.3 - 1.7 x faster than the fused gather, whose
+            # border lanes hold their waves up (DESIGN.md 5.33).  DLWP_SCONV_FUSED_ADJOINT=1 keeps the fused kernel (A/B runs).
+            dpad = ops.depth_to_space2_crop(c.gD, cin, 0, 0, ph, pw)
+            book.deposit(op.src, op.in_c_off, cin, ops.pad2d_bwd(dpad, (self.n, cin, hh, ww), c.d))
+            return
+        # a channel window that holds no gradient yet: the kernel writes it in place (every element of the window); the whole
+        # tensor (adopted without a copy where it is the first gradient) or a window that holds one: dense, then deposited
+        g = book.claim_window(op.src, op.in_c_off, cin) if not (op.in_c_off == 0 and cin == c.src.shape[1]) else None
+        if g is not None:
+            ops.space_to_depth2_pad_bwd(c.gD, cin, hh, ww, c.d, out=g.view((self.n, -1, hh, ww)), c_off=op.in_c_off)
+        else:
+            book.deposit(op.src, op.in_c_off, cin, ops.space_to_depth2_pad_bwd(c.gD, cin, hh, ww, c.d))
 
     def _crop(self, c):
         """Cropping2D: the gradient is zero padding"""
@@ -611,4 +678,4 @@ class BackwardPass(object):
 
     adjoints = {'d2s': _d2s, 'conv': _conv, 'rowconv': _rowconv, 'dense': _dense, 'dropout': _dropout, 'bn': _bn,
                 'lstm': _lstm, 'copy': _copy, 'pad': _pad, 'maxpool': _maxpool, 'avgpool': _avgpool, 'upsample': _upsample,
-                'bilinear': _bilinear, 'act': _act, 'merge': _merge, 'd2sc': _d2sc, 'crop': _crop}
+                'bilinear': _bilinear, 'act': _act, 'merge': _merge, 'd2sc': _d2sc, 'crop': _crop, 's2dp': _s2dp}

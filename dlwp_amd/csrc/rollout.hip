@@ -23,7 +23,9 @@ struct dlwp_rollout {
 namespace {
 
 // derived-kernel ops: parameter buffers only, run once at the head of the graph
-bool is_weight_op(const dlwp_op& op) { return op.kind == DLWP_OP_PHASE_WEIGHTS || op.kind == DLWP_OP_TCONV_WEIGHTS; }
+bool is_weight_op(const dlwp_op& op) {
+  return op.kind == DLWP_OP_PHASE_WEIGHTS || op.kind == DLWP_OP_TCONV_WEIGHTS || op.kind == DLWP_OP_SCONV_WEIGHTS;
+}
 
 bool is_step(const dlwp_op& op) { return op.kind == DLWP_OP_CONV2D && op.conv.lstm_f > 0 && op.src2 != DLWP_BUF_NONE; }
 
@@ -73,6 +75,11 @@ int enqueue_op(dlwp_handle_t h, const dlwp_op& op, const void* src, void* dst, c
     case DLWP_OP_DEPTH2SPACE_CROP:
       return dlwp_depth_to_space2_crop(h, src, dst, op.xs.n, op.xs.c, op.xs.h, op.xs.w, op.aux[0], op.aux[1], op.aux[2], op.aux[3],
                                        op.conv.out_c_off, op.conv.out_c_total > 0 ? op.conv.out_c_total : op.xs.c, dtype, (void*)s);
+    case DLWP_OP_SCONV_WEIGHTS:   // (src / dst are parameter buffers; no derived bias: the layer's own rides in its convolution)
+      return dlwp_sconv_weights(h, src, dst, op.conv.kh, op.conv.kw, op.xs.c, op.conv.cout, op.aux[1], op.aux[2], dtype, (void*)s);
+    case DLWP_OP_SPACE2DEPTH_PAD: // the halo in front of a strided Conv2D + its 'same' zeros + the de-interleave, one pass
+      return dlwp_space_to_depth2_pad(h, src, dst, op.xs.n, op.xs.c, op.xs.h, op.xs.w, op.pad, op.aux[0], op.aux[1],
+                                      op.conv.in_c_off, op.conv.in_c_total > 0 ? op.conv.in_c_total : op.xs.c, dtype, (void*)s);
     case DLWP_OP_CROP2D:          // keras Cropping2D: the adjoint of zero padding ("zero drops")
       return dlwp_pad2d_bwd(h, src, dst, op.xs.n * op.xs.c, op.xs.h - op.pad.top - op.pad.bottom,
                             op.xs.w - op.pad.left - op.pad.right, 1, op.pad, dtype, (void*)s);

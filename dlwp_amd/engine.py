@@ -115,7 +115,10 @@ class Executor(object):
     def conv_weights(self, op):
         """(kernel, bias) tensors a conv launch multiplies with: the layer's, or the derived ones of a restated layer."""
         if op.wparam is not None:
-            return self.phase_buffers()[op.wparam]
+            w2, b2 = self.phase_buffers()[op.wparam]
+            if self.plan.phase_params[op.wparam].get('kind') == 'sconv':      # (a strided Conv2D keeps its own bias)
+                return w2, op.layer.bias
+            return w2, b2
         return op.layer.kernel, op.layer.bias
 
     def _descriptors(self):
@@ -128,7 +131,7 @@ class Executor(object):
                     descs.append(ops.make_conv(f, kh, kw, dil, ops.make_pad(*op.halo), op.act,
                                                op.in_c_off, op.in_c_total, op.out_c_off, op.out_c_total, op.src_mode,
                                                op.out_pool, op.out_d2s, op.lstm_f, op.rec_act))
-                elif op.kind in ('pad', 'crop'):
+                elif op.kind in ('pad', 'crop', 's2dp'):
                     descs.append(ops.make_pad(*op.halo))
                 else:
                     descs.append(None)
@@ -279,7 +282,7 @@ class Executor(object):
         pooled_too = self._pooled_too() if prepared is not None or skip_ops else {}
         done = set()
         for k, (op, d) in enumerate(zip(self.plan.ops, self._descriptors())):
-            if (op.kind in ('phasew', 'tphasew') and skip_phasew) or k in skip_ops or k in done:
+            if (op.kind in ('phasew', 'tphasew', 'sphasew') and skip_phasew) or k in skip_ops or k in done:
                 continue
             src, dst = res(op.src), res(op.dst)
             if k in pooled_too:
@@ -328,6 +331,11 @@ class Executor(object):
                                          c_off=op.out_c_off)
             elif op.kind == 'crop':
                 ops.crop2d(src, d, out=dst)
+            elif op.kind == 'sphasew':        # Conv2D(strides=2): kernel -> the kernel on its 4 cin phase channels
+                ops.sconv_weights(op.layer.kernel, w2=self.phase_buffers()[op.wparam][0])
+                continue
+            elif op.kind == 's2dp':           # halo + 'same' zeros + de-interleave, one pass
+                ops.space_to_depth2_pad(src, op.xs[0], d, op.out_shape[1], op.out_shape[2], c_off=op.in_c_off, out=dst)
             elif op.kind == 'pad':
                 if op.inner > 1:
                     hh, ww = op.xs[1], op.xs[2]
@@ -545,7 +553,8 @@ class Executor(object):
                 'phasew': _lib.OP_PHASE_WEIGHTS, 'd2s': _lib.OP_DEPTH2SPACE, 'rowconv': _lib.OP_ROWCONV2D,
                 'bn': _lib.OP_BATCHNORM, 'dense': _lib.OP_DENSE, 'scale': _lib.OP_SCALE, 'act': _lib.OP_ACTIVATION,
                 'merge': _lib.OP_MERGE, 'avgpool': _lib.OP_AVGPOOL2, 'bilinear': _lib.OP_BILINEAR2,
-                'tphasew': _lib.OP_TCONV_WEIGHTS, 'd2sc': _lib.OP_DEPTH2SPACE_CROP, 'crop': _lib.OP_CROP2D}
+                'tphasew': _lib.OP_TCONV_WEIGHTS, 'd2sc': _lib.OP_DEPTH2SPACE_CROP, 'crop': _lib.OP_CROP2D,
+                'sphasew': _lib.OP_SCONV_WEIGHTS, 's2dp': _lib.OP_SPACE2DEPTH_PAD}
         arr = (_lib.Op * len(self.plan.ops))()
         for k, (op, d) in enumerate(zip(self.plan.ops, self._descriptors())):
             o = arr[k]
@@ -554,6 +563,8 @@ class Executor(object):
             o.xs = _lib.Shape4(n, *op.xs)
             if op.kind == 'conv':
                 o.w, o.b = pidx[op.wparam] if op.wparam is not None else widx[id(op.layer)]
+                if op.wparam is not None and self.plan.phase_params[op.wparam].get('kind') == 'sconv':
+                    o.b = widx[id(op.layer)][1]            # (a strided Conv2D keeps its own bias)
                 o.conv = d
                 o.aux[0] = self._conv_dtype(op)
                 if op.lstm_f:                          # cell update in the epilogue: z_add | NONE, c_prev | NONE, c_out
@@ -592,6 +603,17 @@ class Executor(object):
                 o.aux[0], o.aux[1], o.aux[2], o.aux[3] = op.crop[0], op.crop[1], op.out_shape[1], op.out_shape[2]
             elif op.kind == 'crop':
                 o.pad = d
+            elif op.kind == 'sphasew':                 # Conv2D(strides=2) kernel -> derived kernel, once at the head of the graph
+                o.src = widx[id(op.layer)][0]
+                o.dst = pidx[op.wparam][0]
+                o.aux[0] = _lib.BUF_NONE
+                o.conv.cout, o.conv.kh, o.conv.kw = op.layer.filters, op.layer.kernel_size[0], op.layer.kernel_size[1]
+                o.aux[1], o.aux[2] = self.plan.phase_params[op.wparam]['w2_shape'][:2]      # the stored taps
+                o.xs = _lib.Shape4(n, op.xs[0], 1, 1)
+            elif op.kind == 's2dp':                    # the padded space-to-depth: pad = the halo, aux = hp, wp
+                o.pad = d
+                o.conv.in_c_off, o.conv.in_c_total = op.in_c_off, op.in_c_total
+                o.aux[0], o.aux[1] = op.out_shape[1], op.out_shape[2]
             elif op.kind == 'dense':
                 o.w, o.b = didx[id(op.layer)]
                 o.conv.cout, o.conv.act = op.layer.units, op.act
@@ -895,6 +917,10 @@ class Model(object):
             raise NotImplementedError('bfloat16 activation storage of a model with activation / merge layers (%s) is not '
                                       'implemented (the element-wise kernels read and write float32)'
                                       % ', '.join(lay.name for lay in self.plan.eltwise_layers))
+        if dtype == 'bfloat16' and any(p.get('kind') == 'sconv' for p in self.plan.phase_params):
+            raise NotImplementedError('bfloat16 activation storage of a model with a Conv2D(strides=2) layer (%s) is not '
+                                      'implemented (the padded space-to-depth kernels read and write float32)'
+                                      % ', '.join(p['layer'].name for p in self.plan.phase_params if p.get('kind') == 'sconv'))
         if dtype != self.activation_dtype:
             self.activation_dtype = dtype
             # interleaved phase stores (dlwp_conv2d.out_d2s) belong to the float32 Winograd kernels; with bfloat16 storage

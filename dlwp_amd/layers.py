@@ -184,9 +184,11 @@ class ZeroPadding2D(_Pad2DBase):
 
 
 class Conv2D(Layer):
-    """keras.layers.Conv2D: stride 1, 'valid' | 'same', dilation, bias, activation in {None,'linear','tanh','relu'},
-    data_format='channels_first' (what every reference call site passes: examples/train.py:164-219).
-    Weights: kernel (kh, kw, cin, cout) glorot_uniform, bias (cout,) zeros -- Keras layout and initialisers."""
+    """keras.layers.Conv2D: strides 1 or 2, 'valid' | 'same', dilation (stride 1 only), bias, activation in
+    {None,'linear','tanh','relu'}, data_format='channels_first' (what every reference call site passes: examples/train.py:164-219).
+    Weights: kernel (kh, kw, cin, cout) glorot_uniform, bias (cout,) zeros -- Keras layout and initialisers.
+    strides=2 (the learned down-sampling of an encoder; examples/train_generator.py:113-141 of the reference carries one) runs as a
+    padded space-to-depth pass + one stride-1 convolution on 4 x cin phase channels (csrc/sconv.hip)."""
 
     def __init__(self, filters, kernel_size, strides=(1, 1), padding='valid', data_format=None, dilation_rate=(1, 1),
                  activation=None, use_bias=True, kernel_initializer='glorot_uniform', bias_initializer='zeros',
@@ -199,8 +201,15 @@ class Conv2D(Layer):
         dl = (dilation_rate, dilation_rate) if isinstance(dilation_rate, (int, np.integer)) else tuple(dilation_rate)
         if len(ks) != 2 or len(st) != 2 or len(dl) != 2:
             raise ValueError('kernel_size / strides / dilation_rate must be an int or a pair')
-        if tuple(st) != (1, 1):
-            raise NotImplementedError('Conv2D: only strides=1 is implemented (the reference never strides)')
+        try:
+            st = tuple(int(v) if int(v) == v else v for v in st)
+        except (TypeError, ValueError):
+            raise ValueError('Conv2D: strides %r' % (strides,))
+        if st not in ((1, 1), (2, 2)):
+            raise NotImplementedError('Conv2D: strides=1 and strides=2 are implemented (equal on both axes), got %r' % (st,))
+        if st == (2, 2) and any(int(d) != 1 for d in dl):
+            raise ValueError('Conv2D: strides > 1 is not supported together with dilation_rate > 1 (got strides %r, '
+                             'dilation_rate %r)' % (st, tuple(dl)))
         if padding not in ('valid', 'same'):
             raise ValueError("Conv2D padding must be 'valid' or 'same'")
         if callable(activation):
@@ -210,7 +219,7 @@ class Conv2D(Layer):
         if kernel_initializer not in ('glorot_uniform', 'zeros') or bias_initializer not in ('zeros',):
             raise NotImplementedError('initialisers: kernel glorot_uniform|zeros, bias zeros')
         self.kernel_size = tuple(int(k) for k in ks)
-        self.strides = (1, 1)
+        self.strides = st
         self.padding = padding
         self.data_format = normalize_data_format(data_format)
         if self.data_format != 'channels_first':
@@ -230,10 +239,30 @@ class Conv2D(Layer):
         tot_w = self.dilation_rate[1] * (self.kernel_size[1] - 1)
         return (tot_h // 2, tot_h - tot_h // 2, tot_w // 2, tot_w - tot_w // 2)
 
+    def strided_geometry(self, h, w):
+        """strides=2, per axis (T, pad_lo, pad_hi, out): T = ceil(k / 2) taps on the space-to-depth image, TensorFlow's padding
+        ('same': out = ceil(len / 2), total max((out - 1) 2 + k - len, 0), smaller half first; 'valid': none,
+        out = (len - k) // 2 + 1) -- the rule of dlwp_sconv_geometry (include/dlwp_hip.h), restated on the host."""
+        geo = []
+        for k, n in zip(self.kernel_size, (int(h), int(w))):
+            if self.padding == 'same':
+                out = (n + 1) // 2
+                tot = max((out - 1) * 2 + k - n, 0)
+                lo, hi = tot // 2, tot - tot // 2
+            else:
+                if n < k:
+                    raise ValueError('%s: kernel %r does not fit the input %r' % (self.name, self.kernel_size, (h, w)))
+                out, lo, hi = (n - k) // 2 + 1, 0, 0
+            geo.append(((k + 1) // 2, lo, hi, out))
+        return tuple(geo)
+
     def compute_output_shape(self, s):
         if len(s) != 3:
             raise ValueError('%s expects 4D input, got per-sample shape %r' % (self.name, s))
         c, h, w = s
+        if self.strides == (2, 2):
+            (_, _, _, ho), (_, _, _, wo) = self.strided_geometry(h, w)
+            return (self.filters, ho, wo)
         if self.padding == 'same':
             return (self.filters, h, w)
         ho = h - self.dilation_rate[0] * (self.kernel_size[0] - 1)
@@ -266,7 +295,7 @@ class Conv2D(Layer):
 
     def get_config(self):
         cfg = super(Conv2D, self).get_config()
-        cfg.update({'filters': self.filters, 'kernel_size': self.kernel_size, 'padding': self.padding,
+        cfg.update({'filters': self.filters, 'kernel_size': self.kernel_size, 'strides': self.strides, 'padding': self.padding,
                     'data_format': self.data_format, 'dilation_rate': self.dilation_rate,
                     'activation': self.activation, 'use_bias': self.use_bias})
         return cfg

@@ -731,6 +731,77 @@ def crop2d(x, crop, out=None):
     return y
 
 
+def sconv_geometry(k, padding, length):
+    """(T, pad_lo, pad_hi, out_len) of one axis of Conv2D(k, strides=2, padding): T = ceil(k / 2) taps on the space-to-depth image,
+    the layer's own zero padding (TensorFlow's 'same' rule for stride 2) and the output length (include/dlwp_hip.h:
+    dlwp_sconv_geometry; host only).  ValueError where a 'valid' kernel does not fit."""
+    t, lo, hi, out = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    rc = _lib.lib.dlwp_sconv_geometry(int(k), 1 if padding == 'same' else 0, int(length), ctypes.byref(t), ctypes.byref(lo),
+                                      ctypes.byref(hi), ctypes.byref(out))
+    if rc != 0:
+        raise ValueError(_lib.lib.dlwp_last_error().decode())
+    return t.value, lo.value, hi.value, out.value
+
+
+def sconv_weights(k_hwio, w2=None, taps=None):
+    """Kernel of a Conv2D(strides=2) restated as a stride-1 convolution on the space-to-depth image of its input: K (kh, kw, cin, F)
+    -> w2 (sh, sw, 4 cin, F) (include/dlwp_hip.h: dlwp_sconv_weights).  taps = (sh, sw) >= (Th, Tw): the stored taps (those of w2
+    when it is given, else Th x Tw), the Th x Tw block at (0, 0)."""
+    _check_f32(k_hwio, w2)
+    kh, kw, cin, f = k_hwio.shape
+    sh, sw = taps if taps is not None else (tuple(w2.shape[:2]) if w2 is not None else ((kh + 1) // 2, (kw + 1) // 2))
+    if w2 is None:
+        w2 = torch.empty((sh, sw, 4 * cin, f), dtype=torch.float32, device=k_hwio.device)
+    if tuple(w2.shape) != (sh, sw, 4 * cin, f):
+        raise ValueError('sconv_weights: derived kernel %r does not belong to a kernel %r' % (tuple(w2.shape), tuple(k_hwio.shape)))
+    _lib.check(_lib.lib.dlwp_sconv_weights(_lib.handle(_dev(k_hwio)), _ptr(k_hwio), _ptr(w2), kh, kw, cin, f, int(sh), int(sw),
+                                           _lib.F32, _stream(k_hwio)))
+    return w2
+
+
+def sconv_weights_bwd(dw2, dk, accumulate=False):
+    """Adjoint of sconv_weights: dk (kh, kw, cin, F) (+)= the gather of dw2 (sh, sw, 4 cin, F)."""
+    _check_f32(dw2, dk)
+    kh, kw, cin, f = dk.shape
+    sh, sw = int(dw2.shape[0]), int(dw2.shape[1])
+    if dw2.dim() != 4 or tuple(dw2.shape[2:]) != (4 * cin, f) or sh < (kh + 1) // 2 or sw < (kw + 1) // 2:
+        raise ValueError('sconv_weights_bwd: derived gradient %r does not belong to a kernel %r' % (tuple(dw2.shape), tuple(dk.shape)))
+    _lib.check(_lib.lib.dlwp_sconv_weights_bwd(_lib.handle(_dev(dw2)), _ptr(dw2), _ptr(dk), kh, kw, cin, f, sh, sw,
+                                               1 if accumulate else 0, _lib.F32, _stream(dw2)))
+    return dk
+
+
+def space_to_depth2_pad(src, c, pad, hp, wp, c_off=0, out=None):
+    """(n, c_total, H, W)[c_off:+c] under the halo `pad` (a Pad2d, the five modes per axis) -> (n, 4c, hp, wp) phase-major:
+    out[:, (2a+b) c + ch, i, j] = padded[:, ch, 2i+a, 2j+b], +0 beyond the padded image (include/dlwp_hip.h:
+    dlwp_space_to_depth2_pad) -- the padding in front of a strided Conv2D, its 'same' zeros and the de-interleave in one pass."""
+    _check_f32(src, out)
+    n, c_total, hh, ww = src.shape
+    if out is None:
+        out = torch.empty((n, 4 * int(c), int(hp), int(wp)), dtype=torch.float32, device=src.device)
+    if tuple(out.shape) != (n, 4 * int(c), int(hp), int(wp)):
+        raise ValueError('space_to_depth2_pad: output shape %r' % (tuple(out.shape),))
+    _lib.check(_lib.lib.dlwp_space_to_depth2_pad(_lib.handle(_dev(src)), _ptr(src), _ptr(out), n, int(c), hh, ww, pad, int(hp),
+                                                 int(wp), int(c_off), c_total, _lib.F32, _stream(src)))
+    return out
+
+
+def space_to_depth2_pad_bwd(dout, c, in_h, in_w, pad, out=None, c_off=0):
+    """Adjoint of space_to_depth2_pad: (n, 4c, hp, wp) -> channels [c_off, +c) of `out` (n, c_total, in_h, in_w) (a new
+    (n, c, in_h, in_w) tensor when None).  Every element of the window is written (overwritten, as pad2d_bwd does)."""
+    _check_f32(dout, out)
+    n, c4, hp, wp = dout.shape
+    if c4 != 4 * int(c):
+        raise ValueError('space_to_depth2_pad_bwd: %d channels is not 4 x %d' % (c4, c))
+    if out is None:
+        out = torch.empty((n, int(c), int(in_h), int(in_w)), dtype=torch.float32, device=dout.device)
+    if out.shape[0] != n or tuple(out.shape[2:]) != (int(in_h), int(in_w)):
+        raise ValueError('space_to_depth2_pad_bwd: output shape %r' % (tuple(out.shape),))
+    _lib.check(_lib.lib.dlwp_space_to_depth2_pad_bwd(_lib.handle(_dev(dout)), _ptr(dout), _ptr(out), n, int(c), int(in_h),
+                                                     int(in_w), pad, hp, wp, int(c_off), out.shape[1], _lib.F32, _stream(dout)))
+    return out
+
+
 def uses_bf16_weights(xs, cd, dtype):
     """Does conv2d on an input of shape xs = (n, c, h, w) stored as `dtype` (a _lib.dtype_io code) multiply with weights
     rounded to bfloat16 (the bf16 matrix-core kernels)?  Host logic only."""

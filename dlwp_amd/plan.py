@@ -66,7 +66,7 @@ class View(object):
 
 class PlanOp(object):
     """One launch.  kind in {'conv','rowconv','pad','maxpool','avgpool','upsample','bilinear','copy','lstm','phasew','d2s','bn',
-    'dense','dropout','scale','act','merge','tphasew','d2sc','crop'}."""
+    'dense','dropout','scale','act','merge','tphasew','d2sc','crop','sphasew','s2dp'}."""
 
     def __init__(self, kind, src, dst, xs, **kw):
         self.kind, self.src, self.dst = kind, src, dst
@@ -105,6 +105,9 @@ class PlanOp(object):
         # d2sc only (the cropping interleave of a Conv2DTranspose): (top, left) of the window [top, +ho) x [left, +wo) it takes of
         # the depth-to-space image of its source; layer / act = the layer's, for the backward (bias gradient at full resolution)
         self.crop = kw.pop('crop', None)
+        # conv of a Conv2D(strides=2) only: its source is the space-to-depth image of the MODEL INPUT (the 's2dp' op in front reads
+        # STATE_IN), so nobody needs the gradient of that source: the backward pass launches no data gradient
+        self.input_image = kw.pop('input_image', False)
         assert not kw, kw
 
     @property
@@ -134,6 +137,9 @@ class PlanOp(object):
             extra = ' %s crop%r -> %r' % (self.layer.name, tuple(self.crop), tuple(self.out_shape))
         if self.kind == 'crop':
             extra = ' crop%r' % (tuple(self.halo[:4]),)
+        if self.kind == 's2dp':
+            extra = ' halo%s cin[%d:+%d/%d] -> %r' % (tuple(self.halo), self.in_c_off, self.xs[0], self.in_c_total,
+                                                     tuple(self.out_shape))
         return '<%s %s -> %s xs=%s%s>' % (self.kind, self.src, self.dst, self.xs, extra)
 
 
@@ -685,6 +691,47 @@ def build_plan(inputs, outputs, inference=False, fuse_d2s=True, fuse_lstm=False,
                 materialize(v, dst=dst, dst_c_off=off, dst_c_total=c_tot)
                 off += v.logical[0]
             views[t.uid] = View(dst, 0, c_tot, c_tot, hh, ww)
+        elif isinstance(lay, L.Conv2D) and tuple(lay.strides) == (2, 2):
+            # keras Conv2D(strides=2) (csrc/sconv.hip): a stride-1 'valid' convolution of the space-to-depth image P of the padded
+            # input (4 cin phase-major channels) with a kernel that is a permutation of the layer's own, stored with the 3 x 3 /
+            # 5 x 5 taps the matrix-core kernels exist for (tconv_taps; the T x T block at the origin, zero taps below / right, P
+            # that much longer).  Three ops: 'sphasew' (kernel -> derived kernel; plan.phase_params), 's2dp' (the lazy halo of the
+            # input + the layer's own 'same' zeros + the de-interleave in one pass) and ONE 'conv' on P with the layer's bias and
+            # activation in its epilogue.
+            if any(p['layer'] is lay for p in plan.phase_params):
+                raise NotImplementedError('%s: a Conv2D layer with strides=2 applied more than once is not implemented' % lay.name)
+            v = ins[0]
+            if v.shape is not None and len(v.shape) != 3:
+                raise NotImplementedError('%s on a non-3D tensor %r' % (lay.name, v.shape))
+            if v.src_mode != SRC_DIRECT:         # (the pass reads a stored tensor; a halo in front may stay lazy)
+                v = materialize(v.copy(halo=NO_HALO)).copy(halo=v.halo)
+            _, hl, wl = v.logical                                   # what the layer sees as its input
+            (th, pt, pb, ho), (tw, pl, pr, wo) = lay.strided_geometry(hl, wl)
+            halo = _compose_halo(v.halo, ((pt, pb), (pl, pr)), PAD_ZERO)
+            if halo is None:
+                v = materialize(v)
+                halo = Halo(pt, pb, pl, pr, PAD_ZERO, PAD_ZERO)
+            kh, kw = lay.kernel_size
+            sh, sw = tconv_taps(th, tw)
+            hp, wp = ho + sh - 1, wo + sw - 1                       # the phase tensor the stored taps read
+            f = lay.filters
+            alg = 2 * ho * wo * f * v.c * kh * kw
+            pidx = len(plan.phase_params)
+            plan.phase_params.append({'layer': lay, 'w2_shape': (sh, sw, 4 * v.c, f), 'bias': False, 'kind': 'sconv'})
+            emit(PlanOp('sphasew', STATE_IN, STATE_IN, (v.c, 0, 0), layer=lay, wparam=pidx, out_shape=(0, 0, 0)))
+            tmp = plan.new_buffer(4 * v.c, hp, wp)
+            emit(PlanOp('s2dp', v.buf, tmp, (v.c, v.h, v.w), halo=halo, in_c_off=v.c_off, in_c_total=v.c_total,
+                        out_c_total=4 * v.c, out_shape=(4 * v.c, hp, wp)))
+            if outs:
+                dst = OUT(outs[0])
+                plan.output_store[outs[0]] = (f, ho, wo)
+            else:
+                dst = plan.new_buffer(f, ho, wo)
+            emit(PlanOp('conv', tmp, dst, (4 * v.c, hp, wp), layer=lay, halo=NO_HALO, src_mode=SRC_DIRECT, act=ACT[lay.activation],
+                        in_c_off=0, in_c_total=4 * v.c, out_c_off=0, out_c_total=f, out_shape=(f, ho, wo), dil=(1, 1),
+                        ksize=(sh, sw), filters=f, wparam=pidx, alg_flops=alg, input_image=v.buf == STATE_IN))
+            producer.pop(dst, None)              # (a MaxPooling2D behind it stays a launch / a lazy source of its own)
+            views[t.uid] = View(dst, 0, f, f, ho, wo)
         elif isinstance(lay, L.Conv2D):
             v = ins[0]
             if v.shape is not None and len(v.shape) != 3:

@@ -34,7 +34,7 @@ def _layer_config(lay):
             cfg['kernel_regularizer'] = {'l2': lay.kernel_regularizer.l2}
     elif isinstance(lay, L.Conv2D):
         from .regularizers import L1L2
-        cfg.update(filters=lay.filters, kernel_size=list(lay.kernel_size), padding=lay.padding,
+        cfg.update(filters=lay.filters, kernel_size=list(lay.kernel_size), strides=list(lay.strides), padding=lay.padding,
                    data_format=lay.data_format, dilation_rate=list(lay.dilation_rate), activation=lay.activation,
                    use_bias=lay.use_bias)
         if isinstance(lay.kernel_regularizer, L1L2):
@@ -210,7 +210,7 @@ def _keras_layer_spec(lay):
                  kernel_regularizer=reg(lay.kernel_regularizer), recurrent_regularizer=None, recurrent_constraint=None,
                  dropout=0.0, recurrent_dropout=0.0, **tail)
     elif isinstance(lay, L.Conv2D):
-        c.update(filters=lay.filters, kernel_size=list(lay.kernel_size), strides=[1, 1], padding=lay.padding,
+        c.update(filters=lay.filters, kernel_size=list(lay.kernel_size), strides=list(lay.strides), padding=lay.padding,
                  data_format=lay.data_format, dilation_rate=list(lay.dilation_rate), activation=lay.activation or 'linear',
                  use_bias=lay.use_bias, kernel_initializer=_GLOROT, bias_initializer=_ZEROS,
                  kernel_regularizer=reg(lay.kernel_regularizer), **tail)

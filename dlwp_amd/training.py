@@ -587,6 +587,8 @@ class Trainer(object):
             elif op.kind == 'tphasew':
                 w2, b2 = ex.phase_buffers()[op.wparam]
                 ops.tconv_weights(op.layer.kernel, op.layer.bias, w2=w2, b2=b2)
+            elif op.kind == 'sphasew':
+                ops.sconv_weights(op.layer.kernel, w2=ex.phase_buffers()[op.wparam][0])
         cache = self._prep_cache.get(n)
         if cache is None:
             if len(self._prep_cache) > 4:

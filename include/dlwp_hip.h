@@ -608,6 +608,43 @@ int dlwp_depth_to_space2_crop(dlwp_handle_t, const void* src, void* dst, int n, 
 int dlwp_space_to_depth2_fill(dlwp_handle_t, const void* src, void* dst, int n, int f, int hp, int wp, int top, int left,
                               int in_h, int in_w, int c_off, int c_total, int dtype, void* stream);
 
+/* ---- keras Conv2D(filters, k, strides=2, padding='valid'|'same', data_format='channels_first') (sconv.hip):
+ *      y[n][o][i][j] = b[o] + sum xpad[n][c][2i+u][2j+v] K[u][v][c][o], K (kh, kw, cin, F).  Per axis -- 'valid': no padding,
+ *      out = (len - k) / 2 + 1;  'same' (TensorFlow's rule for stride 2, NOT the stride-1 rule): out = ceil(len / 2),
+ *      max((out - 1) 2 + k - len, 0) zeros in all, the smaller half first.  With T = ceil(k / 2) per axis and P the space-to-depth
+ *      image of xpad, P[n][(2a+b) cin + c][i][j] = xpad[n][c][2i+a][2j+b] (phase-major, +0 outside the padded image), y is the
+ *      stride-1 'valid' cross-correlation of P with w2[ti][tj][(2a+b) cin + c][o] = K[2ti+a][2tj+b][c][o] (zero where that index is
+ *      >= kh / kw): ONE dlwp_conv2d_fwd on 4 cin phase-major channels, bias and activation in its epilogue (the bias is the layer's).
+ *      dlwp_sconv_geometry (host only), per axis: *t = T, *pad_lo / *pad_hi = the layer's own zero padding, *out_len; an error where
+ *          a 'valid' kernel does not fit.
+ *      dlwp_sconv_weights: K -> w2 (sh, sw, 4 cin, F).  sh >= Th and sw >= Tw taps are stored: the Th x Tw block at offset (0, 0),
+ *          zeros below / right of it (the matrix-core kernels exist for 3 x 3 and 5 x 5 taps); P then has hp = out_h + sh - 1 rows and
+ *          wp = out_w + sw - 1 columns, and the convolution stays 'valid' with no halo.
+ *      dlwp_sconv_weights_bwd: dK[u][v][c][o] (+)= dw2[u/2][v/2][(2(u&1) + (v&1)) cin + c][o]  (a gather, no sums).
+ *      dlwp_space_to_depth2_pad: src (n, c_total, in_h, in_w)[c_off:+c] -> dst (n, 4c, hp, wp),
+ *          dst[n][(2a+b) c + ch][i][j] = src[n][c_off+ch][map(2i+a - pad.top, in_h, pad.mode_h)][map(2j+b - pad.left, in_w, pad.mode_w)],
+ *          map = the DLWP_PAD_* rule of dlwp_pad2d_fwd; +0 where a map says zero or (2i+a, 2j+b) lies beyond the padded image
+ *          (in_h + top + bottom) x (in_w + left + right).  Every element of dst is written.  This is dlwp_pad2d_fwd (the halo layers in
+ *          front of the Conv2D and its own 'same' zeros, composed) and the de-interleave in one pass.
+ *      dlwp_space_to_depth2_pad_bwd: its adjoint, ddst (n, 4c, hp, wp) -> dsrc (n, c_total, in_h, in_w)[c_off:+c], in gather form (no
+ *          atomics): source pixel (y, x) receives the sum of ddst over the padded positions (r, s) inside [0, 2hp) x [0, 2wp) and
+ *          inside the padded image that map to it (wrap adds the periodic images, edge adds to the border, the mirrors add their
+ *          reflections, zero drops): its own position first, then the halo positions in ascending (r, s).  As dlwp_pad2d_bwd, it
+ *          OVERWRITES: every element of the window is written, +0 where nothing maps to it; a caller that already holds a gradient
+ *          there adds the result itself.
+ *      The four stream entry points refuse, without a launch and in this order: bad sizes / halos / channel windows / stored taps,
+ *      null pointers, a null handle.
+ *      All float32; all but the sums of the adjoint bit-exact (they move and zero-fill). */
+int dlwp_sconv_geometry(int k, int same, int len, int* t, int* pad_lo, int* pad_hi, int* out_len);
+int dlwp_sconv_weights(dlwp_handle_t, const void* w, void* w2, int kh, int kw, int cin, int f, int sh, int sw, int dtype,
+                       void* stream);
+int dlwp_sconv_weights_bwd(dlwp_handle_t, const void* dw2, void* dw, int kh, int kw, int cin, int f, int sh, int sw,
+                           int accumulate, int dtype, void* stream);
+int dlwp_space_to_depth2_pad(dlwp_handle_t, const void* src, void* dst, int n, int c, int in_h, int in_w, dlwp_pad2d pad, int hp,
+                             int wp, int c_off, int c_total, int dtype, void* stream);
+int dlwp_space_to_depth2_pad_bwd(dlwp_handle_t, const void* ddst, void* dsrc, int n, int c, int in_h, int in_w, dlwp_pad2d pad,
+                                 int hp, int wp, int c_off, int c_total, int dtype, void* stream);
+
 /* ---- ConvLSTM2D cell update (keras ConvLSTM2DCell.call; call sites examples/train.py:148-155,
  *      examples/train_functional.py:207-219).  zx / zh: (n, 4F, h*w) gate pre-activations i | f | c | o from the input
  *      convolution (+bias) and the recurrent 'same' convolution of h_{t-1}; zh and c_prev may be NULL on the first step
@@ -822,6 +859,10 @@ int dlwp_scale_inv(dlwp_handle_t, const void* x, void* y, const void* shift, con
                                    * conv.out_c_total channels; xs = (n, F, hp, wp), aux = {top, left, out_h, out_w} */
 #define DLWP_OP_CROP2D    18      /* keras Cropping2D = dlwp_pad2d_bwd with DLWP_PAD_ZERO: src (n, c, h, w) -> dst (n, c, h - top -
                                    * bottom, w - left - right); xs = (n, c, h, w) of src, pad = the cropping */
+#define DLWP_OP_SCONV_WEIGHTS 19  /* dlwp_sconv_weights: src = the layer's kernel, dst = w2 (parameter buffers); conv = {cout = F, kh,
+                                   * kw}, xs.c = cin, aux[1] / aux[2] = sh / sw.  Run ONCE at the head of the rollout graph.   */
+#define DLWP_OP_SPACE2DEPTH_PAD 20 /* dlwp_space_to_depth2_pad: src window [conv.in_c_off, +xs.c) of conv.in_c_total channels, xs =
+                                   * (n, c, h, w) of that window -> dst (n, 4c, hp, wp); pad = the halo, aux = {hp, wp}        */
 typedef struct {
   int kind;                 /* DLWP_OP_*                                                                */
   int src, dst;             /* buffer indices                                                              */
