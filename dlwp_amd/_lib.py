@@ -41,6 +41,7 @@ OP_AVGPOOL2 = 14
 OP_BILINEAR2 = 15
 OP_TCONV_WEIGHTS, OP_DEPTH2SPACE_CROP, OP_CROP2D = 16, 17, 18
 OP_SCONV_WEIGHTS, OP_SPACE2DEPTH_PAD = 19, 20
+OP_DEPTHWISE2D, OP_POINTWISE2D = 21, 22
 ELT_RELU, ELT_ELU, ELT_SELU, ELT_SIGMOID, ELT_HARD_SIGMOID, ELT_SOFTPLUS, ELT_SOFTSIGN, ELT_TANH = 0, 1, 2, 3, 4, 5, 6, 7   # dlwp_activation kinds
 MERGE_ADD, MERGE_SUBTRACT, MERGE_MULTIPLY, MERGE_AVERAGE, MERGE_MAXIMUM, MERGE_MINIMUM = 0, 1, 2, 3, 4, 5            # dlwp_merge kinds
 SCALE_STANDARD, SCALE_MINMAX = 0, 1                 # dlwp_scale kinds
@@ -77,6 +78,19 @@ class Conv2d(ctypes.Structure):
                 ('in_c_total', ctypes.c_int), ('out_c_off', ctypes.c_int), ('out_c_total', ctypes.c_int),
                 ('src_mode', ctypes.c_int), ('out_pool', ctypes.c_int), ('out_d2s', ctypes.c_int),
                 ('lstm_f', ctypes.c_int), ('lstm_rec_act', ctypes.c_int)]
+
+
+class Depthwise2d(ctypes.Structure):
+    """dlwp_depthwise2d (include/dlwp_hip.h): taps, dilation, depth multiplier, halo, activation and channel windows of one launch"""
+    _fields_ = [('kh', ctypes.c_int), ('kw', ctypes.c_int), ('dil_h', ctypes.c_int), ('dil_w', ctypes.c_int),
+                ('depth_multiplier', ctypes.c_int), ('halo', Pad2d), ('act', ctypes.c_int), ('in_c_off', ctypes.c_int),
+                ('in_c_total', ctypes.c_int), ('out_c_off', ctypes.c_int), ('out_c_total', ctypes.c_int)]
+
+
+class Pointwise2d(ctypes.Structure):
+    """dlwp_pointwise2d (include/dlwp_hip.h): channels, activation and channel windows of one 1 x 1 product"""
+    _fields_ = [('q', ctypes.c_int), ('o', ctypes.c_int), ('act', ctypes.c_int), ('in_c_off', ctypes.c_int),
+                ('in_c_total', ctypes.c_int), ('out_c_off', ctypes.c_int), ('out_c_total', ctypes.c_int)]
 
 
 class Op(ctypes.Structure):
@@ -208,6 +222,15 @@ _sig('dlwp_sconv_weights', [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp])
 _sig('dlwp_sconv_weights_bwd', [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp])
 _sig('dlwp_space_to_depth2_pad', [_vp, _vp, _vp, _i, _i, _i, _i, Pad2d, _i, _i, _i, _i, _i, _vp])
 _sig('dlwp_space_to_depth2_pad_bwd', [_vp, _vp, _vp, _i, _i, _i, _i, Pad2d, _i, _i, _i, _i, _i, _vp])
+_sig('dlwp_depthwise2d_out_shape', [Shape4, Depthwise2d, _P(Shape4)])
+_sig('dlwp_depthwise2d_fwd', [_vp, _vp, _vp, _vp, _vp, Shape4, Depthwise2d, _i, _vp])
+_sig('dlwp_depthwise2d_bwd_data', [_vp, _vp, _vp, _vp, Shape4, Depthwise2d, _i, _vp])
+_sig('dlwp_depthwise2d_bwd_workspace', [Shape4, Depthwise2d], _sz)
+_sig('dlwp_depthwise2d_bwd_weight', [_vp, _vp, _vp, _vp, Shape4, Depthwise2d, _vp, _i, _i, _vp])
+_sig('dlwp_pointwise2d_fwd', [_vp, _vp, _vp, _vp, _vp, _i, _i, Pointwise2d, _i, _vp])
+_sig('dlwp_pointwise2d_bwd_data', [_vp, _vp, _vp, _vp, _i, _i, Pointwise2d, _i, _vp])
+_sig('dlwp_pointwise2d_bwd_workspace', [_i, _i, Pointwise2d], _sz)
+_sig('dlwp_pointwise2d_bwd_weight', [_vp, _vp, _vp, _vp, _i, _i, Pointwise2d, _vp, _i, _i, _vp])
 _sig('dlwp_conv2d_uses_bf16_weights', [_vp, Shape4, _P(Conv2d), _i])
 _sig('dlwp_conv2d_prefers_unfused_pool', [_vp, _i, _i, _i, _i, _i, _i])
 _sig('dlwp_conv2d_supports_out_pool', [_vp, Shape4, _P(Conv2d)])

@@ -533,6 +533,52 @@ class BackwardPass(object):
         else:
             book.deposit(op.src, op.in_c_off, cin, ops.space_to_depth2_pad_bwd(c.gD, cin, hh, ww, c.d))
 
+    def _sep_act_bias(self, c, channels):
+        """dy -> dz in place and the bias gradient of the stage that owns the layer's bias and activation (the existing
+        dlwp_act_bwd / dlwp_act_bwd_bias_grad / dlwp_bias_grad passes)"""
+        op, lay, gD = c.op, c.op.layer, c.gD
+        y = self.book.tensor(op.dst)
+        gv = self.trainer._grad_view
+        if lay.activation != 'linear' and lay.bias is not None:
+            ops.act_bwd_bias_grad(y, gD, op.act, gv(lay, 'bias'), channels, out=gD, ws_key=self.key('bias', c.k))
+            return
+        if lay.activation != 'linear':
+            ops.act_bwd(y, gD, op.act, out=gD)
+        if lay.bias is not None:
+            gb, bkey = gv(lay, 'bias'), self.key('bias', c.k)
+            self.lanes.run(lambda: ops.bias_grad(gD, gb, channels, ws_key=bkey))
+
+    def _pwconv(self, c):
+        """The 1 x 1 stage of a SeparableConv2D: activation and bias gradient, the pointwise kernel's gradient on a side lane (it reads
+        the intermediate tensor the training plan keeps), then the gradient of that intermediate tensor"""
+        op, lay, d, gD, src = c.op, c.op.layer, c.d, c.gD, c.src
+        self._sep_act_bias(c, lay.filters)
+        gw, wkey = self.trainer._grad_view(lay, 'pointwise_kernel'), self.key('wgrad', c.k)
+        self.lanes.run(lambda: ops.pointwise2d_bwd_weight(src, gD, gw, d, ws_key=wkey))
+        self.touched.add(id(lay))
+        self.book.deposit(op.src, 0, op.xs[0], ops.pointwise2d_bwd_data(gD, lay.pointwise_kernel, d))
+
+    def _dwconv(self, c):
+        """The depthwise stencil (DepthwiseConv2D, or the first stage of a SeparableConv2D, which has no bias / activation of its
+        own): the kernel's gradient on a side lane, then -- not for the model input -- the adjoint in the input, halo included,
+        written in place into the layer's channel window where that holds no gradient yet"""
+        op, lay, d, gD, src = c.op, c.op.layer, c.d, c.gD, c.src
+        cin, hh, ww = op.xs
+        if not isinstance(lay, L.SeparableConv2D):
+            self._sep_act_bias(c, cin * lay.depth_multiplier)
+        gk, wkey = self.trainer._grad_view(lay, 'depthwise_kernel'), self.key('wgrad', c.k)
+        self.lanes.run(lambda: ops.depthwise2d_bwd_weight(src, gD, gk, d, ws_key=wkey))
+        self.touched.add(id(lay))
+        if op.src == P.STATE_IN:       # (a first layer: nobody needs the gradient of the model input)
+            return
+        book = self.book
+        whole = op.in_c_off == 0 and cin == src.shape[1]
+        g = book.claim_window(op.src, op.in_c_off, cin) if not whole else None
+        if g is not None:
+            ops.depthwise2d_bwd_data(gD, lay.depthwise_kernel, d, hh, ww, out=g.view((self.n, -1, hh, ww)))
+        else:
+            book.deposit(op.src, op.in_c_off, cin, ops.depthwise2d_bwd_data(gD, lay.depthwise_kernel, d, hh, ww))
+
     def _crop(self, c):
         """Cropping2D: the gradient is zero padding"""
         if c.op.src != P.STATE_IN:
@@ -678,4 +724,5 @@ class BackwardPass(object):
 
     adjoints = {'d2s': _d2s, 'conv': _conv, 'rowconv': _rowconv, 'dense': _dense, 'dropout': _dropout, 'bn': _bn,
                 'lstm': _lstm, 'copy': _copy, 'pad': _pad, 'maxpool': _maxpool, 'avgpool': _avgpool, 'upsample': _upsample,
-                'bilinear': _bilinear, 'act': _act, 'merge': _merge, 'd2sc': _d2sc, 'crop': _crop, 's2dp': _s2dp}
+                'bilinear': _bilinear, 'act': _act, 'merge': _merge, 'd2sc': _d2sc, 'crop': _crop, 's2dp': _s2dp, 'dwconv': _dwconv,
+                'pwconv': _pwconv}

@@ -40,7 +40,8 @@ def install(force=False):
     keras = _module('keras')
     keras.layers = _module('keras.layers', **{k: v for k, v in vars(layers).items() if not k.startswith('_')})
     keras.layers.convolutional = _module('keras.layers.convolutional', ZeroPadding2D=layers.ZeroPadding2D,
-                                         Conv2DTranspose=layers.Conv2DTranspose, Cropping2D=layers.Cropping2D)
+                                         Conv2DTranspose=layers.Conv2DTranspose, Cropping2D=layers.Cropping2D,
+                                         SeparableConv2D=layers.SeparableConv2D, DepthwiseConv2D=layers.DepthwiseConv2D)
     keras.layers.advanced_activations = _module('keras.layers.advanced_activations', LeakyReLU=layers.LeakyReLU, ReLU=layers.ReLU,
                                                 ELU=layers.ELU, ThresholdedReLU=layers.ThresholdedReLU, PReLU=layers.PReLU,
                                                 Softmax=layers.Softmax)

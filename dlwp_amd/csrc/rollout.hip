@@ -80,6 +80,16 @@ int enqueue_op(dlwp_handle_t h, const dlwp_op& op, const void* src, void* dst, c
     case DLWP_OP_SPACE2DEPTH_PAD: // the halo in front of a strided Conv2D + its 'same' zeros + the de-interleave, one pass
       return dlwp_space_to_depth2_pad(h, src, dst, op.xs.n, op.xs.c, op.xs.h, op.xs.w, op.pad, op.aux[0], op.aux[1],
                                       op.conv.in_c_off, op.conv.in_c_total > 0 ? op.conv.in_c_total : op.xs.c, dtype, (void*)s);
+    case DLWP_OP_DEPTHWISE2D: {   // keras DepthwiseConv2D / the first stage of a SeparableConv2D: aux[0] = depth_multiplier
+      const dlwp_depthwise2d d{op.conv.kh, op.conv.kw, op.conv.dil_h, op.conv.dil_w, op.aux[0], op.conv.halo, op.conv.act,
+                               op.conv.in_c_off, op.conv.in_c_total, op.conv.out_c_off, op.conv.out_c_total};
+      return dlwp_depthwise2d_fwd(h, src, w, b, dst, op.xs, d, DLWP_F32, (void*)s);
+    }
+    case DLWP_OP_POINTWISE2D: {   // the 1 x 1 stage of a SeparableConv2D on the matrix cores
+      const dlwp_pointwise2d d{op.xs.c, op.conv.cout, op.conv.act, op.conv.in_c_off, op.conv.in_c_total, op.conv.out_c_off,
+                               op.conv.out_c_total};
+      return dlwp_pointwise2d_fwd(h, src, w, b, dst, op.xs.n, op.xs.h * op.xs.w, d, DLWP_F32, (void*)s);
+    }
     case DLWP_OP_CROP2D:          // keras Cropping2D: the adjoint of zero padding ("zero drops")
       return dlwp_pad2d_bwd(h, src, dst, op.xs.n * op.xs.c, op.xs.h - op.pad.top - op.pad.bottom,
                             op.xs.w - op.pad.left - op.pad.right, 1, op.pad, dtype, (void*)s);
@@ -226,7 +236,8 @@ static int create_impl(dlwp_handle_t h, const dlwp_op* plan_in, int n_ops, void*
                    op.src);
     DLWP_CHECK_ARG(op.dst != DLWP_BUF_STATE_IN && op.dst >= DLWP_BUF_OUT(n_outputs - 1) && op.dst < n_buffers,
                    "rollout op %d: dst buffer %d out of range", i, op.dst);
-    if (op.kind == DLWP_OP_CONV2D || op.kind == DLWP_OP_ROWCONV2D || op.kind == DLWP_OP_DENSE)
+    if (op.kind == DLWP_OP_CONV2D || op.kind == DLWP_OP_ROWCONV2D || op.kind == DLWP_OP_DENSE || op.kind == DLWP_OP_DEPTHWISE2D ||
+        op.kind == DLWP_OP_POINTWISE2D)
       DLWP_CHECK_ARG(op.w >= 0 && op.w < n_buffers && op.b >= -1 && op.b < n_buffers,
                      "rollout op %d: weight/bias buffer out of range", i);
     if (is_weight_op(op))
@@ -326,7 +337,8 @@ static int create_impl(dlwp_handle_t h, const dlwp_op* plan_in, int n_ops, void*
       for (int i = 0; i < n_ops && rc == DLWP_OK; ++i) {
         const dlwp_op& op = plan[i];
         if (is_weight_op(op)) continue;   // done once, at the head of the graph
-        const bool weighted = op.kind == DLWP_OP_CONV2D || op.kind == DLWP_OP_ROWCONV2D || op.kind == DLWP_OP_DENSE;
+        const bool weighted = op.kind == DLWP_OP_CONV2D || op.kind == DLWP_OP_ROWCONV2D || op.kind == DLWP_OP_DENSE ||
+                              op.kind == DLWP_OP_DEPTHWISE2D || op.kind == DLWP_OP_POINTWISE2D;
         const bool scale = op.kind == DLWP_OP_SCALE;
         const bool bn = op.kind == DLWP_OP_BATCHNORM;
         const void* w = (weighted || ((bn || scale) && op.w >= 0)) ? buffers[op.w] : nullptr;

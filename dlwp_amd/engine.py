@@ -133,6 +133,14 @@ class Executor(object):
                                                op.out_pool, op.out_d2s, op.lstm_f, op.rec_act))
                 elif op.kind in ('pad', 'crop', 's2dp'):
                     descs.append(ops.make_pad(*op.halo))
+                elif op.kind == 'dwconv':
+                    kh, kw = op.layer.kernel_size
+                    descs.append(ops.make_depthwise(kh, kw, tuple(op.layer.dilation_rate), op.layer.depth_multiplier,
+                                                    ops.make_pad(*op.halo), op.act, op.in_c_off, op.in_c_total, op.out_c_off,
+                                                    op.out_c_total))
+                elif op.kind == 'pwconv':
+                    descs.append(ops.make_pointwise(op.xs[0], op.out_shape[0], op.act, op.in_c_off, op.in_c_total, op.out_c_off,
+                                                    op.out_c_total))
                 else:
                     descs.append(None)
             self._few_wino = False
@@ -334,6 +342,10 @@ class Executor(object):
             elif op.kind == 'sphasew':        # Conv2D(strides=2): kernel -> the kernel on its 4 cin phase channels
                 ops.sconv_weights(op.layer.kernel, w2=self.phase_buffers()[op.wparam][0])
                 continue
+            elif op.kind == 'dwconv':         # DepthwiseConv2D / the stencil of a SeparableConv2D (which has no bias of its own)
+                ops.depthwise2d(src, op.layer.depthwise_kernel, op.layer.depthwise_part.bias, d, out=dst)
+            elif op.kind == 'pwconv':         # the 1 x 1 product of a SeparableConv2D
+                ops.pointwise2d(src, op.layer.pointwise_kernel, op.layer.bias, d, out=dst)
             elif op.kind == 's2dp':           # halo + 'same' zeros + de-interleave, one pass
                 ops.space_to_depth2_pad(src, op.xs[0], d, op.out_shape[1], op.out_shape[2], c_off=op.in_c_off, out=dst)
             elif op.kind == 'pad':
@@ -542,6 +554,14 @@ class Executor(object):
                     if t is not None:
                         table.append(t)
                 sidx[role] = ent
+        qidx = {}                                  # DepthwiseConv2D / SeparableConv2D: depthwise kernel, pointwise kernel | -1, bias | -1
+        for lay in self.plan.sep_layers:
+            ent = []
+            for t in (lay.depthwise_kernel, getattr(lay, 'pointwise_kernel', None), lay.bias):
+                ent.append(len(table) if t is not None else -1)
+                if t is not None:
+                    table.append(t)
+            qidx[id(lay)] = ent
         pidx = []                                  # derived (phase-summed) kernels: (w2 index, b2 index | -1)
         for w2, b2 in self.phase_buffers():
             pidx.append((len(table), len(table) + 1 if b2 is not None else -1))
@@ -554,7 +574,8 @@ class Executor(object):
                 'bn': _lib.OP_BATCHNORM, 'dense': _lib.OP_DENSE, 'scale': _lib.OP_SCALE, 'act': _lib.OP_ACTIVATION,
                 'merge': _lib.OP_MERGE, 'avgpool': _lib.OP_AVGPOOL2, 'bilinear': _lib.OP_BILINEAR2,
                 'tphasew': _lib.OP_TCONV_WEIGHTS, 'd2sc': _lib.OP_DEPTH2SPACE_CROP, 'crop': _lib.OP_CROP2D,
-                'sphasew': _lib.OP_SCONV_WEIGHTS, 's2dp': _lib.OP_SPACE2DEPTH_PAD}
+                'sphasew': _lib.OP_SCONV_WEIGHTS, 's2dp': _lib.OP_SPACE2DEPTH_PAD, 'dwconv': _lib.OP_DEPTHWISE2D,
+                'pwconv': _lib.OP_POINTWISE2D}
         arr = (_lib.Op * len(self.plan.ops))()
         for k, (op, d) in enumerate(zip(self.plan.ops, self._descriptors())):
             o = arr[k]
@@ -610,6 +631,20 @@ class Executor(object):
                 o.conv.cout, o.conv.kh, o.conv.kw = op.layer.filters, op.layer.kernel_size[0], op.layer.kernel_size[1]
                 o.aux[1], o.aux[2] = self.plan.phase_params[op.wparam]['w2_shape'][:2]      # the stored taps
                 o.xs = _lib.Shape4(n, op.xs[0], 1, 1)
+            elif op.kind == 'dwconv':                  # the depthwise stencil: conv = taps, dilation, halo, act, windows; aux[0] = dm
+                dk, pk, bi = qidx[id(op.layer)]
+                o.w, o.b = dk, (bi if pk < 0 else -1)      # (the bias of a SeparableConv2D belongs to its pointwise stage)
+                o.conv.kh, o.conv.kw, o.conv.dil_h, o.conv.dil_w = d.kh, d.kw, d.dil_h, d.dil_w
+                o.conv.halo, o.conv.act = d.halo, d.act
+                o.conv.in_c_off, o.conv.in_c_total, o.conv.out_c_off, o.conv.out_c_total = (d.in_c_off, d.in_c_total, d.out_c_off,
+                                                                                             d.out_c_total)
+                o.aux[0] = d.depth_multiplier
+            elif op.kind == 'pwconv':                  # the 1 x 1 product: conv = cout, act, windows
+                dk, pk, bi = qidx[id(op.layer)]
+                o.w, o.b = pk, bi
+                o.conv.cout, o.conv.act = d.o, d.act
+                o.conv.in_c_off, o.conv.in_c_total, o.conv.out_c_off, o.conv.out_c_total = (d.in_c_off, d.in_c_total, d.out_c_off,
+                                                                                             d.out_c_total)
             elif op.kind == 's2dp':                    # the padded space-to-depth: pad = the halo, aux = hp, wp
                 o.pad = d
                 o.conv.in_c_off, o.conv.in_c_total = op.in_c_off, op.in_c_total
@@ -921,6 +956,10 @@ class Model(object):
             raise NotImplementedError('bfloat16 activation storage of a model with a Conv2D(strides=2) layer (%s) is not '
                                       'implemented (the padded space-to-depth kernels read and write float32)'
                                       % ', '.join(p['layer'].name for p in self.plan.phase_params if p.get('kind') == 'sconv'))
+        if dtype == 'bfloat16' and self.plan.sep_layers:
+            raise NotImplementedError('bfloat16 activation storage of a model with DepthwiseConv2D / SeparableConv2D layers (%s) is '
+                                      'not implemented (the stencil and 1 x 1 kernels read and write float32)'
+                                      % ', '.join(lay.name for lay in self.plan.sep_layers))
         if dtype != self.activation_dtype:
             self.activation_dtype = dtype
             # interleaved phase stores (dlwp_conv2d.out_d2s) belong to the float32 Winograd kernels; with bfloat16 storage

@@ -301,6 +301,208 @@ class Conv2D(Layer):
         return cfg
 
 
+class _SepPart(object):
+    """One of the two stages of a SeparableConv2D (or the one stage of a DepthwiseConv2D), presented like a layer of its own: it
+    reads the parent's weights through properties, so re-homed (flattened) parameters stay visible (as _ConvPart does)."""
+
+    def __init__(self, parent, which, last):
+        self.parent, self.which = parent, which            # which: 'depthwise_kernel' | 'pointwise_kernel'
+        self.name = '%s/%s' % (parent.name, which[:-len('_kernel')])
+        self.activation = parent.activation if last else 'linear'
+        self._last = last
+
+    @property
+    def kernel(self):
+        return getattr(self.parent, self.which)
+
+    @property
+    def bias(self):
+        return self.parent.bias if self._last else None
+
+
+def _pair(v, what):
+    p = (v, v) if isinstance(v, (int, np.integer)) else tuple(v)
+    if len(p) != 2:
+        raise ValueError('%s must be an int or a pair, got %r' % (what, v))
+    return tuple(int(a) for a in p)
+
+
+class DepthwiseConv2D(Layer):
+    """keras.layers.DepthwiseConv2D (Keras 2.2.4): strides 1, 'valid' | 'same', dilation 1..4, depth_multiplier 1..8, kernel sizes
+    1..7 per axis, bias, activation in {None,'linear','tanh','relu'}, data_format='channels_first'.
+    Weights, in Keras order: depthwise_kernel (kh, kw, cin, dm) glorot_uniform (Keras' _compute_fans on this shape: fan_in =
+    kh kw cin, fan_out = kh kw dm), bias (cin dm,) zeros.  Output channel c dm + m reads input channel c (csrc/sepconv.hip)."""
+
+    _has_pointwise = False
+
+    def __init__(self, kernel_size, strides=(1, 1), padding='valid', depth_multiplier=1, data_format=None, dilation_rate=(1, 1),
+                 activation=None, use_bias=True, depthwise_initializer='glorot_uniform', bias_initializer='zeros',
+                 depthwise_regularizer=None, bias_regularizer=None, activity_regularizer=None, depthwise_constraint=None,
+                 bias_constraint=None, **kwargs):
+        super(DepthwiseConv2D, self).__init__(**kwargs)
+        self._init_common(kernel_size, strides, padding, depth_multiplier, data_format, dilation_rate, activation, use_bias,
+                          bias_initializer, bias_regularizer, activity_regularizer, bias_constraint)
+        if depthwise_initializer not in ('glorot_uniform', 'zeros'):
+            raise NotImplementedError('%s: depthwise_initializer %r is not implemented (glorot_uniform, zeros are)'
+                                      % (type(self).__name__, depthwise_initializer))
+        if depthwise_constraint is not None:
+            raise NotImplementedError('%s: depthwise_constraint is not implemented' % type(self).__name__)
+        self.depthwise_initializer = depthwise_initializer
+        self.depthwise_regularizer = depthwise_regularizer     # l2 handled by the trainer, as Conv2D's kernel_regularizer
+        self.depthwise_kernel = None
+        self.depthwise_part = _SepPart(self, 'depthwise_kernel', last=not self._has_pointwise)
+
+    def _init_common(self, kernel_size, strides, padding, depth_multiplier, data_format, dilation_rate, activation, use_bias,
+                     bias_initializer, bias_regularizer, activity_regularizer, bias_constraint):
+        who = type(self).__name__
+        ks, st, dl = _pair(kernel_size, 'kernel_size'), _pair(strides, 'strides'), _pair(dilation_rate, 'dilation_rate')
+        if st != (1, 1):
+            raise NotImplementedError('%s: only strides=1 is implemented, got strides %r' % (who, strides))
+        if padding not in ('valid', 'same'):
+            raise ValueError("%s padding must be 'valid' or 'same'" % who)
+        if any(k < 1 or k > 7 for k in ks):
+            raise ValueError('%s: kernel_size %r (1 .. 7 per axis)' % (who, ks))
+        if any(d < 1 or d > 4 for d in dl):
+            raise ValueError('%s: dilation_rate %r (1 .. 4 per axis)' % (who, dl))
+        if int(depth_multiplier) != depth_multiplier or not 1 <= int(depth_multiplier) <= 8:
+            raise ValueError('%s: depth_multiplier %r (1 .. 8)' % (who, depth_multiplier))
+        if callable(activation):
+            activation = getattr(activation, '__name__', None)
+        if activation not in (None, 'linear', 'tanh', 'relu'):
+            raise NotImplementedError('%s activation %r is not implemented (linear, tanh, relu are)' % (who, activation))
+        if bias_initializer not in ('zeros',):
+            raise NotImplementedError('%s: bias_initializer %r is not implemented (zeros is)' % (who, bias_initializer))
+        if activity_regularizer is not None:
+            raise NotImplementedError('%s: activity_regularizer is not implemented' % who)
+        if bias_regularizer is not None:
+            raise NotImplementedError('%s: bias_regularizer is not implemented' % who)
+        if bias_constraint is not None:
+            raise NotImplementedError('%s: bias_constraint is not implemented' % who)
+        self.kernel_size, self.strides, self.padding, self.dilation_rate = ks, (1, 1), padding, dl
+        self.depth_multiplier = int(depth_multiplier)
+        self.data_format = normalize_data_format(data_format)
+        if self.data_format != 'channels_first':
+            raise NotImplementedError("%s: data_format='channels_first' is required (pass it explicitly; Keras' default is "
+                                      "channels_last)" % who)
+        self.activation = activation or 'linear'
+        self.use_bias = bool(use_bias)
+        self.bias = None
+
+    same_halo = Conv2D.same_halo
+
+    def _out_channels(self, cin):
+        return cin * self.depth_multiplier
+
+    def compute_output_shape(self, s):
+        if len(s) != 3:
+            raise ValueError('%s expects 4D input, got per-sample shape %r' % (self.name, s))
+        c, h, w = s
+        if self.padding == 'same':
+            return (self._out_channels(c), h, w)
+        ho = h - self.dilation_rate[0] * (self.kernel_size[0] - 1)
+        wo = w - self.dilation_rate[1] * (self.kernel_size[1] - 1)
+        if ho <= 0 or wo <= 0:
+            raise ValueError('%s: kernel %r with dilation %r does not fit the input %r' %
+                             (self.name, self.kernel_size, self.dilation_rate, s))
+        return (self._out_channels(c), ho, wo)
+
+    @staticmethod
+    def _glorot(rng, shape, fan_in, fan_out):
+        limit = math.sqrt(6.0 / (fan_in + fan_out))
+        return rng.uniform(-limit, limit, size=shape).astype(np.float32)
+
+    def _new_depthwise(self, cin, rng):
+        kh, kw = self.kernel_size
+        shape = (kh, kw, cin, self.depth_multiplier)
+        if self.depthwise_initializer == 'glorot_uniform':        # (_compute_fans: receptive field x shape[-2] / shape[-1])
+            return self._glorot(rng, shape, kh * kw * cin, kh * kw * self.depth_multiplier)
+        return np.zeros(shape, dtype=np.float32)
+
+    def build(self, input_shape, device, rng):
+        import torch
+        if self.built:
+            if self.depthwise_kernel.shape[2] != input_shape[0]:
+                raise ValueError('%s was built for %d input channels, now called with %d' %
+                                 (self.name, self.depthwise_kernel.shape[2], input_shape[0]))
+            return
+        cin = int(input_shape[0])
+        self.depthwise_kernel = torch.from_numpy(self._new_depthwise(cin, rng)).to(device)
+        self._weights = [('depthwise_kernel', self.depthwise_kernel)]
+        if self.use_bias:
+            self.bias = torch.zeros(cin * self.depth_multiplier, dtype=torch.float32, device=device)
+            self._weights.append(('bias', self.bias))
+        self.built = True
+
+    def get_config(self):
+        cfg = super(DepthwiseConv2D, self).get_config()
+        cfg.update({'kernel_size': self.kernel_size, 'strides': self.strides, 'padding': self.padding,
+                    'data_format': self.data_format, 'dilation_rate': self.dilation_rate, 'activation': self.activation,
+                    'use_bias': self.use_bias, 'depth_multiplier': self.depth_multiplier})
+        return cfg
+
+
+class SeparableConv2D(DepthwiseConv2D):
+    """keras.layers.SeparableConv2D (Keras 2.2.4): a depthwise stencil (no bias, no activation) followed by a 1 x 1 product that
+    applies both.  Weights, in Keras order: depthwise_kernel (kh, kw, cin, dm), pointwise_kernel (1, 1, cin dm, filters)
+    (glorot_uniform: fan_in = cin dm, fan_out = filters), bias (filters,).  The two stages are `depthwise_part` / `pointwise_part`
+    (as ConvLSTM2D's input_part / recurrent_part); the pointwise product runs on the matrix cores (csrc/sepconv.hip)."""
+
+    _has_pointwise = True
+
+    def __init__(self, filters, kernel_size, strides=(1, 1), padding='valid', data_format=None, dilation_rate=(1, 1),
+                 depth_multiplier=1, activation=None, use_bias=True, depthwise_initializer='glorot_uniform',
+                 pointwise_initializer='glorot_uniform', bias_initializer='zeros', depthwise_regularizer=None,
+                 pointwise_regularizer=None, bias_regularizer=None, activity_regularizer=None, depthwise_constraint=None,
+                 pointwise_constraint=None, bias_constraint=None, **kwargs):
+        super(SeparableConv2D, self).__init__(kernel_size, strides=strides, padding=padding, depth_multiplier=depth_multiplier,
+                                              data_format=data_format, dilation_rate=dilation_rate, activation=activation,
+                                              use_bias=use_bias, depthwise_initializer=depthwise_initializer,
+                                              bias_initializer=bias_initializer, depthwise_regularizer=depthwise_regularizer,
+                                              bias_regularizer=bias_regularizer, activity_regularizer=activity_regularizer,
+                                              depthwise_constraint=depthwise_constraint, bias_constraint=bias_constraint, **kwargs)
+        if pointwise_initializer not in ('glorot_uniform', 'zeros'):
+            raise NotImplementedError('SeparableConv2D: pointwise_initializer %r is not implemented (glorot_uniform, zeros are)'
+                                      % (pointwise_initializer,))
+        if pointwise_constraint is not None:
+            raise NotImplementedError('SeparableConv2D: pointwise_constraint is not implemented')
+        self.filters = int(filters)
+        if self.filters < 1:
+            raise ValueError('SeparableConv2D: filters %r' % (filters,))
+        self.pointwise_initializer = pointwise_initializer
+        self.pointwise_regularizer = pointwise_regularizer
+        self.pointwise_kernel = None
+        self.pointwise_part = _SepPart(self, 'pointwise_kernel', last=True)
+
+    def _out_channels(self, cin):
+        return self.filters
+
+    def build(self, input_shape, device, rng):
+        import torch
+        if self.built:
+            if self.depthwise_kernel.shape[2] != input_shape[0]:
+                raise ValueError('%s was built for %d input channels, now called with %d' %
+                                 (self.name, self.depthwise_kernel.shape[2], input_shape[0]))
+            return
+        cin = int(input_shape[0])
+        q = cin * self.depth_multiplier
+        self.depthwise_kernel = torch.from_numpy(self._new_depthwise(cin, rng)).to(device)
+        if self.pointwise_initializer == 'glorot_uniform':
+            pk = self._glorot(rng, (1, 1, q, self.filters), q, self.filters)
+        else:
+            pk = np.zeros((1, 1, q, self.filters), dtype=np.float32)
+        self.pointwise_kernel = torch.from_numpy(pk).to(device)
+        self._weights = [('depthwise_kernel', self.depthwise_kernel), ('pointwise_kernel', self.pointwise_kernel)]
+        if self.use_bias:
+            self.bias = torch.zeros(self.filters, dtype=torch.float32, device=device)
+            self._weights.append(('bias', self.bias))
+        self.built = True
+
+    def get_config(self):
+        cfg = super(SeparableConv2D, self).get_config()
+        cfg['filters'] = self.filters
+        return cfg
+
+
 class RowConnected2D(Layer):
     """DLWP.custom.RowConnected2D (reference DLWP/custom.py:695-837; a keras LocallyConnected2D subclass): a convolution whose
     filters are shared along a row only.  kernel (output_rows, kh, kw, cin, filters), bias (output_rows, 1, filters)

@@ -802,6 +802,142 @@ def space_to_depth2_pad_bwd(dout, c, in_h, in_w, pad, out=None, c_off=0):
     return out
 
 
+def make_depthwise(kh, kw, dil=1, depth_multiplier=1, halo=None, act=ACT_LINEAR, in_c_off=0, in_c_total=0, out_c_off=0,
+                   out_c_total=0):
+    """A dlwp_depthwise2d descriptor (include/dlwp_hip.h); channel totals of 0 = the window itself."""
+    dh, dw = (dil, dil) if isinstance(dil, int) else dil
+    return _lib.Depthwise2d(int(kh), int(kw), int(dh), int(dw), int(depth_multiplier), halo if halo is not None else make_pad(),
+                            int(act), int(in_c_off), int(in_c_total), int(out_c_off), int(out_c_total))
+
+
+def make_pointwise(q, o, act=ACT_LINEAR, in_c_off=0, in_c_total=0, out_c_off=0, out_c_total=0):
+    """A dlwp_pointwise2d descriptor (include/dlwp_hip.h); channel totals of 0 = the window itself."""
+    return _lib.Pointwise2d(int(q), int(o), int(act), int(in_c_off), int(in_c_total), int(out_c_off), int(out_c_total))
+
+
+def depthwise_out_shape(xs, d):
+    """Shape4 of the output of a depthwise stencil on the input window xs (host only; DlwpError where the descriptor is refused)."""
+    ys = Shape4()
+    _lib.check(_lib.lib.dlwp_depthwise2d_out_shape(xs, d, ctypes.byref(ys)))
+    return ys
+
+
+def depthwise2d(x, k, bias, d, out=None):
+    """keras DepthwiseConv2D forward: channels [d.in_c_off, +cin) of x (n, c_total, h, w) under d.halo, kernel k (kh, kw, cin, dm),
+    bias (cin dm) or None -> channels [d.out_c_off, +cin dm) of `out` (a new dense tensor when None).  include/dlwp_hip.h:
+    dlwp_depthwise2d_fwd."""
+    _check_f32(x, k, bias, out)
+    n, c_total, hh, ww = x.shape
+    cin = int(k.shape[2])
+    xs = Shape4(n, cin, hh, ww)
+    d = _lib.Depthwise2d.from_buffer_copy(d)
+    d.in_c_total = c_total
+    if out is not None:
+        d.out_c_total = int(out.shape[1])
+    ys = depthwise_out_shape(xs, d)
+    if out is None:
+        out = torch.empty((n, d.out_c_total if d.out_c_total > 0 else ys.c, ys.h, ys.w), dtype=torch.float32, device=x.device)
+    if out.shape[0] != n or tuple(out.shape[2:]) != (ys.h, ys.w):
+        raise ValueError('depthwise2d: output shape %r, expected (%d, *, %d, %d)' % (tuple(out.shape), n, ys.h, ys.w))
+    _lib.check(_lib.lib.dlwp_depthwise2d_fwd(_lib.handle(_dev(x)), _ptr(x), _ptr(k), _ptr(bias), _ptr(out), xs, d, _lib.F32,
+                                             _stream(x)))
+    return out
+
+
+def depthwise2d_bwd_data(dz, k, d, in_h, in_w, out=None):
+    """Adjoint of depthwise2d in its input, halo included: dz (n, z_total, ho, wo)[d.out_c_off:+cin dm] -> channels
+    [d.in_c_off, +cin) of `out` (n, c_total, in_h, in_w) (a new dense tensor when None).  The window is overwritten."""
+    _check_f32(dz, k, out)
+    n = dz.shape[0]
+    cin = int(k.shape[2])
+    xs = Shape4(n, cin, int(in_h), int(in_w))
+    d = _lib.Depthwise2d.from_buffer_copy(d)
+    d.out_c_total = int(dz.shape[1])
+    if out is None:
+        d.in_c_off, d.in_c_total = 0, cin
+        out = torch.empty((n, cin, int(in_h), int(in_w)), dtype=torch.float32, device=dz.device)
+    else:
+        d.in_c_total = int(out.shape[1])
+    ys = depthwise_out_shape(xs, d)
+    if out.shape[0] != n or tuple(out.shape[2:]) != (int(in_h), int(in_w)) or tuple(dz.shape[2:]) != (ys.h, ys.w):
+        raise ValueError('depthwise2d_bwd_data: gradient %r / output %r do not belong to an input of %d x %d'
+                         % (tuple(dz.shape), tuple(out.shape), in_h, in_w))
+    _lib.check(_lib.lib.dlwp_depthwise2d_bwd_data(_lib.handle(_dev(dz)), _ptr(dz), _ptr(k), _ptr(out), xs, d, _lib.F32, _stream(dz)))
+    return out
+
+
+def depthwise2d_bwd_weight(x, dz, dk, d, accumulate=False, ws_key=None):
+    """dk (kh, kw, cin, dm) (+)= the depthwise kernel's gradient from the layer input x (its window d.in_c_off) and dz (its window
+    d.out_c_off): two launches, a fixed tree, the same bits on every run (include/dlwp_hip.h: dlwp_depthwise2d_bwd_weight)."""
+    _check_f32(x, dz, dk)
+    n, c_total, hh, ww = x.shape
+    cin = int(dk.shape[2])
+    xs = Shape4(n, cin, hh, ww)
+    d = _lib.Depthwise2d.from_buffer_copy(d)
+    d.in_c_total, d.out_c_total = c_total, int(dz.shape[1])
+    ys = depthwise_out_shape(xs, d)
+    if dz.shape[0] != n or tuple(dz.shape[2:]) != (ys.h, ys.w) or tuple(dk.shape) != (d.kh, d.kw, cin, d.depth_multiplier):
+        raise ValueError('depthwise2d_bwd_weight: shapes %r, %r, %r do not belong together'
+                         % (tuple(x.shape), tuple(dz.shape), tuple(dk.shape)))
+    ws = workspace(x.device, _lib.lib.dlwp_depthwise2d_bwd_workspace(xs, d), ('dw_wgrad', ws_key))
+    _lib.check(_lib.lib.dlwp_depthwise2d_bwd_weight(_lib.handle(_dev(x)), _ptr(x), _ptr(dz), _ptr(dk), xs, d, _ptr(ws),
+                                                    int(bool(accumulate)), _lib.F32, _stream(x)))
+    return dk
+
+
+def pointwise2d(x, w, bias, d, out=None):
+    """The 1 x 1 product of a SeparableConv2D on the matrix cores: channels [d.in_c_off, +q) of x (n, c_total, h, w), w (q, o) (or
+    keras' (1, 1, q, o)), bias (o) or None -> channels [d.out_c_off, +o) of `out` (a new dense tensor when None)."""
+    _check_f32(x, w, bias, out)
+    n, c_total, hh, ww = x.shape
+    d = _lib.Pointwise2d.from_buffer_copy(d)
+    d.in_c_total = c_total
+    if w.numel() != d.q * d.o:
+        raise ValueError('pointwise2d: kernel %r is not (%d, %d)' % (tuple(w.shape), d.q, d.o))
+    if out is None:
+        out = torch.empty((n, d.out_c_total if d.out_c_total > 0 else d.o, hh, ww), dtype=torch.float32, device=x.device)
+    d.out_c_total = int(out.shape[1])
+    if out.shape[0] != n or tuple(out.shape[2:]) != (hh, ww):
+        raise ValueError('pointwise2d: output shape %r' % (tuple(out.shape),))
+    _lib.check(_lib.lib.dlwp_pointwise2d_fwd(_lib.handle(_dev(x)), _ptr(x), _ptr(w), _ptr(bias), _ptr(out), n, hh * ww, d, _lib.F32,
+                                             _stream(x)))
+    return out
+
+
+def pointwise2d_bwd_data(dz, w, d, out=None):
+    """dx[n][q][p] = sum_o dz[n][o][p] w[q][o]: dz (n, z_total, h, w)[d.out_c_off:+o] -> channels [d.in_c_off, +q) of `out` (a new
+    dense tensor when None); the window is overwritten."""
+    _check_f32(dz, w, out)
+    n, z_total, hh, ww = dz.shape
+    d = _lib.Pointwise2d.from_buffer_copy(d)
+    d.out_c_total = z_total
+    if out is None:
+        d.in_c_off, d.in_c_total = 0, d.q
+        out = torch.empty((n, d.q, hh, ww), dtype=torch.float32, device=dz.device)
+    else:
+        d.in_c_total = int(out.shape[1])
+    if out.shape[0] != n or tuple(out.shape[2:]) != (hh, ww) or w.numel() != d.q * d.o:
+        raise ValueError('pointwise2d_bwd_data: shapes %r, %r, %r' % (tuple(dz.shape), tuple(w.shape), tuple(out.shape)))
+    _lib.check(_lib.lib.dlwp_pointwise2d_bwd_data(_lib.handle(_dev(dz)), _ptr(dz), _ptr(w), _ptr(out), n, hh * ww, d, _lib.F32,
+                                                  _stream(dz)))
+    return out
+
+
+def pointwise2d_bwd_weight(x, dz, dw, d, accumulate=False, ws_key=None):
+    """dw (q, o) (+)= sum over samples and pixels of x[n][q][p] dz[n][o][p]: a fixed split over (sample, pixel) and a deterministic
+    final sum (include/dlwp_hip.h: dlwp_pointwise2d_bwd_weight)."""
+    _check_f32(x, dz, dw)
+    n, c_total, hh, ww = x.shape
+    d = _lib.Pointwise2d.from_buffer_copy(d)
+    d.in_c_total, d.out_c_total = c_total, int(dz.shape[1])
+    if dz.shape[0] != n or tuple(dz.shape[2:]) != (hh, ww) or dw.numel() != d.q * d.o:
+        raise ValueError('pointwise2d_bwd_weight: shapes %r, %r, %r' % (tuple(x.shape), tuple(dz.shape), tuple(dw.shape)))
+    ws = workspace(x.device, _lib.lib.dlwp_pointwise2d_bwd_workspace(n, hh * ww, d), ('pw_wgrad', ws_key))
+    _lib.check(_lib.lib.dlwp_pointwise2d_bwd_weight(_lib.handle(_dev(x)), _ptr(x), _ptr(dz), _ptr(dw), n, hh * ww, d, _ptr(ws),
+                                                    int(bool(accumulate)), _lib.F32, _stream(x)))
+    return dw
+
+
 def uses_bf16_weights(xs, cd, dtype):
     """Does conv2d on an input of shape xs = (n, c, h, w) stored as `dtype` (a _lib.dtype_io code) multiply with weights
     rounded to bfloat16 (the bf16 matrix-core kernels)?  Host logic only."""

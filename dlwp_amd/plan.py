@@ -66,7 +66,7 @@ class View(object):
 
 class PlanOp(object):
     """One launch.  kind in {'conv','rowconv','pad','maxpool','avgpool','upsample','bilinear','copy','lstm','phasew','d2s','bn',
-    'dense','dropout','scale','act','merge','tphasew','d2sc','crop','sphasew','s2dp'}."""
+    'dense','dropout','scale','act','merge','tphasew','d2sc','crop','sphasew','s2dp','dwconv','pwconv'}."""
 
     def __init__(self, kind, src, dst, xs, **kw):
         self.kind, self.src, self.dst = kind, src, dst
@@ -140,6 +140,9 @@ class PlanOp(object):
         if self.kind == 's2dp':
             extra = ' halo%s cin[%d:+%d/%d] -> %r' % (tuple(self.halo), self.in_c_off, self.xs[0], self.in_c_total,
                                                      tuple(self.out_shape))
+        if self.kind in ('dwconv', 'pwconv'):
+            extra = ' %s halo%s act%d cin[%d:+%d/%d] -> %r' % (self.layer.name, tuple(self.halo), self.act, self.in_c_off, self.xs[0],
+                                                              self.in_c_total, tuple(self.out_shape))
         return '<%s %s -> %s xs=%s%s>' % (self.kind, self.src, self.dst, self.xs, extra)
 
 
@@ -156,6 +159,7 @@ class Plan(object):
         self.dense_layers = []   # Dense layers in plan order (one 'dense' op each)
         self.dropout_layers = [] # Dropout layers in graph order (training plans: one 'dropout' op each; its index keys the mask)
         self.eltwise_layers = [] # activation / merge layers with a launch, in first-use order (stateless: any number of ops each)
+        self.sep_layers = []     # DepthwiseConv2D / SeparableConv2D layers in plan order (one 'dwconv' (+ one 'pwconv') op each)
 
     def new_buffer(self, c, h, w):
         self.buffers.append((int(c), int(h), int(w)))
@@ -731,6 +735,48 @@ def build_plan(inputs, outputs, inference=False, fuse_d2s=True, fuse_lstm=False,
                         in_c_off=0, in_c_total=4 * v.c, out_c_off=0, out_c_total=f, out_shape=(f, ho, wo), dil=(1, 1),
                         ksize=(sh, sw), filters=f, wparam=pidx, alg_flops=alg, input_image=v.buf == STATE_IN))
             producer.pop(dst, None)              # (a MaxPooling2D behind it stays a launch / a lazy source of its own)
+            views[t.uid] = View(dst, 0, f, f, ho, wo)
+        elif isinstance(lay, L.DepthwiseConv2D):
+            # keras DepthwiseConv2D / SeparableConv2D (csrc/sepconv.hip): 'dwconv' = the stencil, which takes the lazy halo of its
+            # input and the layer's own 'same' zeros composed (a lazy pooling / up-sampling view is materialised first: the stencil
+            # reads a stored tensor); for a SeparableConv2D it has neither bias nor activation and writes a plan buffer that the
+            # training step keeps (the pointwise weight gradient reads it), and 'pwconv' = the 1 x 1 product on the matrix cores
+            # with the layer's bias and activation, which writes the model's output slot or a buffer of its own.
+            if lay in plan.sep_layers:
+                raise NotImplementedError('%s: a %s layer applied more than once is not implemented' % (lay.name, type(lay).__name__))
+            plan.sep_layers.append(lay)
+            v = ins[0]
+            if v.shape is not None and len(v.shape) != 3:
+                raise NotImplementedError('%s on a non-3D tensor %r' % (lay.name, v.shape))
+            if v.src_mode != SRC_DIRECT:
+                v = materialize(v.copy(halo=NO_HALO)).copy(halo=v.halo)
+            halo = v.halo
+            if lay.padding == 'same':
+                st, sb, sl, sr = lay.same_halo()
+                halo2 = _compose_halo(halo, ((st, sb), (sl, sr)), PAD_ZERO)
+                if halo2 is None:
+                    v = materialize(v)
+                    halo2 = Halo(st, sb, sl, sr, PAD_ZERO, PAD_ZERO)
+                halo = halo2
+            _, hl, wl = v.copy(halo=halo).logical
+            ho = hl - lay.dilation_rate[0] * (lay.kernel_size[0] - 1)
+            wo = wl - lay.dilation_rate[1] * (lay.kernel_size[1] - 1)
+            if ho < 1 or wo < 1:
+                raise ValueError('%s: kernel %r with dilation %r does not fit the input' % (lay.name, lay.kernel_size, lay.dilation_rate))
+            q = v.c * lay.depth_multiplier
+            sep = isinstance(lay, L.SeparableConv2D)
+            f = lay.filters if sep else q
+            if outs:
+                dst = OUT(outs[0])
+                plan.output_store[outs[0]] = (f, ho, wo)
+            else:
+                dst = plan.new_buffer(f, ho, wo)
+            mid = plan.new_buffer(q, ho, wo) if sep else dst
+            emit(PlanOp('dwconv', v.buf, mid, (v.c, v.h, v.w), layer=lay, halo=halo, act=0 if sep else ACT[lay.activation],
+                        in_c_off=v.c_off, in_c_total=v.c_total, out_c_off=0, out_c_total=q, out_shape=(q, ho, wo)))
+            if sep:
+                emit(PlanOp('pwconv', mid, dst, (q, ho, wo), layer=lay, act=ACT[lay.activation], in_c_off=0, in_c_total=q,
+                            out_c_off=0, out_c_total=f, out_shape=(f, ho, wo)))
             views[t.uid] = View(dst, 0, f, f, ho, wo)
         elif isinstance(lay, L.Conv2D):
             v = ins[0]

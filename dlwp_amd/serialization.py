@@ -39,6 +39,16 @@ def _layer_config(lay):
                    use_bias=lay.use_bias)
         if isinstance(lay.kernel_regularizer, L1L2):
             cfg['kernel_regularizer'] = {'l2': lay.kernel_regularizer.l2}
+    elif isinstance(lay, L.DepthwiseConv2D):       # (and SeparableConv2D, its subclass)
+        from .regularizers import L1L2
+        cfg.update(kernel_size=list(lay.kernel_size), strides=list(lay.strides), padding=lay.padding, data_format=lay.data_format,
+                   dilation_rate=list(lay.dilation_rate), depth_multiplier=lay.depth_multiplier, activation=lay.activation,
+                   use_bias=lay.use_bias, depthwise_initializer=lay.depthwise_initializer)
+        if isinstance(lay, L.SeparableConv2D):
+            cfg.update(filters=lay.filters, pointwise_initializer=lay.pointwise_initializer)
+        for key in ('depthwise_regularizer', 'pointwise_regularizer'):
+            if isinstance(getattr(lay, key, None), L1L2):
+                cfg[key] = {'l2': getattr(lay, key).l2}
     elif isinstance(lay, L.RowConnected2D):
         from .regularizers import L1L2
         cfg.update(filters=lay.filters, kernel_size=list(lay.kernel_size), strides=list(lay.strides), padding=lay.padding,
@@ -214,6 +224,18 @@ def _keras_layer_spec(lay):
                  data_format=lay.data_format, dilation_rate=list(lay.dilation_rate), activation=lay.activation or 'linear',
                  use_bias=lay.use_bias, kernel_initializer=_GLOROT, bias_initializer=_ZEROS,
                  kernel_regularizer=reg(lay.kernel_regularizer), **tail)
+    elif isinstance(lay, L.DepthwiseConv2D):
+        # keras.layers.DepthwiseConv2D.get_config(): Conv2D's keys without filters / kernel_* + depth_multiplier and the depthwise_*
+        # keys; SeparableConv2D.get_config(): Conv2D's keys without kernel_* + depth_multiplier, depthwise_* and pointwise_* keys
+        init = {'glorot_uniform': _GLOROT, 'zeros': _ZEROS}
+        c.update(kernel_size=list(lay.kernel_size), strides=list(lay.strides), padding=lay.padding, data_format=lay.data_format,
+                 dilation_rate=list(lay.dilation_rate), activation=lay.activation or 'linear', use_bias=lay.use_bias,
+                 bias_initializer=_ZEROS, bias_regularizer=None, activity_regularizer=None, bias_constraint=None,
+                 depth_multiplier=lay.depth_multiplier, depthwise_initializer=init[lay.depthwise_initializer],
+                 depthwise_regularizer=reg(lay.depthwise_regularizer), depthwise_constraint=None)
+        if isinstance(lay, L.SeparableConv2D):
+            c.update(filters=lay.filters, pointwise_initializer=init[lay.pointwise_initializer],
+                     pointwise_regularizer=reg(lay.pointwise_regularizer), pointwise_constraint=None)
     elif isinstance(lay, L.RowConnected2D):
         c.update(filters=lay.filters, kernel_size=list(lay.kernel_size), strides=list(lay.strides), padding=lay.padding,
                  data_format=lay.data_format, activation=lay.activation or 'linear', use_bias=lay.use_bias,
@@ -396,10 +418,10 @@ def _keras_layer_kwargs(cls, cfg):
         if k in ('dtype', 'sparse') or k.endswith('_initializer') or k.endswith('_constraint') or k == 'activity_regularizer':
             continue
         if k.endswith('_regularizer'):
-            if isinstance(v, dict) and k == 'kernel_regularizer':
+            if isinstance(v, dict) and k in ('kernel_regularizer', 'depthwise_regularizer', 'pointwise_regularizer') and k in params:
                 c = v.get('config', {})
                 if c.get('l1', 0.0):
-                    raise NotImplementedError('l1 kernel regulariser in the checkpoint')
+                    raise NotImplementedError('l1 %s in the checkpoint' % k.replace('_', ' '))
                 kw[k] = L1L2(l2=float(c.get('l2', 0.0)))
             continue
         if k not in params and k not in ('name', 'trainable'):      # (the base Layer takes name / trainable / input_shape)
@@ -616,9 +638,10 @@ def load_model_file(path, custom_objects=None, device=None, package_objects=None
         for k in ('kernel_size', 'dilation_rate', 'strides', 'target_shape', 'input_shape'):
             if k in cfg and isinstance(cfg[k], list):
                 cfg[k] = tuple(cfg[k])
-        if isinstance(cfg.get('kernel_regularizer'), dict):
-            from .regularizers import L1L2
-            cfg['kernel_regularizer'] = L1L2(l2=cfg['kernel_regularizer']['l2'])
+        for key in ('kernel_regularizer', 'depthwise_regularizer', 'pointwise_regularizer'):
+            if isinstance(cfg.get(key), dict):
+                from .regularizers import L1L2
+                cfg[key] = L1L2(l2=cfg[key]['l2'])
         objs.append(cls(**cfg))
     tensors = []
     for node in arch['nodes']:

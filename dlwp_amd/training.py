@@ -568,7 +568,8 @@ class Trainer(object):
                     seen.add(id(op.layer))
             # every deferred sum of a step in ONE flush (csrc/common.h: DLWP_MAX_BATCH_JOBS = 24; an early flush would run on
             # whichever stream filled the table)
-            ok = ok and 2 * len(seen) + len(self.plan.output_store) <= 24 and 3 * len(seen) <= 24
+            n_red = len(seen) + len(self.plan.sep_layers)     # (a depthwise / separable layer defers its bias sum only)
+            ok = ok and 2 * n_red + len(self.plan.output_store) <= 24 and 3 * len(seen) <= 24
             self._fold = bool(ok)
         return self._fold
 
@@ -753,6 +754,10 @@ class Trainer(object):
             reg = getattr(lay, 'kernel_regularizer', None)
             if nm == 'kernel' and isinstance(reg, L1L2) and reg.l2 > 0:
                 yield reg.l2, off, numel
+            if nm in ('depthwise_kernel', 'pointwise_kernel'):      # DepthwiseConv2D / SeparableConv2D: one regulariser per kernel
+                reg = getattr(lay, nm[:-len('kernel')] + 'regularizer', None)
+                if isinstance(reg, L1L2) and reg.l2 > 0:
+                    yield reg.l2, off, numel
 
     def _add_regularizer_gradients(self):
         from . import ops

@@ -645,6 +645,65 @@ int dlwp_space_to_depth2_pad(dlwp_handle_t, const void* src, void* dst, int n, i
 int dlwp_space_to_depth2_pad_bwd(dlwp_handle_t, const void* ddst, void* dsrc, int n, int c, int in_h, int in_w, dlwp_pad2d pad,
                                  int hp, int wp, int c_off, int c_total, int dtype, void* stream);
 
+/* ---- keras DepthwiseConv2D / SeparableConv2D (strides 1, data_format='channels_first') (sepconv.hip).  float32 only.
+ *      Depthwise stencil, kernel K (kh, kw, cin, dm), bias (cin dm) nullable, output channel c dm + m:
+ *          y[n][c dm + m][i][j] = act(b[c dm + m] + sum_{u,v} xpad[n][c][i + u dil_h][j + v dil_w] K[u][v][c][m])
+ *      xpad = x under `halo` (the five DLWP_PAD_* modes per axis, the index map of dlwp_pad2d_fwd: the padding layers in front of
+ *      the layer and its own 'same' zeros arrive composed); out = padded - dil (k - 1) per axis.  xs = (n, cin, h, w) of the
+ *      input WINDOW [in_c_off, +cin) of in_c_total channels; y is window [out_c_off, +cin dm) of out_c_total channels (a total
+ *      of 0 = the window itself).  Every output element is one float32 fmaf chain that starts from the bias (or +0) and runs over
+ *      the taps in ascending (u, v).
+ *      dlwp_depthwise2d_out_shape (host only): ys = (n, cin dm, out_h, out_w), or an error.
+ *      dlwp_depthwise2d_bwd_data: the adjoint, halo included, in gather form (no atomics, no workspace):
+ *          dx[n][c][y][x] = sum over the padded positions (r, s) that map to (y, x) -- wrap adds the periodic images, edge adds to
+ *          the border, the mirrors add their reflections, zero drops: dlwp_pad2d_bwd's semantics -- of
+ *          sum_{m,u,v} dz[n][c dm + m][r - u dil_h][s - v dil_w] K[u][v][c][m].
+ *          dz lies in the descriptor's OUTPUT window, dx in its input window, which is OVERWRITTEN (every element written).
+ *      dlwp_depthwise2d_bwd_weight: dK[u][v][c][m] (+)= sum_{n,i,j} xpad[n][c][i + u dil_h][j + v dil_w] dz[n][c dm + m][i][j].
+ *          Two launches: partial sums over fixed runs of 4096 consecutive (n, i, j) positions into ws
+ *          (dlwp_depthwise2d_bwd_workspace bytes), then their sum in ascending order; no atomics, the same bits on every run.
+ *          accumulate = 1: dK = dK + (that sum), as dlwp_sconv_weights_bwd.
+ *      Pointwise product, kernel P (q, o) (= keras (1, 1, q, o)), bias (o) nullable, pixels contiguous:
+ *          y[n][o][p] = act(b[o] + sum_q x[n][q][p] P[q][o])             x (n, in_c_total, hw)[in_c_off:+q], y likewise [out_c_off:+o]
+ *      on v_mfma_f32_32x32x2_f32: every output element is one q-ordered float32 chain that starts from the bias; a sample's bits do
+ *      not depend on the batch it rides in.
+ *      dlwp_pointwise2d_bwd_data:   dx[n][q][p] = sum_o dz[n][o][p] P[q][o]   (dz in the output window; dx's window is overwritten)
+ *      dlwp_pointwise2d_bwd_weight: dP[q][o] (+)= sum_{n,p} x[n][q][p] dz[n][o][p].  Two launches: partial sums over fixed runs of
+ *          16 units (a unit = 32 consecutive pixels of one sample, samples in turn) into ws (dlwp_pointwise2d_bwd_workspace
+ *          bytes), then their sum in ascending order; accumulate as above.
+ *      act'(y) and the bias gradients are dlwp_act_bwd / dlwp_act_bwd_bias_grad / dlwp_bias_grad on the output.
+ *      The stream entry points refuse, without a launch and in this order: bad sizes, halos that do not fit the map, bad channel
+ *      windows, null pointers, a null handle. */
+typedef struct {
+  int kh, kw, dil_h, dil_w;       /* 1 .. 7 taps, dilation 1 .. 4 per axis                                     */
+  int depth_multiplier;           /* 1 .. 8                                                                    */
+  dlwp_pad2d halo;
+  int act;                        /* DLWP_ACT_* after the bias (forward only)                                  */
+  int in_c_off, in_c_total;       /* as dlwp_conv2d                                                            */
+  int out_c_off, out_c_total;
+} dlwp_depthwise2d;
+typedef struct {
+  int q, o;                       /* input / output channels                                                   */
+  int act;                        /* DLWP_ACT_* after the bias (forward only)                                  */
+  int in_c_off, in_c_total;
+  int out_c_off, out_c_total;
+} dlwp_pointwise2d;
+int dlwp_depthwise2d_out_shape(dlwp_shape4 xs, dlwp_depthwise2d d, dlwp_shape4* ys);
+int dlwp_depthwise2d_fwd(dlwp_handle_t, const void* x, const void* w, const void* bias, void* y, dlwp_shape4 xs, dlwp_depthwise2d d,
+                         int dtype, void* stream);
+int dlwp_depthwise2d_bwd_data(dlwp_handle_t, const void* dz, const void* w, void* dx, dlwp_shape4 xs, dlwp_depthwise2d d, int dtype,
+                              void* stream);
+size_t dlwp_depthwise2d_bwd_workspace(dlwp_shape4 xs, dlwp_depthwise2d d);
+int dlwp_depthwise2d_bwd_weight(dlwp_handle_t, const void* x, const void* dz, void* dw, dlwp_shape4 xs, dlwp_depthwise2d d, void* ws,
+                                int accumulate, int dtype, void* stream);
+int dlwp_pointwise2d_fwd(dlwp_handle_t, const void* x, const void* w, const void* bias, void* y, int n, int hw, dlwp_pointwise2d d,
+                         int dtype, void* stream);
+int dlwp_pointwise2d_bwd_data(dlwp_handle_t, const void* dz, const void* w, void* dx, int n, int hw, dlwp_pointwise2d d, int dtype,
+                              void* stream);
+size_t dlwp_pointwise2d_bwd_workspace(int n, int hw, dlwp_pointwise2d d);
+int dlwp_pointwise2d_bwd_weight(dlwp_handle_t, const void* x, const void* dz, void* dw, int n, int hw, dlwp_pointwise2d d, void* ws,
+                                int accumulate, int dtype, void* stream);
+
 /* ---- ConvLSTM2D cell update (keras ConvLSTM2DCell.call; call sites examples/train.py:148-155,
  *      examples/train_functional.py:207-219).  zx / zh: (n, 4F, h*w) gate pre-activations i | f | c | o from the input
  *      convolution (+bias) and the recurrent 'same' convolution of h_{t-1}; zh and c_prev may be NULL on the first step
@@ -863,6 +922,9 @@ int dlwp_scale_inv(dlwp_handle_t, const void* x, void* y, const void* shift, con
                                    * kw}, xs.c = cin, aux[1] / aux[2] = sh / sw.  Run ONCE at the head of the rollout graph.   */
 #define DLWP_OP_SPACE2DEPTH_PAD 20 /* dlwp_space_to_depth2_pad: src window [conv.in_c_off, +xs.c) of conv.in_c_total channels, xs =
                                    * (n, c, h, w) of that window -> dst (n, 4c, hp, wp); pad = the halo, aux = {hp, wp}        */
+#define DLWP_OP_DEPTHWISE2D 21    /* dlwp_depthwise2d_fwd: xs = (n, cin, h, w) of the input window; conv = {kh, kw, dil, halo, act, the
+                                   * channel windows}, aux[0] = depth_multiplier; w / b = depthwise kernel / bias (b may be NONE)  */
+#define DLWP_OP_POINTWISE2D 22    /* dlwp_pointwise2d_fwd: xs = (n, q, h, w); conv = {cout = o, act, the channel windows}; w / b  */
 typedef struct {
   int kind;                 /* DLWP_OP_*                                                                */
   int src, dst;             /* buffer indices                                                              */
