@@ -3,3 +3,4 @@ from .generators import (DataGenerator, ArrayDataset, SeriesDataGenerator, Serie
                          LabeledArray)
 from .extensions import TimeSeriesEstimator  # noqa: F401
 from . import verify  # noqa: F401
+from . import ensemble  # noqa: F401

@@ -1,0 +1,232 @@
+"""
+Ensemble verification: what reduces ACROSS the member axis of a perturbed-initial-condition rollout -- the ensemble mean and
+spread, the error of the mean, the spread-skill ratio, the CRPS and the rank histogram.  The reference has no such module: its
+examples/plot_ensemble.py:242,269 takes np.mean over members on the host.  Here the series predict_timeseries(...,
+return_device=True) leaves in HBM is scored where it is (csrc/ensemble.hip); DESIGN.md 5.35 has the kernels and the measurements.
+
+Definitions (the contract; the host and the device path compute exactly these).  A column is one (lead t, sample s, field point
+p): M member values x_0 .. x_{M-1} (float32) and, for the scores, one verifying value y (float32).  All per-column arithmetic is
+float64 on the float32 inputs; comparisons are made on the float32 values themselves.
+
+* mean = (sum_i x_i) / M, summed in member order.
+* variance: shifted sums with d_i = x_i - x_0 (exact in float64): var_ddof = (sum d_i^2 - (sum d_i)^2 / M) / (M - ddof), and
+  spread = sqrt(max(var, 0)).
+* CRPS terms: A = (1/M) sum_i |x_i - y| and B = sum_{i<j} |x_i - x_j|, computed as sum_k (2k - M + 1) x_(k) over the ascending
+  order x_(0) <= ... <= x_(M-1) (each product of a small integer and a float32 is exact in float64);
+  crps = A - B / M^2 and fair_crps = A - B / (M (M - 1)).
+* rank r = #{i : x_i < y} in 0 .. M.  Ties count as not below; there is no randomisation, so repeated runs give identical
+  histograms.
+* NaN rule: the mean and spread FIELDS are NaN where any member is NaN; for the SCORES a column with a NaN y or any NaN member is
+  skipped and not counted.
+
+Two paths, as in model/verify.py: numpy arguments without `device=` run the numpy float64 code below; CUDA float32 tensors, or
+numpy arrays with device='cuda', are reduced by dlwp_ens_mean_spread / dlwp_ens_score_sums, and only (leads, groups, 6) float64
+sums and the int64 histogram come back.  The device path covers 2 <= M <= 256 and, for `axis`, forecast_error's rule: None (one
+value per lead) and the tuple that keeps the lead and the first field axis (one value per lead and variable); anything else runs
+the host code on downloaded arrays.
+"""
+import collections
+
+import numpy as np
+import torch
+
+from .verify import _common_device, _groups_run, _prod, _to_device, _to_host, _wants_device
+
+MAX_DEVICE_MEMBERS = 256
+
+#: rmse_mean, mae_mean, spread, spread_skill (= spread / rmse_mean), crps, fair_crps: float32 (T,) or (T, G); rank_hist: int64
+#: (T[, G], M + 1); count: int64, the columns counted; crps_field: the per-column crps (T, S, *field) or None
+EnsembleScores = collections.namedtuple('EnsembleScores', 'rmse_mean mae_mean spread spread_skill crps fair_crps rank_hist count crps_field')
+
+
+def _layout(forecast, member_axis):
+    """(T, S, M, field) of a forecast (T, S, M, *field) (member_axis=2) or (T, M, S, *field) (member_axis=1)"""
+    if member_axis not in (1, 2):
+        raise ValueError("'member_axis' must be 1 or 2, got %r" % (member_axis,))
+    shape = tuple(int(s) for s in forecast.shape)
+    if len(shape) < 4:
+        raise ValueError("'forecast' must be (T, S, M, *field) or (T, M, S, *field) with at least one field axis, got %r" % (shape,))
+    t, s, m = shape[0], shape[3 - member_axis], shape[member_axis]
+    if m < 2:
+        raise ValueError('an ensemble needs at least 2 members, got %d' % m)
+    if t < 1 or s < 1 or _prod(shape[3:]) < 1:
+        raise ValueError("'forecast' %r has an empty axis" % (shape,))
+    return t, s, m, shape[3:]
+
+
+def _check_ddof(ddof):
+    if ddof not in (0, 1):
+        raise ValueError("'ddof' must be 0 or 1, got %r" % (ddof,))
+
+
+def _device_of(named, device):
+    dev = _common_device([v.device for _, v in named if isinstance(v, torch.Tensor)], device)
+    if dev is None or dev.index is None:
+        dev = torch.device('cuda', torch.cuda.current_device())
+    return dev
+
+
+# -- the host path: numpy float64 on one lead at a time ----------------------------------------------------------------------------- #
+def _moments_host(x):
+    """x: float32 (S, M, *field) -> float64 (member-order sum, sum d, sum d^2), each (S, *field)"""
+    x0 = x[:, 0].astype(np.float64)
+    s = np.zeros(x0.shape, np.float64)
+    sd = np.zeros(x0.shape, np.float64)
+    sdd = np.zeros(x0.shape, np.float64)
+    with np.errstate(invalid='ignore', over='ignore'):
+        for i in range(x.shape[1]):
+            xi = x[:, i].astype(np.float64)
+            s += xi
+            d = xi - x0
+            sd += d
+            sdd += d * d
+    return s, sd, sdd
+
+
+def _members_second(forecast, t, member_axis):
+    x = forecast[t]
+    return x if member_axis == 2 else np.moveaxis(x, 0, 1)
+
+
+def _columns_host(x, y):
+    """One lead.  x: float32 (S, M, *field), y: float32 (S, *field) -> float64 (e, var_0, A, B), int64 rank, bool ok, each (S, *field)"""
+    m = x.shape[1]
+    s, sd, sdd = _moments_host(x)
+    with np.errstate(invalid='ignore', over='ignore'):
+        yd = y.astype(np.float64)
+        e = s / m - yd
+        var0 = (sdd - sd * sd / m) / m
+        a = np.zeros(yd.shape, np.float64)
+        rank = np.zeros(yd.shape, np.int64)
+        for i in range(m):
+            a += np.abs(x[:, i].astype(np.float64) - yd)
+            rank += x[:, i] < y
+        a /= m
+        xs = np.sort(x, axis=1)                                    # NaNs last; such a column is skipped
+        coef = (2.0 * np.arange(m) - m + 1.0).reshape((1, m) + (1,) * (x.ndim - 2))
+        b = np.zeros(yd.shape, np.float64)
+        for k in range(m):                                         # ascending order, as the device adds them
+            b += coef[:, k] * xs[:, k].astype(np.float64)
+    ok = ~(np.isnan(y) | np.isnan(x).any(axis=1))
+    return e, var0, a, b, rank, ok
+
+
+def _scores_host(forecast, valid, member_axis, axis, want_field):
+    """(sums (*keep, 6) float64, hist (*keep, M + 1) int64, crps field or None) over any `axis` of valid's axes that leaves the lead"""
+    t_n, s_n, m, field = _layout(forecast, member_axis)
+    ndim = valid.ndim
+    if axis is None:
+        red = tuple(range(1, ndim))
+    else:
+        red = tuple(sorted({int(a) + ndim if int(a) < 0 else int(a) for a in (axis if isinstance(axis, (tuple, list)) else (axis,))}))
+        if not red or red[0] < 1 or red[-1] >= ndim:
+            raise ValueError("'axis' %r must name axes 1 .. %d of 'valid' (the lead axis stays)" % (axis, ndim - 1))
+    keep = tuple(a for a in range(1, ndim) if a not in red)
+    keep_shape = tuple(valid.shape[a] for a in keep)
+    cells = _prod(keep_shape)
+    sums = np.zeros((t_n, cells, 6), np.float64)
+    hist = np.zeros((t_n, cells, m + 1), np.int64)
+    crps = np.full(valid.shape, np.nan, np.float32) if want_field else None
+    order = tuple(a - 1 for a in keep) + tuple(a - 1 for a in red)
+
+    def flat(v):
+        return np.transpose(v, order).reshape(cells, -1)
+    cell_of = np.arange(cells)[:, None]
+    for t in range(t_n):
+        e, var0, a, b, rank, ok = _columns_host(_members_second(forecast, t, member_axis), valid[t])
+        okf = flat(ok)
+        with np.errstate(invalid='ignore', over='ignore'):
+            for k, v in enumerate((e * e, np.abs(e), var0, a, b)):
+                sums[t, :, k] = np.where(okf, flat(v), 0.0).sum(axis=1)
+            if want_field:
+                crps[t] = np.where(ok, a - b / (float(m) * m), np.nan).astype(np.float32)
+        sums[t, :, 5] = okf.sum(axis=1)
+        index = (cell_of * (m + 1) + flat(rank))[okf]
+        hist[t] = np.bincount(index, minlength=cells * (m + 1)).reshape(cells, m + 1)
+    return sums.reshape((t_n,) + keep_shape + (6,)), hist.reshape((t_n,) + keep_shape + (m + 1,)), crps
+
+
+def finish(sums, hist, members, ddof, crps_field=None):
+    """(..., 6) float64 sums and the (..., M + 1) histogram -> EnsembleScores: divisions in float64, one cast to float32, NaN where
+    nothing was counted"""
+    sums = np.asarray(sums, dtype=np.float64)
+    m = float(members)
+    count = sums[..., 5]
+    with np.errstate(divide='ignore', invalid='ignore', over='ignore'):
+        n = np.where(count > 0, count, np.nan)
+        rmse = np.sqrt(sums[..., 0] / n)
+        mae = sums[..., 1] / n
+        var = m / (m - ddof) * (sums[..., 2] / n)
+        spread = np.sqrt(np.where(var < 0, 0.0, var))
+        crps = (sums[..., 3] - sums[..., 4] / (m * m)) / n
+        fair = (sums[..., 3] - sums[..., 4] / (m * (m - 1.0))) / n
+        vals = [v.astype(np.float32) for v in (rmse, mae, spread, spread / rmse, crps, fair)]
+    return EnsembleScores(*vals, rank_hist=np.asarray(hist, dtype=np.int64), count=count.astype(np.int64), crps_field=crps_field)
+
+
+# -- public ------------------------------------------------------------------------------------------------------------------------- #
+def ensemble_mean_spread(forecast, member_axis=2, ddof=1, device=None):
+    """Ensemble mean and spread fields.  forecast: (T, S, M, *field) with member_axis=2 or (T, M, S, *field) with member_axis=1 --
+    predict_timeseries returns (T, S * M, ...) or (T, M * S, ...), and viewing it in either form is free.  Returns (mean, spread) of
+    shape (T, S, *field), float32: CUDA tensors for a CUDA tensor, numpy arrays otherwise.  NaN where any member is NaN."""
+    t_n, s_n, m, field = _layout(forecast, member_axis)
+    _check_ddof(ddof)
+    named = (('forecast', forecast),)
+    if _wants_device(named, device):
+        from .. import ops
+        dev = _device_of(named, device)
+        row = _prod(field)
+        with torch.cuda.device(dev):
+            x = _to_device(forecast, dev)
+            mean, spread = ops.ens_mean_spread(x, ops.ens_strides(s_n, m, row, member_axis), t_n, s_n, m, row, ddof)
+            mean, spread = mean.view((t_n, s_n) + field), spread.view((t_n, s_n) + field)
+            if not isinstance(forecast, torch.Tensor):
+                mean, spread = mean.cpu().numpy(), spread.cpu().numpy()
+        return mean, spread
+    forecast = np.asarray(forecast, dtype=np.float32)
+    mean = np.empty((t_n, s_n) + field, np.float32)
+    spread = np.empty((t_n, s_n) + field, np.float32)
+    for t in range(t_n):
+        s, sd, sdd = _moments_host(_members_second(forecast, t, member_axis))
+        with np.errstate(invalid='ignore', over='ignore'):
+            var = (sdd - sd * sd / m) / (m - ddof)
+            mean[t] = (s / m).astype(np.float32)
+            spread[t] = np.sqrt(np.where(var < 0, 0.0, var)).astype(np.float32)
+    return mean, spread
+
+
+def ensemble_scores(forecast, valid, member_axis=2, axis=None, ddof=1, crps_field=False, device=None):
+    """Scores of an ensemble forecast against the per-lead verification `valid` (T, S, *field) -- what verify.verification_tensor
+    leaves in HBM.  `axis` names the axes of `valid` the means run over, by forecast_error's rule: None gives one value per lead, the
+    tuple that keeps the lead and the first field axis ((1, 3, 4) for a 5-D `valid`) one value per lead and variable; both run on
+    the device for device operands, any other axis on the host.  Returns an EnsembleScores (module docstring): `spread` is
+    sqrt(M / (M - ddof) * mean var_0), values are NaN where nothing was counted, and with crps_field=True the per-column crps comes
+    back too (a CUDA tensor where `forecast` is one), NaN in skipped columns."""
+    t_n, s_n, m, field = _layout(forecast, member_axis)
+    _check_ddof(ddof)
+    if tuple(int(s) for s in valid.shape) != (t_n, s_n) + field:
+        raise ValueError('ensemble_scores: shapes %r (forecast, member_axis=%d) and %r (valid) do not match; valid must be %r'
+                         % (tuple(forecast.shape), member_axis, tuple(valid.shape), (t_n, s_n) + field))
+    named = (('forecast', forecast), ('valid', valid))
+    if _wants_device(named, device):
+        gr = _groups_run(field, axis, 1) if m <= MAX_DEVICE_MEMBERS else None
+        if gr is not None:
+            from .. import ops
+            dev = _device_of(named, device)
+            with torch.cuda.device(dev):
+                x, y = _to_device(forecast, dev), _to_device(valid, dev)
+                out = ops.ens_score_sums(x, ops.ens_strides(s_n, m, gr[0] * gr[1], member_axis), y, t_n, s_n, m, gr[0], gr[1],
+                                         crps_field=crps_field)
+                sums, hist = out[0].cpu().numpy(), out[1].cpu().numpy()
+                field_out = None
+                if crps_field:
+                    field_out = out[2].view((t_n, s_n) + field)
+                    if not isinstance(forecast, torch.Tensor):
+                        field_out = field_out.cpu().numpy()
+            if axis is None:
+                sums, hist = sums[:, 0], hist[:, 0]
+            return finish(sums, hist, m, ddof, field_out)
+        forecast, valid = _to_host(forecast), _to_host(valid)
+    forecast, valid = np.asarray(forecast, dtype=np.float32), np.asarray(valid, dtype=np.float32)
+    sums, hist, field_out = _scores_host(forecast, valid, member_axis, axis, crps_field)
+    return finish(sums, hist, m, ddof, field_out)

@@ -1900,6 +1900,93 @@ def gather_rows_fill(src, rows, out=None):
     return out
 
 
+# -- ensemble verification (csrc/ensemble.hip) --------------------------------------------------------------------------------------- #
+ENS_MAX_MEMBERS = 256
+
+
+def ens_strides(samples, members, row, member_axis=2):
+    """(lead_stride, sample_stride, member_stride) in elements of a contiguous series viewed as (T, S, M, row) (member_axis=2) or
+    (T, M, S, row) (member_axis=1): the table of include/dlwp_hip.h"""
+    samples, members, row = int(samples), int(members), int(row)
+    if member_axis == 2:
+        return samples * members * row, members * row, row
+    if member_axis == 1:
+        return members * samples * row, row, samples * row
+    raise ValueError("'member_axis' must be 1 or 2, got %r" % (member_axis,))
+
+
+def ens_extent(strides, leads, samples, members, row):
+    """Elements the ensemble operand must hold: one past the last offset the strides address"""
+    ls, ss, ms = (int(v) for v in strides)
+    return (int(leads) - 1) * ls + (int(samples) - 1) * ss + (int(members) - 1) * ms + int(row)
+
+
+def _ens_check(who, x, strides, leads, samples, members, row):
+    if leads < 1 or samples < 1 or row < 1 or min(strides) < 0:
+        raise ValueError('%s: leads, samples and the row must be >= 1 and the strides >= 0' % who)
+    need = ens_extent(strides, leads, samples, members, row)
+    if need > x.numel():
+        raise ValueError('%s: the ensemble holds %d elements, the strides address %d' % (who, x.numel(), need))
+
+
+def ens_mean_spread(x, strides, leads, samples, members, row, ddof=1, want_mean=True, want_spread=True):
+    """include/dlwp_hip.h: dlwp_ens_mean_spread.  x: contiguous float32 device tensor read as a flat array through strides =
+    (lead_stride, sample_stride, member_stride) in elements.  Returns NEW float32 tensors (mean, spread) of shape (leads, samples,
+    row) (None for the one not wanted), enqueued on the current stream."""
+    _check_f32(x)
+    d = _dev(x)
+    leads, samples, members, row, ddof = int(leads), int(samples), int(members), int(row), int(ddof)
+    if members < 2:
+        raise ValueError('ens_mean_spread: %d members, at least 2' % members)
+    if ddof not in (0, 1):
+        raise ValueError('ens_mean_spread: ddof must be 0 or 1, got %d' % ddof)
+    if not (want_mean or want_spread):
+        raise ValueError('ens_mean_spread: neither the mean nor the spread is wanted')
+    _ens_check('ens_mean_spread', x, strides, leads, samples, members, row)
+    mean = torch.empty((leads, samples, row), dtype=torch.float32, device=x.device) if want_mean else None
+    spread = torch.empty((leads, samples, row), dtype=torch.float32, device=x.device) if want_spread else None
+    _lib.check(_lib.lib.dlwp_ens_mean_spread(_lib.handle(d), _ptr(x), leads, samples, members, int(strides[0]), int(strides[1]),
+                                             int(strides[2]), row, ddof, _ptr(mean), _ptr(spread), _stream(x)))
+    return mean, spread
+
+
+def ens_score_workspace(device_index, leads, groups, members):
+    """bytes of workspace dlwp_ens_score_sums needs on that device (any sample count)"""
+    return int(_lib.lib.dlwp_ens_score_workspace(_lib.handle(int(device_index)), int(leads), int(groups), int(members)))
+
+
+def ens_score_sums(x, strides, y, leads, samples, members, groups, run, crps_field=False, ws=None):
+    """include/dlwp_hip.h: dlwp_ens_score_sums.  x: the ensemble as in ens_mean_spread; y: contiguous float32 device tensor of
+    leads * samples * groups * run elements.  Returns NEW device tensors (sums (leads, groups, 6) float64, hist (leads, groups,
+    members + 1) int64) and, with crps_field, the per-column crps (leads, samples, groups * run) float32 as a third."""
+    _check_f32(x, y)
+    d = _dev(x)
+    if _dev(y) != d:
+        raise ValueError('ens_score_sums: operands on devices %d and %d' % (d, _dev(y)))
+    leads, samples, members, groups, run = int(leads), int(samples), int(members), int(groups), int(run)
+    if not 2 <= members <= ENS_MAX_MEMBERS:
+        raise ValueError('ens_score_sums: %d members, expected 2 .. %d' % (members, ENS_MAX_MEMBERS))
+    if groups < 1 or run < 1:
+        raise ValueError('ens_score_sums: groups and run must be >= 1')
+    _ens_check('ens_score_sums', x, strides, leads, samples, members, groups * run)
+    if y.numel() != leads * samples * groups * run:
+        raise ValueError('ens_score_sums: the verification holds %d elements, expected %d' % (y.numel(), leads * samples * groups * run))
+    h = _lib.handle(d)
+    need = max(int(_lib.lib.dlwp_ens_score_workspace(h, leads, groups, members)), 8)
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+    elif ws.numel() * ws.element_size() < need or ws.device != x.device:
+        raise ValueError('ens_score_sums: the workspace holds %d bytes on %s, expected %d on %s' % (ws.numel() * ws.element_size(),
+                                                                                                  ws.device, need, x.device))
+    sums = torch.empty((leads, groups, 6), dtype=torch.float64, device=x.device)
+    hist = torch.empty((leads, groups, members + 1), dtype=torch.int64, device=x.device)
+    crps = torch.empty((leads, samples, groups * run), dtype=torch.float32, device=x.device) if crps_field else None
+    _lib.check(_lib.lib.dlwp_ens_score_sums(h, _ptr(x), int(strides[0]), int(strides[1]), int(strides[2]), _ptr(y), leads, samples,
+                                            members, groups, run, _ptr(sums), _ptr(hist), _ptr(crps), _ptr(ws),
+                                            ws.numel() * ws.element_size(), _stream(x)))
+    return (sums, hist, crps) if crps_field else (sums, hist)
+
+
 # -- batches of a series generator out of an HBM-resident series (csrc/series.hip) --------------------------------------------------- #
 SERIES_CHUNK_UNITS = 1024          # units (16 bytes, or one float on the scalar path) a block moves per turn
 

@@ -1179,6 +1179,45 @@ int dlwp_series_gather_grid_cap(dlwp_handle_t);
 int dlwp_series_window_gather(dlwp_handle_t, const dlwp_series_src* srcs, int n_src, const dlwp_series_dst* dsts, int n_dst,
                               const dlwp_series_seg* segs, int n_seg, const void* samples, long long n, void* stream);
 
+/* ---- ensemble verification on the device (csrc/ensemble.hip; the reference averages members on the host,
+ *      examples/plot_ensemble.py:242,269): reductions ACROSS the member axis of the series predict_timeseries(...,
+ *      return_device=True) leaves in HBM.  A column is one (lead t, sample s, point p) with `members` float32 values
+ *        x[t * lead_stride + s * sample_stride + i * member_stride + p],  i < members, p < row,
+ *      all strides in ELEMENTS and >= 0; consecutive points are contiguous.  The two layouts of a contiguous series of row floats:
+ *
+ *        series viewed as        lead_stride   sample_stride   member_stride
+ *        (T, S, M, row)          S * M * row   M * row         row
+ *        (T, M, S, row)          M * S * row   row             S * row
+ *
+ *      All per-column arithmetic is float64 on the float32 values: mean = (sum_i x_i) / M in member order; with d_i = x_i - x_0
+ *      (exact), var_ddof = (sum d_i^2 - (sum d_i)^2 / M) / (M - ddof) and spread = sqrt(max(var, 0)).
+ *      dlwp_ens_mean_spread: mean, spread (leads, samples, row) float32, either may be NULL (not both); NaN where a member is NaN.
+ *      One pass over the members, a thread owns four adjacent columns (16-byte accesses: row and the three strides multiples of 4,
+ *      all bases 16-byte aligned) or one.  2 <= members, ddof 0 or 1.
+ *      dlwp_ens_score_sums: y is the contiguous verification (leads, samples, groups * run) float32 and row = groups * run.  Per
+ *      (lead, group) cell, over the columns where neither y nor a member is NaN:
+ *        sums[cell][0..5] = sum (mean - y)^2, sum |mean - y|, sum var_0, sum A, sum B, columns counted      (float64)
+ *        hist[cell][r]    = columns with r = #{i : x_i < y}, r = 0 .. members (ties count as not below)       (int64)
+ *      with A = (1/M) sum_i |x_i - y| and B = sum_{i<j} |x_i - x_j| = sum_k (2k - M + 1) x_(k) over the ascending order, so that
+ *      crps = A - B / M^2 and fair_crps = A - B / (M (M - 1)).  crps_out, if not NULL, is (leads, samples, groups * run) float32 and
+ *      receives every column's crps, NaN for a skipped column.  2 <= members <= 256, any integer.  A wave owns 64 adjacent points;
+ *      a lane keeps 32 members of its column in registers, sorts them with an unrolled bitonic network on order-preserving integer
+ *      keys and, above 32 members, parks the sorted runs in LDS ([member][point], a lane only ever touches its own column: no bank
+ *      conflicts, no barriers) and merges up to 8 runs head by head while it accumulates B.  Sums are two-stage on a fixed tree
+ *      (lanes, one partial per block in ws, a second launch adds a cell's partials in index order); the histogram uses integer LDS
+ *      atomics inside a block and the same second launch: no global atomics, repeated calls give identical bits.
+ *      dlwp_ens_score_workspace returns the bytes of ws for any sample count (a NULL handle counts 256 CUs), 0 for sizes outside the
+ *      ranges above.  ws must be 8-byte aligned.  Refused without a launch: sizes out of range, negative strides, null pointers, more
+ *      than 2^20 cells, a workspace too small or misaligned, a null handle (in that order).  The caller guarantees that every
+ *      addressed element exists (dlwp_amd.ops checks it).  None is part of a training step: all mark a recording tape foreign.   */
+int dlwp_ens_mean_spread(dlwp_handle_t, const void* x, int leads, int samples, int members, long long lead_stride,
+                         long long sample_stride, long long member_stride, long long row, int ddof, void* mean, void* spread,
+                         void* stream);
+size_t dlwp_ens_score_workspace(dlwp_handle_t, int leads, int groups, int members);
+int dlwp_ens_score_sums(dlwp_handle_t, const void* x, long long lead_stride, long long sample_stride, long long member_stride,
+                        const void* y, int leads, int samples, int members, int groups, long long run, void* sums, void* hist,
+                        void* crps_out, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
