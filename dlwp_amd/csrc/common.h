@@ -166,6 +166,13 @@ __device__ static inline int dlwp_map_coord_tile(int p, int n, int mode) {
   return p < 0 ? max(p + n, 0) : min(p - n, n - 1);   // DLWP_PAD_WRAP
 }
 
+// The forward ReLU and every forward max-pool (standalone, pooled loader, pooled epilogue): a maximum that PROPAGATES NaN, as
+// np.maximum / np.max of the oracle do -- fmaxf returns the other operand, so a NaN sample would come out finite.  llvm.maximum:
+// one v_maximum3_f32 on gfx950, nothing to canonicalise.  Of +0 and -0 it returns +0 (fmaxf: either).  The backward kernels
+// (pooled-source weight-gradient loaders, dlwp_maxpool2_bwd) keep fmaxf: training on NaN has no defined result in the reference.
+__device__ __forceinline__ float dlwp_nmax(float a, float b) { return __builtin_elementwise_maximum(a, b); }
+__device__ __forceinline__ float dlwp_nmax4(float a, float b, float c, float d) { return dlwp_nmax(dlwp_nmax(a, b), dlwp_nmax(c, d)); }
+
 // internal launchers shared between the public entry points and the rollout graph builder
 // u_pre: weights already prepared by dlwp_conv2d_prep for this (w, xs, cd) -- the rollout graph transforms once per
 // launch instead of once per forward; NULL = transform into the handle's scratch right before the multiply

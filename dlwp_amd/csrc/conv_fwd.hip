@@ -467,7 +467,7 @@ __global__ __launch_bounds__(256) void conv2d_fwd_direct_f32(const ConvArgs a, i
           if (a.src_mode == DLWP_SRC_UPSAMPLE2) xv = at((long long)(rs >> 1) * a.Ws + (cs >> 1));
           else if (a.src_mode == DLWP_SRC_MAXPOOL2) {
             const long long o = (long long)(rs * 2) * a.Ws + cs * 2;
-            xv = fmaxf(fmaxf(at(o), at(o + 1)), fmaxf(at(o + a.Ws), at(o + a.Ws + 1)));
+            xv = dlwp_nmax4(at(o), at(o + 1), at(o + a.Ws), at(o + a.Ws + 1));
           } else xv = at((long long)rs * a.Ws + cs);
           acc = fmaf(xv, wp[(long long)ci * a.Cout], acc);
         }

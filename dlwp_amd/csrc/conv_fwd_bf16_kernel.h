@@ -588,9 +588,9 @@ __global__ __launch_bounds__(C::NT, 2) void conv2d_fwd_mfma_bf16(const ConvArgs 
                 f32x4 m;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                  const float v = fmaxf(acc[i][t][r], acc[i + C::FA / 2][t][r]);
+                  const float v = dlwp_nmax(acc[i][t][r], acc[i + C::FA / 2][t][r]);
                   const float w = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
-                  m[r] = fmaxf(v, w);
+                  m[r] = dlwp_nmax(v, w);
                 }
                 const f32x2 lo = act_apply2_c<ACT>(m.xy + bias4[t].xy), hi = act_apply2_c<ACT>(m.zw + bias4[t].zw);
                 __builtin_amdgcn_raw_buffer_store_b64((u32x2){pack_bf16x2(lo.x, lo.y), pack_bf16x2(hi.x, hi.y)}, y_rsrc,
@@ -721,8 +721,8 @@ __global__ __launch_bounds__(C::NT, 2) void conv2d_fwd_mfma_bf16(const ConvArgs 
 #pragma unroll
           for (int g = 0; g < C::BNF; ++g) {
             const f32x4 u = acc[i][g], d = acc[i + C::FA / 2][g];
-            const f32x2 o01 = act_apply2_c<ACT>((f32x2){fmaxf(fmaxf(u[0], u[1]), fmaxf(d[0], d[1])),
-                                                         fmaxf(fmaxf(u[2], u[3]), fmaxf(d[2], d[3]))} + (f32x2){bias_v[g], bias_v[g]});
+            const f32x2 o01 = act_apply2_c<ACT>((f32x2){dlwp_nmax4(u[0], u[1], d[0], d[1]),
+                                                         dlwp_nmax4(u[2], u[3], d[2], d[3])} + (f32x2){bias_v[g], bias_v[g]});
             const float o0 = o01.x, o1 = o01.y;
             const unsigned e = coff[g] + poff;
             const unsigned off0 = (ok0 && coff[g] != DROP) ? e * esz : DROP;

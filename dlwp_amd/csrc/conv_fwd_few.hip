@@ -314,7 +314,7 @@ __global__ __launch_bounds__(256, (OUT == 0 && CG == 1) ? 4 : 3) void conv2d_fwd
           for (int i = 0; i < 2; ++i) {
             const f32x4 u = acc[i][g], d = acc[i + 2][g];
             o[i] = act_apply2_c<((DLWP_KNOCK_FEW & 2) ? 0 : ACT)>(
-                (f32x2){fmaxf(fmaxf(u[0], u[1]), fmaxf(d[0], d[1])), fmaxf(fmaxf(u[2], u[3]), fmaxf(d[2], d[3]))} + (f32x2){bv[g], bv[g]});
+                (f32x2){dlwp_nmax4(u[0], u[1], d[0], d[1]), dlwp_nmax4(u[2], u[3], d[2], d[3])} + (f32x2){bv[g], bv[g]});
           }
           if ((DLWP_KNOCK_FEW & 4) && o[0].x != 12345.678f) continue;
           if (wide) {

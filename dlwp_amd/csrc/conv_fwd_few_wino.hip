@@ -287,8 +287,8 @@ __global__ __launch_bounds__(256, QUAD ? 3 : 2) void conv2d_fwd_few_wino_f32(con
         f32x2 o[2];                // pooled row aa: columns 0, 1 of the tile's 2 x 2 block
 #pragma unroll
         for (int aa = 0; aa < 2; ++aa) {
-          const f32x2 mx = (f32x2){fmaxf(fmaxf(y[0][aa][0].x, y[0][aa][0].y), fmaxf(y[1][aa][0].x, y[1][aa][0].y)),
-                                   fmaxf(fmaxf(y[0][aa][1].x, y[0][aa][1].y), fmaxf(y[1][aa][1].x, y[1][aa][1].y))};
+          const f32x2 mx = (f32x2){dlwp_nmax(dlwp_nmax(y[0][aa][0].x, y[0][aa][0].y), dlwp_nmax(y[1][aa][0].x, y[1][aa][0].y)),
+                                   dlwp_nmax(dlwp_nmax(y[0][aa][1].x, y[0][aa][1].y), dlwp_nmax(y[1][aa][1].x, y[1][aa][1].y))};
           o[aa] = act_apply2_c<ACT>(mx + (f32x2){bv[g], bv[g]});
         }
         __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, o[0]), y_rsrc, voff[g], 0, 0);

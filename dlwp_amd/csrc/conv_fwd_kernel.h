@@ -150,7 +150,7 @@ __device__ __forceinline__ float dlwp_tanh_rational(float x) {
 template <int ACT>
 __device__ __forceinline__ float act_apply_c(float v) {
   if constexpr (ACT == DLWP_ACT_TANH) return dlwp_tanh(v);
-  else if constexpr (ACT == DLWP_ACT_RELU) return fmaxf(v, 0.f);
+  else if constexpr (ACT == DLWP_ACT_RELU) return dlwp_nmax(v, 0.f);
   else return v;
 }
 
@@ -195,7 +195,7 @@ __device__ __forceinline__ f32x2 act_apply2_c(f32x2 v) {
     const f32x2 r = (f32x2){__builtin_amdgcn_rcpf(e.x), __builtin_amdgcn_rcpf(e.y)};
     return __builtin_elementwise_fma(r, (f32x2){2.f, 2.f}, (f32x2){-1.f, -1.f});
   } else if constexpr (ACT == DLWP_ACT_RELU) {
-    return (f32x2){fmaxf(v.x, 0.f), fmaxf(v.y, 0.f)};
+    return (f32x2){dlwp_nmax(v.x, 0.f), dlwp_nmax(v.y, 0.f)};
   } else {
     return v;
   }
@@ -210,7 +210,7 @@ __device__ __forceinline__ void act_dispatch(int act, F&& f) {
 
 __device__ __forceinline__ float act_apply(float v, int act) {
   if (act == DLWP_ACT_TANH) return dlwp_tanh(v);
-  if (act == DLWP_ACT_RELU) return fmaxf(v, 0.f);
+  if (act == DLWP_ACT_RELU) return dlwp_nmax(v, 0.f);
   return v;
 }
 
@@ -401,7 +401,7 @@ __global__ __launch_bounds__(C::NT, 2) void conv2d_fwd_mfma_f32(const ConvArgs a
         const bool c_ok = c0 + ci < a.Cin;
 #pragma unroll
         for (int q = 0; q < C::NPOS; ++q) {
-          float v = fmaxf(fmaxf(pv[ci][q][0][0], pv[ci][q][0][1]), fmaxf(pv[ci][q][1][0], pv[ci][q][1][1]));
+          float v = dlwp_nmax4(pv[ci][q][0][0], pv[ci][q][0][1], pv[ci][q][1][0], pv[ci][q][1][1]);
           v = (c_ok && gok[q]) ? v : 0.f;
           xs[((q == C::NPOS - 1 && loff[q] == C::TRASH) ? 0 : ci * C::PS) + loff[q]] = v;
         }
@@ -500,7 +500,7 @@ __global__ __launch_bounds__(C::NT, 2) void conv2d_fwd_mfma_f32(const ConvArgs a
               const int pc = (j0 >> 1) + i * 8 + (lane >> 4) * 2;
               const f32x4 u = acc[i][g], d = acc[i + C::FA / 2][g];
               const f32x2 o01 = act_apply2_c<(DLWP_KNOCK_F32 == 4 ? 0 : ACT)>(
-                  (f32x2){fmaxf(fmaxf(u[0], u[1]), fmaxf(d[0], d[1])), fmaxf(fmaxf(u[2], u[3]), fmaxf(d[2], d[3]))} + (f32x2){bv, bv});
+                  (f32x2){dlwp_nmax4(u[0], u[1], d[0], d[1]), dlwp_nmax4(u[2], u[3], d[2], d[3])} + (f32x2){bv, bv});
               const float o0 = o01.x, o1 = o01.y;
               if (DLWP_KNOCK_F32 == 1 && o0 != 12345.678f) continue;
               if (a.out_bf16) {

@@ -323,7 +323,7 @@ __global__ __launch_bounds__(C::NT, C::WAVES_PER_SIMD) void conv2d_fwd_wino2_f32
             }
             if constexpr (C::DIL == 1) {
               if (a.out_pool) {  // MaxPooling2D(2): the 2x2 tile IS one pooling window; activation after the maximum
-                const float mx = fmaxf(fmaxf(y[0][0], y[0][1]), fmaxf(y[1][0], y[1][1]));
+                const float mx = dlwp_nmax(dlwp_nmax(y[0][0], y[0][1]), dlwp_nmax(y[1][0], y[1][1]));
                 lds[C::O_FLOATS + col * ((C::TH / 2) * (C::TW / 2)) + ti * (C::TW / 2) + tj] = act_apply_c<ACT>(mx + bv);
                 continue;
               }
@@ -388,7 +388,7 @@ __global__ __launch_bounds__(C::NT, C::WAVES_PER_SIMD) void conv2d_fwd_wino2_f32
               }
               if constexpr (C::DIL == 1) {
                 if (a.out_pool) {  // MaxPooling2D(2): the 2x2 tile IS one pooling window; activation after the maximum
-                  const float mx = fmaxf(fmaxf(y[0][0], y[0][1]), fmaxf(y[1][0], y[1][1]));
+                  const float mx = dlwp_nmax(dlwp_nmax(y[0][0], y[0][1]), dlwp_nmax(y[1][0], y[1][1]));
                   lds[C::O_FLOATS + col * ((C::TH / 2) * (C::TW / 2)) + ti * (C::TW / 2) + tj] = act_apply_c<ACT>(mx + bv);
                   continue;
                 }
@@ -428,8 +428,8 @@ __global__ __launch_bounds__(C::NT, C::WAVES_PER_SIMD) void conv2d_fwd_wino2_f32
         const float* p0 = lds + co * C::OPS + (2 * row) * C::TW + 2 * colx;
         const f32x4 a0 = *(const f32x4*)p0, a1 = *(const f32x4*)(p0 + 4);
         const f32x4 b0 = *(const f32x4*)(p0 + C::TW), b1 = *(const f32x4*)(p0 + C::TW + 4);
-        o = (f32x4){fmaxf(fmaxf(a0[0], a0[1]), fmaxf(b0[0], b0[1])), fmaxf(fmaxf(a0[2], a0[3]), fmaxf(b0[2], b0[3])),
-                    fmaxf(fmaxf(a1[0], a1[1]), fmaxf(b1[0], b1[1])), fmaxf(fmaxf(a1[2], a1[3]), fmaxf(b1[2], b1[3]))};
+        o = (f32x4){dlwp_nmax(dlwp_nmax(a0[0], a0[1]), dlwp_nmax(b0[0], b0[1])), dlwp_nmax(dlwp_nmax(a0[2], a0[3]), dlwp_nmax(b0[2], b0[3])),
+                    dlwp_nmax(dlwp_nmax(a1[0], a1[1]), dlwp_nmax(b1[0], b1[1])), dlwp_nmax(dlwp_nmax(a1[2], a1[3]), dlwp_nmax(b1[2], b1[3]))};
       }
       const long long yoff = ybase + ((long long)co * a.Hp + oh) * a.Wp + ow;
       if (a.out_bf16) {

@@ -678,8 +678,8 @@ __device__ __forceinline__ void conv2d_fwd_wino_body(const ConvArgs& a, const in
       if (pool_stage) {  // MaxPooling2D(2): a lane's 2x2 output tile IS one pooling window; activation after the max
         for_tiles([&](const f32x2 (&s)[2][4], int col, f32x2 bv, int ti, int tj, int, int) {
           const f32x2 y00 = y_even(s, 0), y01 = y_odd(s, 0), y10 = y_even(s, 1), y11 = y_odd(s, 1);
-          const f32x2 mx = (f32x2){fmaxf(fmaxf(y00.x, y01.x), fmaxf(y10.x, y11.x)),
-                                   fmaxf(fmaxf(y00.y, y01.y), fmaxf(y10.y, y11.y))};
+          const f32x2 mx = (f32x2){dlwp_nmax(dlwp_nmax(y00.x, y01.x), dlwp_nmax(y10.x, y11.x)),
+                                   dlwp_nmax(dlwp_nmax(y00.y, y01.y), dlwp_nmax(y10.y, y11.y))};
           *(f32x2*)(lds + col * C::OPS + ti * (C::TW / 2) + tj) = act_apply2_c<ACT>(mx + bv);
         });
         return;
@@ -695,8 +695,8 @@ __device__ __forceinline__ void conv2d_fwd_wino_body(const ConvArgs& a, const in
         const f32x2 y0 = act_apply2_c<ACT>(y_even(s, aa) + bv);
         const f32x2 y1 = act_apply2_c<ACT>(y_odd(s, aa) + bv);
         if constexpr (C::POOL2) {   // the maximum of the ACTIVATED window = the activated maximum (monotonic activations)
-          const f32x2 m = (f32x2){fmaxf(y0.x, y1.x), fmaxf(y0.y, y1.y)};
-          pmax = aa == 0 ? m : (f32x2){fmaxf(pmax.x, m.x), fmaxf(pmax.y, m.y)};
+          const f32x2 m = (f32x2){dlwp_nmax(y0.x, y1.x), dlwp_nmax(y0.y, y1.y)};
+          pmax = aa == 0 ? m : (f32x2){dlwp_nmax(pmax.x, m.x), dlwp_nmax(pmax.y, m.y)};
         }
         float* q = op + aa * (C::FLAT ? 2 * C::T : C::DIL * C::TW);
         if constexpr (C::DIL == 1) {
@@ -885,8 +885,8 @@ __device__ __forceinline__ void conv2d_fwd_wino_body(const ConvArgs& a, const in
           const float* p0 = lds + co * C::OPS + (2 * row) * C::TW + 2 * colx;
           const f32x4 a0 = *(const f32x4*)p0, a1 = *(const f32x4*)(p0 + 4);
           const f32x4 b0 = *(const f32x4*)(p0 + C::TW), b1 = *(const f32x4*)(p0 + C::TW + 4);
-          o = (f32x4){fmaxf(fmaxf(a0[0], a0[1]), fmaxf(b0[0], b0[1])), fmaxf(fmaxf(a0[2], a0[3]), fmaxf(b0[2], b0[3])),
-                      fmaxf(fmaxf(a1[0], a1[1]), fmaxf(b1[0], b1[1])), fmaxf(fmaxf(a1[2], a1[3]), fmaxf(b1[2], b1[3]))};
+          o = (f32x4){dlwp_nmax(dlwp_nmax(a0[0], a0[1]), dlwp_nmax(b0[0], b0[1])), dlwp_nmax(dlwp_nmax(a0[2], a0[3]), dlwp_nmax(b0[2], b0[3])),
+                      dlwp_nmax(dlwp_nmax(a1[0], a1[1]), dlwp_nmax(b1[0], b1[1])), dlwp_nmax(dlwp_nmax(a1[2], a1[3]), dlwp_nmax(b1[2], b1[3]))};
         }
         const long long yoff = ybase + ((long long)co * a.Hp + oh) * a.Wp + ow;
         if (a.out_bf16) {
@@ -1009,16 +1009,26 @@ __device__ __forceinline__ void conv2d_fwd_wino_body(const ConvArgs& a, const in
       const unsigned ppix = (unsigned)(ph * a.Wp + pw) * 4u + (unsigned)cb2 * pplane_b;
       const bool prok = ph < a.Hp;
       const float* lp2 = lds + C::O_FLOATS + cb2 * C::PPS + rem2;
+      // As the output's stores above: whole quads by every lane (a dropped address where the quad is cut), then -- uniform -- the
+      // elements of the quad the pooled map's right edge cuts.  (The per-lane choice between one 16-byte and four 4-byte stores
+      // that stood here stored element 0 in every valid slot of a cut quad: pooled widths of 2 or 3 (mod 4) came out with their
+      // last columns repeated; tests/test_gpu_conv_fwd.py, the two-output launch on 12 x 45.)
+      const unsigned pvoff_q = (prok && pw + 3 < a.Wp) ? ppix : DROP;
 #pragma unroll
-      for (int k = 0; k < NP2; ++k) {
-        const f32x4 o = *(const f32x4*)(lp2 + k * CS2 * C::PPS);
-        if (pw + 3 < a.Wp) {
-          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), p_rsrc, prok ? ppix : DROP, (unsigned)(k * CS2) * pplane_b, 0);
-        } else {
+      for (int k = 0; k < NP2; ++k)
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, *(const f32x4*)(lp2 + k * CS2 * C::PPS)), p_rsrc, pvoff_q,
+                                               (unsigned)(k * CS2) * pplane_b, 0);
+      if (a.Wp & 3) {
+        const bool pedge = prok && pw < a.Wp && pw + 3 >= a.Wp;
 #pragma unroll
-          for (int r = 0; r < 4; ++r)
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, o[r]), p_rsrc,
-                                                  (prok && pw + r < a.Wp) ? ppix + 4u * r : DROP, (unsigned)(k * CS2) * pplane_b, 0);
+        for (int k = 0; k < NP2; ++k) {
+          const f32x4 o = *(const f32x4*)(lp2 + k * CS2 * C::PPS);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float v = o[r];
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), p_rsrc,
+                                                  (pedge && pw + r < a.Wp) ? ppix + 4u * r : DROP, (unsigned)(k * CS2) * pplane_b, 0);
+          }
         }
       }
     }

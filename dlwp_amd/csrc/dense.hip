@@ -31,7 +31,7 @@ constexpr int DN_RC = DN_WAVES * DN_RW;  // reduction elements staged per chunk 
 constexpr int DN_PITCH = DN_RC + 1;      // LDS row pitch of the staged operand (odd: the 32 rows of a read hit 32 banks)
 
 __device__ inline float dn_act(float v, int act) {
-  return act == DLWP_ACT_TANH ? tanhf(v) : (act == DLWP_ACT_RELU ? fmaxf(v, 0.f) : v);
+  return act == DLWP_ACT_TANH ? tanhf(v) : (act == DLWP_ACT_RELU ? dlwp_nmax(v, 0.f) : v);
 }
 __device__ inline float dn_act_grad(float y, int act) {
   return act == DLWP_ACT_TANH ? 1.f - y * y : (act == DLWP_ACT_RELU ? (y > 0.f ? 1.f : 0.f) : 1.f);

@@ -506,7 +506,7 @@ __global__ __launch_bounds__(256) void maxpool2_fwd_kernel(const float* __restri
     const int r = (int)(q % H2);
     const long long p = q / H2;
     const float* s = x + (p * H + 2 * r) * W + 2 * j;
-    y[i] = fmaxf(fmaxf(s[0], s[1]), fmaxf(s[W], s[W + 1]));
+    y[i] = dlwp_nmax4(s[0], s[1], s[W], s[W + 1]);
   }
 }
 
@@ -532,8 +532,8 @@ __global__ __launch_bounds__(256) void maxpool2_fwd_bf16_kernel(const unsigned s
       a = (unsigned)s[0] | ((unsigned)s[1] << 16);
       b = (unsigned)s[W] | ((unsigned)s[W + 1] << 16);
     }
-    const float m = fmaxf(fmaxf(__builtin_bit_cast(float, a << 16), __builtin_bit_cast(float, a & 0xffff0000u)),
-                          fmaxf(__builtin_bit_cast(float, b << 16), __builtin_bit_cast(float, b & 0xffff0000u)));
+    const float m = dlwp_nmax4(__builtin_bit_cast(float, a << 16), __builtin_bit_cast(float, a & 0xffff0000u),
+                               __builtin_bit_cast(float, b << 16), __builtin_bit_cast(float, b & 0xffff0000u));
     y[i] = (unsigned short)(__builtin_bit_cast(unsigned, m) >> 16);
   }
 }

@@ -42,7 +42,7 @@ constexpr int PW_UNITS = 16;               // 32-pixel units per first-stage par
 constexpr int PW_PITCH = 33;
 
 __device__ __forceinline__ float sep_act(float v, int act) {
-  return act == DLWP_ACT_TANH ? tanhf(v) : (act == DLWP_ACT_RELU ? fmaxf(v, 0.f) : v);
+  return act == DLWP_ACT_TANH ? tanhf(v) : (act == DLWP_ACT_RELU ? dlwp_nmax(v, 0.f) : v);
 }
 
 // dlwp_map_coord on the range a validated halo reaches (one period / one reflection): no division
