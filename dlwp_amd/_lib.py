@@ -120,6 +120,19 @@ class Dense(ctypes.Structure):
     _fields_ = [('m', ctypes.c_int), ('k', ctypes.c_int), ('n', ctypes.c_int), ('act', ctypes.c_int)]
 
 
+ENS_MAX_RADIUS = 16
+
+
+class EnsPerturb(ctypes.Structure):
+    """dlwp_ens_perturb_desc (include/dlwp_hip.h): shape, members, seed, both radii with their tap tables, flags, output strides"""
+    _fields_ = [('samples', ctypes.c_int), ('channels', ctypes.c_int), ('height', ctypes.c_int), ('width', ctypes.c_int),
+                ('members', ctypes.c_int), ('first_member', ctypes.c_int), ('seed', ctypes.c_ulonglong),
+                ('radius_y', ctypes.c_int), ('radius_x', ctypes.c_int),
+                ('taps_y', ctypes.c_float * (2 * ENS_MAX_RADIUS + 1)), ('taps_x', ctypes.c_float * (2 * ENS_MAX_RADIUS + 1)),
+                ('control', ctypes.c_int), ('antithetic', ctypes.c_int),
+                ('sample_stride', ctypes.c_longlong), ('member_stride', ctypes.c_longlong)]
+
+
 class Dropout(ctypes.Structure):
     """dlwp_dropout (include/dlwp_hip.h): what names one mask -- seed, layer, step -- and how it is applied"""
     _fields_ = [('seed', ctypes.c_ulonglong), ('layer', ctypes.c_uint), ('step', ctypes.c_uint), ('threshold', ctypes.c_uint),
@@ -368,6 +381,7 @@ _sig('dlwp_ens_mean_spread', [_vp, _vp, _i, _i, _i, ctypes.c_longlong, ctypes.c_
 _sig('dlwp_ens_score_workspace', [_vp, _i, _i, _i], _sz)
 _sig('dlwp_ens_score_sums', [_vp, _vp, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, _vp, _i, _i, _i, _i,
                              ctypes.c_longlong, _vp, _vp, _vp, _vp, _sz, _vp])
+_sig('dlwp_ens_perturb', [_vp, _vp, _vp, _vp, EnsPerturb, _vp])
 
 
 # csrc/series.hip: the descriptor tables of dlwp_series_window_gather (include/dlwp_hip.h)

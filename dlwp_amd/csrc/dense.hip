@@ -16,6 +16,7 @@
 // to 32 MT rows; the left operand is staged through LDS in chunks of 128 reduction elements, of which each wave multiplies 16; the
 // eight partial tiles are summed through LDS in wave order.  The split over the waves is the same for every shape.
 #include "common.h"
+#include "philox.h"
 #include "tape.h"
 
 namespace {
@@ -244,23 +245,8 @@ __global__ __launch_bounds__(DN_THREADS) void dense_bgrad_kernel(const float* __
   db[n] = s;
 }
 
-// ---- Dropout: Philox-4x32-10 (Salmon et al., SC'11), counter (q lo, q hi, step, layer), key (seed lo, seed hi); word i of block q
+// ---- Dropout: Philox-4x32-10 (philox.h), counter (q lo, q hi, step, layer), key (seed lo, seed hi); word i of block q
 //      decides element 4 q + i: kept when word >= threshold, and then multiplied by scale ------------
-__device__ inline void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned* o) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    c0 = hi1 ^ c1 ^ k0;
-    c1 = lo1;
-    c2 = hi0 ^ c3 ^ k1;
-    c3 = lo0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
-}
-
 __global__ __launch_bounds__(DN_THREADS) void dropout_kernel(const float* __restrict__ x, float* __restrict__ y, long long n,
                                                              dlwp_dropout d, int vec) {
   const long long q = (long long)blockIdx.x * DN_THREADS + threadIdx.x;

@@ -24,6 +24,22 @@ numpy arrays with device='cuda', are reduced by dlwp_ens_mean_spread / dlwp_ens_
 sums and the int64 histogram come back.  The device path covers 2 <= M <= 256 and, for `axis`, forecast_error's rule: None (one
 value per lead) and the tuple that keeps the lead and the first field axis (one value per lead and variable); anything else runs
 the host code on downloaded arrays.
+
+The generator (perturb_members, ensemble_forecast; csrc/perturb.hip) MAKES such an ensemble:
+out[s, m, k, i, j] = x[s, k, i, j] + sign * sigma[k] * zeta, the product and the sum each rounded once to float32.
+
+* global member g = first_member + m.  With `control`, member g == 0 is x itself, bit for bit, and p = g - 1; otherwise p = g.  With
+  `antithetic`, draw d = p >> 1 and sign = +1 for even p, -1 for odd p; otherwise d = p and sign = +1.
+* white noise z(d, s, k, i, j), defined for every integer virtual row |i| < 32768: Philox-4x32-10 with key (seed lo, seed hi) and
+  counter (j >> 2, (i + 32768) + 65536 k, d, s); words (w0, w1) give columns 4q, 4q + 1 and (w2, w3) columns 4q + 2, 4q + 3 by
+  u1 = (2 (wa >> 9) + 1) 2^-24, u2 = (wb >> 8) 2^-24 (both exact in float32), r = sqrt(-2 ln u1), z_even = r cos(2 pi u2),
+  z_odd = r sin(2 pi u2); |z| <= sqrt(48 ln 2).  white_noise() evaluates the pair in float64; z is that value rounded to float32 (the
+  kernel's float32 evaluation is within a few float32 roundings of it).
+* smoothing: R = ceil(3 L) <= 16 per axis, taps g_a proportional to exp(-a^2 / 2 L^2), normalised in float64 to sum g^2 = 1 and then
+  rounded to float32 (smoothing_taps).  zeta(i, j) = sum_a g_a sum_b g_b z(i + a, (j + b) mod W): the longitude pass first, then
+  latitude, taps in ascending order, float32 accumulators from 0, every product and every sum rounded.  Rows beyond the grid exist
+  in counter space, so there is no boundary rule.  R_x > W, K >= 65536 and H + R_y >= 32768 are refused.
+* NaN in x stays NaN at that element only.
 """
 import collections
 
@@ -33,6 +49,7 @@ import torch
 from .verify import _common_device, _groups_run, _prod, _to_device, _to_host, _wants_device
 
 MAX_DEVICE_MEMBERS = 256
+MAX_RADIUS = 16
 
 #: rmse_mean, mae_mean, spread, spread_skill (= spread / rmse_mean), crps, fair_crps: float32 (T,) or (T, G); rank_hist: int64
 #: (T[, G], M + 1); count: int64, the columns counted; crps_field: the per-column crps (T, S, *field) or None
@@ -230,3 +247,172 @@ def ensemble_scores(forecast, valid, member_axis=2, axis=None, ddof=1, crps_fiel
     forecast, valid = np.asarray(forecast, dtype=np.float32), np.asarray(valid, dtype=np.float32)
     sums, hist, field_out = _scores_host(forecast, valid, member_axis, axis, crps_field)
     return finish(sums, hist, m, ddof, field_out)
+
+
+# -- the member generator: the numpy statement of the definition (module docstring) ------------------------------------------------ #
+_M32 = np.uint64(0xffffffff)
+
+
+def philox4x32_10(counter, key):
+    """Philox-4x32-10 (Salmon et al., SC'11).  counter: four integer arrays that broadcast together (32-bit values), key: two 32-bit
+    integers.  Returns four uint32 arrays."""
+    c0, c1, c2, c3 = np.broadcast_arrays(*[np.asarray(c, dtype=np.uint64) & _M32 for c in counter])
+    k0, k1 = np.uint64(int(key[0]) & 0xffffffff), np.uint64(int(key[1]) & 0xffffffff)
+    m0, m1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
+    for _ in range(10):
+        p0, p1 = m0 * c0, m1 * c2                            # 32 x 32 -> 64 bits: no overflow in uint64
+        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & _M32, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & _M32
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & _M32, (k1 + np.uint64(0xBB67AE85)) & _M32
+    return tuple(c.astype(np.uint32) for c in (c0, c1, c2, c3))
+
+
+def pair_uniforms(wa, wb):
+    """(u1, u2) of a word pair, float64: u1 = (2 (wa >> 9) + 1) 2^-24 in (0, 1), u2 = (wb >> 8) 2^-24 in [0, 1); both are float32 values"""
+    wa, wb = np.asarray(wa, dtype=np.uint32), np.asarray(wb, dtype=np.uint32)
+    return (2.0 * (wa >> np.uint32(9)).astype(np.float64) + 1.0) * 2.0 ** -24, (wb >> np.uint32(8)).astype(np.float64) * 2.0 ** -24
+
+
+def white_noise(seed, draw, sample, channel, rows, width):
+    """z(draw, sample, channel, i, j) for the virtual rows `rows` (integers, |i| < 32768) and j < width, evaluated in float64:
+    (len(rows), width).  The definition's z is this rounded to float32."""
+    seed = int(seed) & 0xffffffffffffffff
+    rows = np.asarray(rows, dtype=np.int64).reshape(-1)
+    quads = (int(width) + 3) // 4
+    w = philox4x32_10((np.arange(quads, dtype=np.int64)[None, :], (rows + 32768 + 65536 * int(channel))[:, None], int(draw), int(sample)),
+                      (seed & 0xffffffff, seed >> 32))
+    z = np.empty((rows.size, quads, 4), np.float64)
+    for e, (wa, wb) in enumerate(((w[0], w[1]), (w[2], w[3]))):
+        u1, u2 = pair_uniforms(wa, wb)
+        r = np.sqrt(-2.0 * np.log(u1))
+        z[:, :, 2 * e] = r * np.cos(2.0 * np.pi * u2)
+        z[:, :, 2 * e + 1] = r * np.sin(2.0 * np.pi * u2)
+    return z.reshape(rows.size, 4 * quads)[:, :int(width)]
+
+
+def smoothing_taps(length):
+    """(R, float32 taps g_a for a = -R .. R) of one axis: R = ceil(3 L), g_a proportional to exp(-a^2 / 2 L^2), normalised in float64 to
+    sum g^2 = 1, then rounded to float32; L = 0 gives R = 0 and g = [1]"""
+    length = float(length)
+    if not length >= 0.0:
+        raise ValueError("'length' must be >= 0, got %r" % (length,))
+    radius = int(np.ceil(3.0 * length))
+    if radius > MAX_RADIUS:
+        raise ValueError("'length' %r needs a radius of %d grid points, at most %d" % (length, radius, MAX_RADIUS))
+    if radius == 0:
+        return 0, np.ones(1, np.float32)
+    a = np.arange(-radius, radius + 1, dtype=np.float64)
+    g = np.exp(-a * a / (2.0 * length * length))
+    return radius, (g / np.sqrt((g * g).sum())).astype(np.float32)
+
+
+def _smooth_host(seed, draw, sample, channel, height, width, taps_y, taps_x):
+    """zeta of one (draw, sample, channel): float32 (height, width)"""
+    ry, rx = taps_y.size // 2, taps_x.size // 2
+    z = white_noise(seed, draw, sample, channel, np.arange(-ry, height + ry), width).astype(np.float32)
+    rowp = np.zeros(z.shape, np.float32)
+    for b in range(-rx, rx + 1):                                   # ascending taps; float32 product, float32 sum
+        rowp = rowp + taps_x[b + rx] * np.roll(z, -b, axis=1)
+    zeta = np.zeros((height, width), np.float32)
+    for a in range(-ry, ry + 1):
+        zeta = zeta + taps_y[a + ry] * rowp[ry + a:ry + a + height]
+    return zeta
+
+
+def _draw_of(g, control, antithetic):
+    """global member -> (draw, sign), or None for the control member"""
+    if control and g == 0:
+        return None
+    p = g - 1 if control else g
+    return (p >> 1, -1.0 if p & 1 else 1.0) if antithetic else (p, 1.0)
+
+
+def _perturb_args(predictors, members, stddev, length, seed, member_axis, first_member):
+    shape = tuple(int(s) for s in predictors.shape)
+    if len(shape) < 2 or _prod(shape) < 1:
+        raise ValueError("'predictors' must be (samples, ..., height, width) or (samples, features) without an empty axis, got %r" % (shape,))
+    s_n = shape[0]
+    k_n, h_n, w_n = (1, 1, shape[1]) if len(shape) == 2 else (_prod(shape[1:-2]), shape[-2], shape[-1])
+    members, first_member = int(members), int(first_member)
+    if members < 1:
+        raise ValueError("'members' must be >= 1, got %d" % members)
+    if first_member < 0 or first_member + members >= 2 ** 31:
+        raise ValueError("'first_member' must be >= 0 and first_member + members < 2^31, got %d" % first_member)
+    if member_axis not in (1, 2):
+        raise ValueError("'member_axis' must be 1 or 2, got %r" % (member_axis,))
+    sigma = np.asarray(stddev, dtype=np.float32).reshape(-1)
+    if sigma.size == 1:
+        sigma = np.repeat(sigma, k_n)
+    if sigma.size != k_n:
+        raise ValueError("'stddev' holds %d values for %d channels (a scalar broadcasts)" % (sigma.size, k_n))
+    ly, lx = (length, length) if np.ndim(length) == 0 else tuple(length)
+    (ry, taps_y), (rx, taps_x) = smoothing_taps(ly), smoothing_taps(lx)
+    if rx > w_n:
+        raise ValueError("'length' %r needs %d columns on either side of a row of %d: more than one wrap" % (lx, rx, w_n))
+    if k_n >= 65536 or h_n + ry >= 32768:
+        raise ValueError('%d channels (at most 65535) or %d + %d rows (below 32768) do not fit the counter' % (k_n, h_n, ry))
+    return shape, (s_n, k_n, h_n, w_n), members, first_member, np.ascontiguousarray(sigma), taps_y, taps_x, int(seed) & 0xffffffffffffffff
+
+
+def _perturb_host(x, dims, members, first_member, sigma, taps_y, taps_x, seed, control, antithetic):
+    """float32 (S, M, K, H, W)"""
+    s_n, k_n, h_n, w_n = dims
+    x = x.reshape(dims)
+    out = np.empty((s_n, members, k_n, h_n, w_n), np.float32)
+    cache = {}
+    for m in range(members):
+        ds = _draw_of(first_member + m, control, antithetic)
+        if ds is None:
+            out[:, m] = x
+            continue
+        for s in range(s_n):
+            for k in range(k_n):
+                key = (ds[0], s, k)
+                if key not in cache:                               # the partner of an antithetic pair follows at once
+                    cache.clear()
+                    cache[key] = _smooth_host(seed, ds[0], s, k, h_n, w_n, taps_y, taps_x)
+                with np.errstate(invalid='ignore', over='ignore'):
+                    out[s, m, k] = x[s, k] + np.float32(ds[1]) * (sigma[k] * cache[key])
+    return out
+
+
+def perturb_members(predictors, members, stddev=1.0, length=0.0, seed=0, member_axis=2, control=True, antithetic=False,
+                    first_member=0, device=None):
+    """A perturbed-initial-condition ensemble of `predictors` (S, ..., H, W) -- every axis between the first and the last two counts
+    as a channel -- or (S, F) (one channel, one row): `members` copies of every sample, each plus stddev * (spatially correlated,
+    longitude-periodic Gaussian noise of unit variance), by the definition of the module docstring.  stddev: a scalar or one value
+    per channel; length: the correlation length in grid points, a scalar or (L_y, L_x), 0 for white noise; control: member 0 is the
+    unperturbed state; antithetic: members come in +/- pairs; first_member: the global index of this call's first member, so that
+    an ensemble can be extended or cut across ranks with the same bits.  Returns the batch predict_timeseries takes, float32:
+    (S * M, ...) with members fastest (member_axis=2) or (M * S, ...) with samples fastest (member_axis=1) -- a CUDA tensor for a CUDA
+    tensor or device='cuda' (made by dlwp_ens_perturb), else a numpy array (made by the numpy code above)."""
+    shape, dims, members, first_member, sigma, taps_y, taps_x, seed = _perturb_args(predictors, members, stddev, length, seed, member_axis,
+                                                                                 first_member)
+    s_n = dims[0]
+    flat = (s_n * members,) + shape[1:]
+    named = (('predictors', predictors),)
+    if _wants_device(named, device):
+        from .. import ops
+        dev = _device_of(named, device)
+        with torch.cuda.device(dev):
+            x = _to_device(predictors, dev).view(dims)
+            out = ops.ens_perturb(x, torch.from_numpy(sigma).to(dev), members, first_member, seed, taps_y, taps_x, control, antithetic,
+                                  member_axis)
+        return out.view(flat)
+    x = np.ascontiguousarray(predictors, dtype=np.float32)
+    out = _perturb_host(x, dims, members, first_member, sigma, taps_y, taps_x, seed, bool(control), bool(antithetic))
+    if member_axis == 1:
+        out = np.ascontiguousarray(np.moveaxis(out, 1, 0))
+    return out.reshape(flat)
+
+
+def ensemble_forecast(wrapper, predictors, time_steps, members, stddev=1.0, length=0.0, seed=0, member_axis=2, control=True,
+                      antithetic=False, first_member=0, keep_time_dim=False, device=None):
+    """Generate -> roll out, without a host array: perturb_members on the device, then wrapper.predict_timeseries(x, time_steps,
+    return_device=True) on the S * M rows.  Returns the series as a CUDA tensor viewed as (T, S, M, ...) (member_axis=2) or
+    (T, M, S, ...) (member_axis=1): what ensemble_mean_spread and ensemble_scores take."""
+    s_n = int(predictors.shape[0])
+    x = perturb_members(predictors, members, stddev, length, seed, member_axis, control, antithetic, first_member,
+                        device=device if (device is not None or isinstance(predictors, torch.Tensor)) else 'cuda')
+    series = wrapper.predict_timeseries(x, time_steps, keep_time_dim=keep_time_dim, return_device=True)
+    lead = (s_n, int(members)) if member_axis == 2 else (int(members), s_n)
+    return series.view((int(series.shape[0]),) + lead + tuple(series.shape[2:]))

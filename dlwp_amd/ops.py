@@ -1987,6 +1987,58 @@ def ens_score_sums(x, strides, y, leads, samples, members, groups, run, crps_fie
     return (sums, hist, crps) if crps_field else (sums, hist)
 
 
+# -- the ensemble member generator (csrc/perturb.hip) -------------------------------------------------------------------------------- #
+ENS_MAX_RADIUS = _lib.ENS_MAX_RADIUS
+
+
+def ens_perturb_desc(samples, channels, height, width, members, first_member, seed, taps_y, taps_x, control, antithetic,
+                     sample_stride, member_stride):
+    """The by-value descriptor of dlwp_ens_perturb; taps_*: odd-length float32 tables (model.ensemble.smoothing_taps)."""
+    d = _lib.EnsPerturb()
+    d.samples, d.channels, d.height, d.width = int(samples), int(channels), int(height), int(width)
+    d.members, d.first_member, d.seed = int(members), int(first_member), int(seed) & 0xffffffffffffffff
+    for name, taps in (('y', taps_y), ('x', taps_x)):
+        taps = np.asarray(taps, dtype=np.float32).reshape(-1)
+        if taps.size % 2 != 1 or taps.size > 2 * ENS_MAX_RADIUS + 1:
+            raise ValueError('ens_perturb: %d taps on axis %s, expected an odd count up to %d' % (taps.size, name, 2 * ENS_MAX_RADIUS + 1))
+        setattr(d, 'radius_' + name, taps.size // 2)
+        table = getattr(d, 'taps_' + name)
+        for i, v in enumerate(taps.tolist()):
+            table[i] = v
+    d.control, d.antithetic = int(bool(control)), int(bool(antithetic))
+    d.sample_stride, d.member_stride = int(sample_stride), int(member_stride)
+    return d
+
+
+def ens_perturb(x, sigma, members, first_member=0, seed=0, taps_y=(1.0,), taps_x=(1.0,), control=True, antithetic=False,
+                member_axis=2, out=None):
+    """include/dlwp_hip.h: dlwp_ens_perturb.  x: contiguous float32 device tensor (S, K, H, W); sigma: float32 device tensor of K
+    elements.  Returns a float32 tensor (S, M, K, H, W) (member_axis=2) or (M, S, K, H, W) (member_axis=1), new or `out` (any
+    contiguous float32 tensor of that many elements), enqueued on the current stream."""
+    _check_f32(x, sigma, out)
+    d = _dev(x)
+    if x.dim() != 4:
+        raise ValueError('ens_perturb: x must be (samples, channels, height, width), got %r' % (tuple(x.shape),))
+    s_n, k_n, h_n, w_n = (int(v) for v in x.shape)
+    members = int(members)
+    if members < 1:
+        raise ValueError('ens_perturb: %d members, at least 1' % members)
+    if _dev(sigma) != d or sigma.numel() != k_n:
+        raise ValueError('ens_perturb: sigma holds %d elements on device %d, expected %d on device %d' % (sigma.numel(), _dev(sigma), k_n, d))
+    row = k_n * h_n * w_n
+    _, sample_stride, member_stride = ens_strides(s_n, members, row, member_axis)
+    desc = ens_perturb_desc(s_n, k_n, h_n, w_n, members, first_member, seed, taps_y, taps_x, control, antithetic, sample_stride,
+                            member_stride)
+    shape = (s_n, members, k_n, h_n, w_n) if member_axis == 2 else (members, s_n, k_n, h_n, w_n)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    elif out.numel() != s_n * members * row or out.device != x.device:
+        raise ValueError('ens_perturb: out holds %d elements on %s, expected %d on %s' % (out.numel(), out.device, s_n * members * row,
+                                                                                        x.device))
+    _lib.check(_lib.lib.dlwp_ens_perturb(_lib.handle(d), _ptr(x), _ptr(sigma), _ptr(out), desc, _stream(x)))
+    return out.view(shape)
+
+
 # -- batches of a series generator out of an HBM-resident series (csrc/series.hip) --------------------------------------------------- #
 SERIES_CHUNK_UNITS = 1024          # units (16 bytes, or one float on the scalar path) a block moves per turn
 

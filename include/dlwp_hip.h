@@ -1218,6 +1218,38 @@ int dlwp_ens_score_sums(dlwp_handle_t, const void* x, long long lead_stride, lon
                         const void* y, int leads, int samples, int members, int groups, long long run, void* sums, void* hist,
                         void* crps_out, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- the ensemble member generator (csrc/perturb.hip; the reference has no counterpart): a perturbed-
+ *      initial-condition ensemble made in HBM.  x: float32 (samples, channels, height, width) contiguous; sigma: float32[channels];
+ *        out[s * sample_stride + m * member_stride + (k * height + i) * width + j] = x[s, k, i, j] + sign * sigma[k] * zeta
+ *      for m < members, strides in ELEMENTS (the two layouts of the table above: (S, M, row) has sample_stride = M * row and
+ *      member_stride = row; (M, S, row) has sample_stride = row and member_stride = S * row), the product and the sum each rounded
+ *      once to float32.  Global member g = first_member + m; with `control`, member g == 0 is x itself bit for bit and p = g - 1,
+ *      otherwise p = g; with `antithetic`, draw d = p >> 1 and sign = -1 for odd p, otherwise d = p and sign = +1.
+ *      White noise z(d, s, k, i, j), defined for every VIRTUAL row |i| < 32768: Philox-4x32-10 with key (seed low, seed high) and
+ *      counter (j >> 2, (i + 32768) + 65536 k, d, s); words (w0, w1) give columns 4q, 4q + 1 and (w2, w3) columns 4q + 2, 4q + 3 by
+ *        u1 = (2 (wa >> 9) + 1) 2^-24, u2 = (wb >> 8) 2^-24, r = sqrt(-2 ln u1), z_even = r cos(2 pi u2), z_odd = r sin(2 pi u2).
+ *      zeta(i, j) = sum_a taps_y[a + radius_y] sum_b taps_x[b + radius_x] z(i + a, (j + b) mod width): the longitude pass first, then
+ *      latitude, taps in ascending order, float32 accumulators from 0 (the caller normalises the taps to sum g^2 = 1; radius 0 with
+ *      tap 1 is white noise).  Both radii 0: no LDS, a lane owns a column quad and stores it for every member it is given (16-byte
+ *      accesses where width and both strides are multiples of 4 and x, out are 16-byte aligned).  Otherwise a workgroup stages a
+ *      32 x 64 tile of white noise plus its halo in LDS; the wrap and the rows beyond the grid come from the counter, not from memory.
+ *      No atomics, no workspace, no synchronisation; the same bits on every run, for every split of the members over calls and
+ *      in both layouts.  NaN in x stays NaN at that element only.  Refused without a launch, in this order: sizes < 1, members < 1,
+ *      first_member < 0, a radius outside 0 .. 16, radius_x > width, channels >= 65536, height + radius_y >= 32768, flags other
+ *      than 0 / 1, sizes too large for one grid, output strides that overlap, null or misaligned pointers, a null handle.
+ *      Not part of a training step: it marks a recording tape foreign.                                                      */
+#define DLWP_ENS_MAX_RADIUS 16
+typedef struct {
+  int samples, channels, height, width;
+  int members, first_member;
+  unsigned long long seed;
+  int radius_y, radius_x;
+  float taps_y[2 * DLWP_ENS_MAX_RADIUS + 1], taps_x[2 * DLWP_ENS_MAX_RADIUS + 1];   /* taps_*[a + radius], a = -radius .. radius */
+  int control, antithetic;
+  long long sample_stride, member_stride;
+} dlwp_ens_perturb_desc;
+int dlwp_ens_perturb(dlwp_handle_t, const void* x, const void* sigma, void* out, dlwp_ens_perturb_desc d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
