@@ -11,6 +11,7 @@ from . import _lib
 from ._lib import (ACT_LINEAR, ACT_RELU, ACT_TANH, PAD_EDGE, PAD_REFLECT, PAD_SYMMETRIC, PAD_WRAP, PAD_ZERO,  # noqa: F401
                    SRC_DIRECT, SRC_MAXPOOL2,
                    SRC_UPSAMPLE2, Conv2d, Pad2d, Shape4)
+from .plan import _phase_geometry
 
 ACTIVATIONS = {None: ACT_LINEAR, 'linear': ACT_LINEAR, 'tanh': ACT_TANH, 'relu': ACT_RELU}
 
@@ -590,11 +591,7 @@ def set_bf16_mfma(enable):
     return bool(_lib.set_option(_lib.OPT_BF16_MFMA, 1 if enable else 0))
 
 
-def phase_geometry(k, pad):
-    """(k2, lo, hi): the window of distinct source offsets [lo, hi] (size k2) that the k taps of a convolution on a 2x
-    up-sampled axis reach, for the two output phases, with a top / left halo of `pad` on the up-sampled axis."""
-    offs = [(a + u - pad) // 2 for a in (0, 1) for u in range(k)]
-    return max(offs) - min(offs) + 1, min(offs), max(offs)
+phase_geometry = _phase_geometry    # (k, pad) -> (k2, lo, hi): the planner's formula (plan.py imports without the library)
 
 
 def phase_weights(w_hwio, bias, pad_top, pad_left, w2=None, b2=None):

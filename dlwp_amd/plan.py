@@ -108,6 +108,9 @@ class PlanOp(object):
         # conv of a Conv2D(strides=2) only: its source is the space-to-depth image of the MODEL INPUT (the 's2dp' op in front reads
         # STATE_IN), so nobody needs the gradient of that source: the backward pass launches no data gradient
         self.input_image = kw.pop('input_image', False)
+        # conv only: per-sample (c, h, w) the convolution COMPUTES where that is not what it stores (out_pool: the pre-pooling tensor,
+        # out_d2s: the 4 F phase channels); None = out_shape.  FLOP accounting reads it (conv_flops_per_sample, bench.py)
+        self.conv_out_shape = kw.pop('conv_out_shape', None)
         assert not kw, kw
 
     @property
@@ -154,7 +157,9 @@ class Plan(object):
         self.output_shapes = []  # per-sample logical shapes of the model outputs
         self.output_store = []   # per-sample stored (c, h, w) of each output slot
         self.conv_layers = []    # unique Conv2D layers in first-use order
-        self.phase_params = []   # derived (phase-summed) kernels: dicts layer, w2_shape, b2 (bool), pad_top, pad_left
+        # derived kernels ('phasew' / 'tphasew' / 'sphasew' ops; _PlanBuilder.derived_kernel): dicts layer, w2_shape, bias (bool: a
+        # derived bias too) + either pad_top, pad_left (an up-sampled Conv2D) or kind in {'tconv', 'sconv'}
+        self.phase_params = []
         self.bn_layers = []      # BatchNormalization layers in plan order (one 'bn' op each)
         self.dense_layers = []   # Dense layers in plan order (one 'dense' op each)
         self.dropout_layers = [] # Dropout layers in graph order (training plans: one 'dropout' op each; its index keys the mask)
@@ -185,7 +190,7 @@ class Plan(object):
                     tot += op.alg_flops
                     continue
                 kh, kw = op.layer.kernel_size
-                co, ho, wo = getattr(op, 'conv_out_shape', None) or op.out_shape
+                co, ho, wo = op.conv_out_shape or op.out_shape
                 tot += 2 * ho * wo * co * op.xs[0] * kh * kw
                 if op.src2 is not None:          # a whole ConvLSTM2D step: the input convolution's share
                     k2 = op.src2['layer'].kernel_size
@@ -287,7 +292,7 @@ RESTATE_UPSAMPLED = os.environ.get('DLWP_RESTATE_UPSAMPLED', '1') != '0'
 
 def _phase_geometry(k, pad):
     """(k2, lo, hi): the distinct source offsets [lo, hi] the k taps of an axis reach on a 2x up-sampled tensor with a
-    top / left halo of `pad` (csrc/phase.hip, ops.phase_geometry)."""
+    top / left halo of `pad` (csrc/phase.hip: dlwp_phase_geometry; ops.phase_geometry is this function)."""
     offs = [(a + u - pad) // 2 for a in (0, 1) for u in range(k)]
     return max(offs) - min(offs) + 1, min(offs), max(offs)
 
@@ -365,59 +370,77 @@ def _supports_lstm_step(lay, f, ho, wo, t_len, cin, v, halo, act, rec_act):
         return False
 
 
-def build_plan(inputs, outputs, inference=False, fuse_d2s=True, fuse_lstm=False, fuse_lstm_step=True, transform=None):
-    """inputs: [KTensor] (exactly one), outputs: [KTensor].  Returns a Plan.  inference=True additionally moves a
-    MaxPooling2D(2) that is the only consumer of a convolution into that convolution's epilogue (the pre-pooling tensor
-    is never written; the training plan keeps it because the backward pass needs it).
-    transform = (head, tail) (inference plans of a model with one output): the wrapper's imputer / scaler as launches of the model
-    call (csrc/scale.hip).  head: a 'scale' op in front reads the input state and writes a buffer of its own, which every consumer
-    of the model input reads instead; tail: a 'scale' op at the end rewrites the output slot in place.  The state a rollout feeds
-    back therefore stays in unscaled units."""
-    if len(inputs) != 1:
-        raise NotImplementedError('exactly one model input is supported')
-    head, tail = (bool(transform[0]), bool(transform[1])) if transform is not None else (False, False)
-    if (head or tail) and not inference:
-        raise ValueError('an input / output transform belongs to inference plans: training data is prepared on the host')
-    if tail and len(outputs) != 1:
-        raise ValueError('an output transform needs a model with exactly one output, got %d' % len(outputs))
-    plan = Plan()
-    x_in = inputs[0]
-    plan.input_shape = tuple(x_in.shape)
-    order = toposort(outputs)
-    consumers = collections.Counter()
-    for t in order:
-        for i in t.inputs:
-            consumers[i.uid] += 1
-    out_index = {}
-    for o, t in enumerate(outputs):
-        out_index.setdefault(t.uid, []).append(o)
-    plan.output_shapes = [tuple(t.shape) for t in outputs]
-    plan.output_store = [None] * len(outputs)
+def _store_of(shape):
+    """stored 3-D (c, h, w) block of a logical per-sample shape: everything in front of the last two axes is
+    channels (the recurrent (T, C, H, W) layout is (T*C, H, W) in memory).  A rank-1 tensor of F features (Dense models) is
+    stored as (F, 1, 1)."""
+    if len(shape) == 1:
+        return (int(shape[0]), 1, 1)
+    if len(shape) < 3:
+        raise NotImplementedError('dense (non-convolutional) tensors of per-sample shape %r are not on the HIP path'
+                                  % (shape,))
+    c = 1
+    for d in shape[:-2]:
+        c *= d
+    return (c, shape[-2], shape[-1])
 
-    def store_of(shape):
-        """stored 3-D (c, h, w) block of a logical per-sample shape: everything in front of the last two axes is
-        channels (the recurrent (T, C, H, W) layout is (T*C, H, W) in memory).  A rank-1 tensor of F features (Dense models) is
-        stored as (F, 1, 1)."""
-        if len(shape) == 1:
-            return (int(shape[0]), 1, 1)
-        if len(shape) < 3:
-            raise NotImplementedError('dense (non-convolutional) tensors of per-sample shape %r are not on the HIP path'
-                                      % (shape,))
-        c = 1
-        for d in shape[:-2]:
-            c *= d
-        return (c, shape[-2], shape[-1])
 
-    plan._in_store = store_of(x_in.shape)
-    views = {}
-    in_buf = STATE_IN                  # what the consumers of the model input read
-    if head:
-        in_buf = plan.new_buffer(*plan._in_store)
-        plan.ops.append(PlanOp('scale', STATE_IN, in_buf, plan._in_store, role='head', out_shape=plan._in_store))
+# what the per-step emitters of a ConvLSTM2D share (_PlanBuilder.lower_convlstm)
+_LstmSteps = collections.namedtuple('_LstmSteps', 'lay v halo rhalo cin f ho wo t_len hbuf cbufs zxs zhs act rec')
 
-    producer = {}                      # scratch buffer -> the conv op that wrote all of it
 
-    def emit(op):
+class _PlanBuilder(object):
+    """The state of one build_plan call and one lowering method per layer kind (_LOWERINGS below says which).  A lowering method
+    (t, lay, ins, outs) -- the tensor, its layer, the views of its inputs, the output slots it fills -- sets views[t.uid].
+    Buffer numbers are part of the contract (the backward pass, bf16_buffers() and the rollout op table index buffers by
+    number): the order of the new_buffer calls inside a method must not change."""
+
+    def __init__(self, inputs, outputs, inference, fuse_d2s, fuse_lstm, fuse_lstm_step, head):
+        self.inference, self.fuse_d2s, self.fuse_lstm, self.fuse_lstm_step = inference, fuse_d2s, fuse_lstm, fuse_lstm_step
+        self.plan = plan = Plan()
+        self.x_in = inputs[0]
+        plan.input_shape = tuple(self.x_in.shape)
+        self.order = toposort(outputs)
+        self.consumers = collections.Counter()
+        for t in self.order:
+            for i in t.inputs:
+                self.consumers[i.uid] += 1
+        self.out_index = {}
+        for o, t in enumerate(outputs):
+            self.out_index.setdefault(t.uid, []).append(o)
+        plan.output_shapes = [tuple(t.shape) for t in outputs]
+        plan.output_store = [None] * len(outputs)
+        plan._in_store = _store_of(self.x_in.shape)
+        self.views = {}
+        self.in_buf = STATE_IN             # what the consumers of the model input read
+        if head:
+            self.in_buf = plan.new_buffer(*plan._in_store)
+            plan.ops.append(PlanOp('scale', STATE_IN, self.in_buf, plan._in_store, role='head', out_shape=plan._in_store))
+        self.producer = {}                 # scratch buffer -> the conv op that wrote all of it
+
+    def run(self):
+        for t in self.order:
+            lay = t.layer
+            if isinstance(lay, L.InputLayer):
+                if t.uid != self.x_in.uid:
+                    raise ValueError('graph reaches an Input that is not the model input')
+                c, h, w = self.plan._in_store
+                self.views[t.uid] = View(self.in_buf, 0, c, c, h, w, shape=tuple(t.shape) if len(t.shape) != 3 else None)
+                continue
+            ins = [self.views[i.uid] for i in t.inputs]
+            outs = self.out_index.get(t.uid, [])
+            for match, lower in _LOWERINGS:
+                if isinstance(lay, match) if isinstance(match, type) else match(lay):
+                    break
+            else:
+                raise NotImplementedError('layer %s (%s) has no HIP lowering' % (lay.name, type(lay).__name__))
+            lower(self, t, lay, ins, outs)
+            self.finish_outputs(t, outs)
+        return self.plan
+
+    # -- launches and buffers ---------------------------------------------------------------------------------------------------- #
+    def emit(self, op):
+        plan, producer = self.plan, self.producer
         plan.ops.append(op)
         if op.kind == 'conv' and op.dst >= 0 and op.out_c_off == 0 and op.out_c_total == op.layer.filters:
             producer[op.dst] = op
@@ -427,9 +450,10 @@ def build_plan(inputs, outputs, inference=False, fuse_d2s=True, fuse_lstm=False,
             plan.conv_layers.append(op.layer)
         return op
 
-    def materialize(v, dst=None, dst_c_off=0, dst_c_total=None):
+    def materialize(self, v, dst=None, dst_c_off=0, dst_c_total=None):
         """Turn a lazy view into real data.  With dst=None a new buffer is created (or the view is returned untouched if
         it is already a whole buffer).  With dst given, the data lands in channels [dst_c_off, +c) of that buffer."""
+        plan, emit = self.plan, self.emit
         cur = v
         steps = []
         if not (cur.c_off == 0 and cur.c == cur.c_total) and not cur.plain:
@@ -469,629 +493,593 @@ def build_plan(inputs, outputs, inference=False, fuse_d2s=True, fuse_lstm=False,
                 cur = View(dst, dst_c_off, cur.c, tot, cur.h, cur.w)
         return cur
 
-    for t in order:
-        lay = t.layer
-        if isinstance(lay, L.InputLayer):
-            if t.uid != x_in.uid:
-                raise ValueError('graph reaches an Input that is not the model input')
-            c, h, w = plan._in_store
-            views[t.uid] = View(in_buf, 0, c, c, h, w, shape=tuple(t.shape) if len(t.shape) != 3 else None)
-            continue
-        ins = [views[i.uid] for i in t.inputs]
-        outs = out_index.get(t.uid, [])
+    # -- the idioms the lowerings share ------------------------------------------------------------------------------------------ #
+    def out_or_new(self, outs, shape):
+        """where a layer's launch writes: the model's output slot when the tensor is a model output (the slot's stored shape is
+        recorded), a new scratch buffer otherwise"""
+        if outs:
+            self.plan.output_store[outs[0]] = shape
+            return OUT(outs[0])
+        return self.plan.new_buffer(*shape)
 
-        if isinstance(lay, L._Pad2DBase):
-            v = ins[0]
-            if v.shape is not None:
-                raise NotImplementedError('%s on a reshaped (non-3D) tensor' % lay.name)
-            if lay.data_format == 'channels_last':
-                # standalone only: buffer holds (H, W, C) per sample, rows of W*C floats
-                v = materialize(v)
-                hh, ww, cc = t.inputs[0].shape
-                (tp, bt), (lf, rt) = lay.padding
-                nb = plan.new_buffer(hh + tp + bt, ww + lf + rt, cc)
-                emit(PlanOp('pad', v.buf, nb, (1, hh, ww), halo=Halo(tp, bt, lf, rt, lay.mode, lay.mode), inner=cc,
-                            out_shape=(hh + tp + bt, ww + lf + rt, cc)))
-                views[t.uid] = View(nb, 0, hh + tp + bt, hh + tp + bt, ww + lf + rt, cc)
-                views[t.uid].shape = tuple(t.shape)
-            else:
-                halo = _compose_halo(v.halo, lay.padding, lay.mode)
-                if halo is None:
-                    v = materialize(v)
-                    halo = _compose_halo(NO_HALO, lay.padding, lay.mode)
-                hh, ww = v.src_hw
-                if halo.mode_h == PAD_WRAP and max(halo.top, halo.bottom) > hh:
-                    raise ValueError('%s: periodic row padding exceeds the input height %d' % (lay.name, hh))
-                if halo.mode_w == PAD_WRAP and max(halo.left, halo.right) > ww:
-                    raise ValueError('%s: periodic column padding exceeds the input width %d' % (lay.name, ww))
-                views[t.uid] = v.copy(halo=halo)
-        elif isinstance(lay, L._Pad3DBase):
-            # (T, C, H, W) stored as (T*C, H, W): a 3-D pad that leaves the first (channel) axis alone is the 2-D halo
-            v = ins[0]
-            if lay.data_format != 'channels_first':
-                raise NotImplementedError("%s: data_format='channels_first' is required" % lay.name)
-            if lay.padding[0] != (0, 0):
-                raise NotImplementedError('%s: padding of the first (channel) axis %r is not lowered to the HIP path'
-                                          % (lay.name, lay.padding[0]))
-            pad2 = (lay.padding[1], lay.padding[2])
-            halo = _compose_halo(v.halo, pad2, lay.mode)
-            if halo is None:
-                shp = v.shape
-                v = materialize(v)
-                v.shape = shp
-                halo = _compose_halo(NO_HALO, pad2, lay.mode)
-            hh, ww = v.src_hw
-            if halo.mode_h == PAD_WRAP and max(halo.top, halo.bottom) > hh:
-                raise ValueError('%s: periodic row padding exceeds the input height %d' % (lay.name, hh))
-            if halo.mode_w == PAD_WRAP and max(halo.left, halo.right) > ww:
-                raise ValueError('%s: periodic column padding exceeds the input width %d' % (lay.name, ww))
-            views[t.uid] = v.copy(halo=halo, shape=tuple(t.shape))
-        elif isinstance(lay, L.ConvLSTM2D):
-            v = ins[0]
-            t_len, cin = t.inputs[0].shape[0], t.inputs[0].shape[1]
-            if v.c != t_len * cin:
-                raise ValueError('%s: input view has %d channels, expected T*C = %d' % (lay.name, v.c, t_len * cin))
-            halo = v.halo
-            if lay.padding == 'same':
-                st, sb, sl, sr = lay.same_halo()
-                halo2 = _compose_halo(halo, ((st, sb), (sl, sr)), PAD_ZERO)
-                if halo2 is None:
-                    v = materialize(v)
-                    halo2 = Halo(st, sb, sl, sr, PAD_ZERO, PAD_ZERO)
-                halo = halo2
-            _, hl, wl = v.copy(halo=halo).logical
-            ho = hl - lay.dilation_rate[0] * (lay.kernel_size[0] - 1)
-            wo = wl - lay.dilation_rate[1] * (lay.kernel_size[1] - 1)
-            f = lay.filters
-            hbuf = plan.new_buffer(t_len * f, ho, wo)           # h_0 .. h_{T-1}, the return_sequences output
-            # every step keeps its own pre-activations and cell state: they are the saved activations of the backward
-            # pass (dlwp_convlstm_gates_bwd) -- T is the reference's time_dim (2), so this costs little
-            cbufs = [plan.new_buffer(f, ho, wo) for _ in range(t_len)]
-            rk = ((lay.kernel_size[0] - 1) // 2, (lay.kernel_size[1] - 1) // 2)
-            rec_code = {'hard_sigmoid': 0, 'sigmoid': 1}[lay.recurrent_activation]
-            rhalo = Halo(rk[0], rk[0], rk[1], rk[1], PAD_ZERO, PAD_ZERO)
-            # bfloat16 inference: the convolution that completes a step's pre-activations applies the cell update in its
-            # epilogue (the input convolution on the first step, the recurrent one afterwards): z_h (z_x on the first step)
-            # is never stored and the gate kernel disappears.  The model input feeds the input convolution as float32.
-            fused = (inference and fuse_lstm and v.buf == STATE_IN and
-                     _supports_lstm_conv((cin, v.h, v.w), lay.input_part, halo, v.src_mode, ACT[lay.activation], rec_code, f,
-                                         v.c_off, v.c_total, 0, t_len * f, False) and
-                     (t_len == 1 or _supports_lstm_conv((f, ho, wo), lay.recurrent_part, rhalo, SRC_DIRECT, ACT[lay.activation],
-                                                        rec_code, f, 0, t_len * f, f, t_len * f, True)))
-            # ... and every later step as ONE launch where the library has the dual-source instance (octet layout; the executor
-            # falls back to the two launches when it cannot keep the h sequence in octets)
-            whole = (fused and fuse_lstm_step and t_len > 1 and os.environ.get('DLWP_LSTM_STEP', '1') != '0' and
-                     _supports_lstm_step(lay, f, ho, wo, t_len, cin, v, halo, ACT[lay.activation], rec_code))
-            zxs = [None if (fused and (step == 0 or whole)) else plan.new_buffer(4 * f, ho, wo) for step in range(t_len)]
-            zhs = [None] + [None if fused else plan.new_buffer(4 * f, ho, wo) for _ in range(t_len - 1)]
-            for step in range(t_len if fused else 0):
-                if step == 0:
-                    emit(PlanOp('conv', v.buf, hbuf, (cin, v.h, v.w), layer=lay.input_part, halo=halo, src_mode=v.src_mode,
-                                act=ACT[lay.activation], rec_act=rec_code, lstm_f=f, aux=(None, None, cbufs[0]),
-                                in_c_off=v.c_off, in_c_total=v.c_total, out_c_off=0, out_c_total=t_len * f,
-                                out_shape=(f, ho, wo)))
-                    continue
-                if whole:
-                    emit(PlanOp('conv', hbuf, hbuf, (f, ho, wo), layer=lay.recurrent_part, halo=rhalo, src_mode=SRC_DIRECT,
-                                act=ACT[lay.activation], rec_act=rec_code, lstm_f=f, aux=(None, cbufs[step - 1], cbufs[step]),
-                                in_c_off=(step - 1) * f, in_c_total=t_len * f, out_c_off=step * f, out_c_total=t_len * f,
-                                out_shape=(f, ho, wo),
-                                src2={'buf': v.buf, 'xs': (cin, v.h, v.w), 'layer': lay.input_part, 'halo': halo,
-                                      'in_c_off': v.c_off + step * cin, 'in_c_total': v.c_total}))
-                    continue
-                emit(PlanOp('conv', v.buf, zxs[step], (cin, v.h, v.w), layer=lay.input_part, halo=halo,
-                            src_mode=v.src_mode, act=0, in_c_off=v.c_off + step * cin, in_c_total=v.c_total, out_c_off=0,
-                            out_c_total=4 * f, out_shape=(4 * f, ho, wo)))
-                emit(PlanOp('conv', hbuf, hbuf, (f, ho, wo), layer=lay.recurrent_part, halo=rhalo, src_mode=SRC_DIRECT,
-                            act=ACT[lay.activation], rec_act=rec_code, lstm_f=f, aux=(zxs[step], cbufs[step - 1], cbufs[step]),
-                            in_c_off=(step - 1) * f, in_c_total=t_len * f, out_c_off=step * f, out_c_total=t_len * f,
-                            out_shape=(f, ho, wo)))
-            for step in range(0 if fused else t_len):
-                emit(PlanOp('conv', v.buf, zxs[step], (cin, v.h, v.w), layer=lay.input_part, halo=halo,
-                            src_mode=v.src_mode, act=0, in_c_off=v.c_off + step * cin, in_c_total=v.c_total, out_c_off=0,
-                            out_c_total=4 * f, out_shape=(4 * f, ho, wo)))
-                if step > 0:
-                    emit(PlanOp('conv', hbuf, zhs[step], (f, ho, wo), layer=lay.recurrent_part,
-                                halo=Halo(rk[0], rk[0], rk[1], rk[1], PAD_ZERO, PAD_ZERO), src_mode=SRC_DIRECT, act=0,
-                                in_c_off=(step - 1) * f, in_c_total=t_len * f, out_c_off=0, out_c_total=4 * f,
-                                out_shape=(4 * f, ho, wo)))
-                emit(PlanOp('lstm', zxs[step], hbuf, (f, ho, wo), act=ACT[lay.activation],
-                            rec_act={'hard_sigmoid': 0, 'sigmoid': 1}[lay.recurrent_activation],
-                            aux=(zhs[step], cbufs[step - 1] if step > 0 else None, cbufs[step]),
-                            out_c_off=step * f, out_c_total=t_len * f, out_shape=(f, ho, wo)))
-            if lay.return_sequences:
-                views[t.uid] = View(hbuf, 0, t_len * f, t_len * f, ho, wo, shape=(t_len, f, ho, wo))
-            else:
-                views[t.uid] = View(hbuf, (t_len - 1) * f, f, t_len * f, ho, wo)
-        elif isinstance(lay, L.UpSampling2D) and lay.interpolation == 'bilinear':
-            # keras UpSampling2D(2, interpolation='bilinear') (csrc/halo.hip): always one launch of its own on a whole stored
-            # buffer -- anything lazy in front is materialised, a channel window is extracted first -- into a new buffer or the
-            # model's output slot.  Never SRC_UPSAMPLE2, never a restated decoder layer and never a convolution's epilogue: the
-            # convolution kernels know nearest up-sampling only.
-            v = ins[0]
-            if v.shape is not None:
-                raise NotImplementedError('%s on a reshaped tensor' % lay.name)
-            v = materialize(v)
-            if not v.full:
-                v = materialize(v, dst=plan.new_buffer(*v.logical))
-            h2, w2 = 2 * v.h, 2 * v.w
-            if outs:
-                dst = OUT(outs[0])
-                plan.output_store[outs[0]] = (v.c, h2, w2)
-            else:
-                dst = plan.new_buffer(v.c, h2, w2)
-            emit(PlanOp('bilinear', v.buf, dst, (v.c, v.h, v.w), out_c_total=v.c, out_shape=(v.c, h2, w2)))
-            views[t.uid] = View(dst, 0, v.c, v.c, h2, w2)
-        elif isinstance(lay, (L.MaxPooling2D, L.UpSampling2D)):
-            v = ins[0]
-            if v.shape is not None:
-                raise NotImplementedError('%s on a reshaped tensor' % lay.name)
-            if not v.plain:
-                v = materialize(v)
-            prod = producer.get(v.buf) if (inference and isinstance(lay, L.MaxPooling2D) and v.full and not outs) else None
-            if (prod is not None and consumers[t.inputs[0].uid] == 1 and not isinstance(prod.layer, L._ConvPart)
-                    and not prod.out_pool and _supports_out_pool(prod)):
-                # the pooling runs in the producing convolution's epilogue: its buffer now holds the pooled tensor
-                prod.out_pool = True
-                c, h2, w2 = v.c, v.h // 2, v.w // 2
-                prod.conv_out_shape = prod.out_shape        # what the convolution computes (FLOP accounting)
-                prod.out_shape = (c, h2, w2)                # what it stores
-                plan.buffers[v.buf] = (c, h2, w2)
-                views[t.uid] = View(v.buf, 0, c, c, h2, w2)
-            else:
-                views[t.uid] = v.copy(src_mode=SRC_MAXPOOL2 if isinstance(lay, L.MaxPooling2D) else SRC_UPSAMPLE2)
-        elif isinstance(lay, L.AveragePooling2D):
-            # keras AveragePooling2D(2) (csrc/halo.hip): always one launch of its own on a whole stored buffer -- anything lazy in
-            # front is materialised, a channel window is extracted first -- into a new buffer or the model's output slot.  Never a
-            # lazy source mode and never a convolution's epilogue: the convolution kernels know max-pooling only.
-            v = ins[0]
-            if v.shape is not None:
-                raise NotImplementedError('%s on a reshaped tensor' % lay.name)
-            v = materialize(v)
-            if not v.full:
-                v = materialize(v, dst=plan.new_buffer(*v.logical))
-            h2, w2 = v.h // 2, v.w // 2
-            if outs:
-                dst = OUT(outs[0])
-                plan.output_store[outs[0]] = (v.c, h2, w2)
-            else:
-                dst = plan.new_buffer(v.c, h2, w2)
-            emit(PlanOp('avgpool', v.buf, dst, (v.c, v.h, v.w), out_c_total=v.c, out_shape=(v.c, h2, w2)))
-            views[t.uid] = View(dst, 0, v.c, v.c, h2, w2)
-        elif isinstance(lay, L.ChannelSlice):
-            v = ins[0]
-            if v.shape is not None:
-                raise NotImplementedError('slice_layer on a reshaped tensor')
-            lo, hi = lay.window(v.c)
-            views[t.uid] = v.copy(c_off=v.c_off + lo, c=hi - lo)
-        elif isinstance(lay, L.Reshape):
-            v = materialize(ins[0])
-            if not v.full:
-                v = materialize(v, dst=plan.new_buffer(*v.logical))
-            c, h, w = store_of(t.shape)
-            if (c * h * w) != v.c * v.h * v.w:
-                raise ValueError('Reshape size mismatch')
-            # relabel the same contiguous block
-            if v.buf >= 0:
-                plan.buffers[v.buf] = (c, h, w)
-                views[t.uid] = View(v.buf, 0, c, c, h, w, shape=tuple(t.shape) if len(t.shape) != 3 else None)
-            else:
-                nb = plan.new_buffer(v.c, v.h, v.w)
-                emit(PlanOp('copy', v.buf, nb, (v.c, v.h, v.w), in_c_total=v.c, out_c_total=v.c,
-                            out_shape=(v.c, v.h, v.w)))
-                plan.buffers[nb] = (c, h, w)
-                views[t.uid] = View(nb, 0, c, c, h, w, shape=tuple(t.shape) if len(t.shape) != 3 else None)
-        elif isinstance(lay, L.Concatenate):
-            c_tot = sum(v.logical[0] for v in ins)
-            _, hh, ww = ins[0].logical
-            if outs:
-                o = outs[0]
-                dst = OUT(o)
-                plan.output_store[o] = (c_tot, hh, ww)
-            else:
-                dst = plan.new_buffer(c_tot, hh, ww)
-            off = 0
-            for v in ins:
-                materialize(v, dst=dst, dst_c_off=off, dst_c_total=c_tot)
-                off += v.logical[0]
-            views[t.uid] = View(dst, 0, c_tot, c_tot, hh, ww)
-        elif isinstance(lay, L.Conv2D) and tuple(lay.strides) == (2, 2):
-            # keras Conv2D(strides=2) (csrc/sconv.hip): a stride-1 'valid' convolution of the space-to-depth image P of the padded
-            # input (4 cin phase-major channels) with a kernel that is a permutation of the layer's own, stored with the 3 x 3 /
-            # 5 x 5 taps the matrix-core kernels exist for (tconv_taps; the T x T block at the origin, zero taps below / right, P
-            # that much longer).  Three ops: 'sphasew' (kernel -> derived kernel; plan.phase_params), 's2dp' (the lazy halo of the
-            # input + the layer's own 'same' zeros + the de-interleave in one pass) and ONE 'conv' on P with the layer's bias and
-            # activation in its epilogue.
-            if any(p['layer'] is lay for p in plan.phase_params):
-                raise NotImplementedError('%s: a Conv2D layer with strides=2 applied more than once is not implemented' % lay.name)
-            v = ins[0]
-            if v.shape is not None and len(v.shape) != 3:
-                raise NotImplementedError('%s on a non-3D tensor %r' % (lay.name, v.shape))
-            if v.src_mode != SRC_DIRECT:         # (the pass reads a stored tensor; a halo in front may stay lazy)
-                v = materialize(v.copy(halo=NO_HALO)).copy(halo=v.halo)
-            _, hl, wl = v.logical                                   # what the layer sees as its input
-            (th, pt, pb, ho), (tw, pl, pr, wo) = lay.strided_geometry(hl, wl)
-            halo = _compose_halo(v.halo, ((pt, pb), (pl, pr)), PAD_ZERO)
-            if halo is None:
-                v = materialize(v)
-                halo = Halo(pt, pb, pl, pr, PAD_ZERO, PAD_ZERO)
-            kh, kw = lay.kernel_size
-            sh, sw = tconv_taps(th, tw)
-            hp, wp = ho + sh - 1, wo + sw - 1                       # the phase tensor the stored taps read
-            f = lay.filters
-            alg = 2 * ho * wo * f * v.c * kh * kw
-            pidx = len(plan.phase_params)
-            plan.phase_params.append({'layer': lay, 'w2_shape': (sh, sw, 4 * v.c, f), 'bias': False, 'kind': 'sconv'})
-            emit(PlanOp('sphasew', STATE_IN, STATE_IN, (v.c, 0, 0), layer=lay, wparam=pidx, out_shape=(0, 0, 0)))
-            tmp = plan.new_buffer(4 * v.c, hp, wp)
-            emit(PlanOp('s2dp', v.buf, tmp, (v.c, v.h, v.w), halo=halo, in_c_off=v.c_off, in_c_total=v.c_total,
-                        out_c_total=4 * v.c, out_shape=(4 * v.c, hp, wp)))
-            if outs:
-                dst = OUT(outs[0])
-                plan.output_store[outs[0]] = (f, ho, wo)
-            else:
-                dst = plan.new_buffer(f, ho, wo)
-            emit(PlanOp('conv', tmp, dst, (4 * v.c, hp, wp), layer=lay, halo=NO_HALO, src_mode=SRC_DIRECT, act=ACT[lay.activation],
-                        in_c_off=0, in_c_total=4 * v.c, out_c_off=0, out_c_total=f, out_shape=(f, ho, wo), dil=(1, 1),
-                        ksize=(sh, sw), filters=f, wparam=pidx, alg_flops=alg, input_image=v.buf == STATE_IN))
-            producer.pop(dst, None)              # (a MaxPooling2D behind it stays a launch / a lazy source of its own)
-            views[t.uid] = View(dst, 0, f, f, ho, wo)
-        elif isinstance(lay, L.DepthwiseConv2D):
-            # keras DepthwiseConv2D / SeparableConv2D (csrc/sepconv.hip): 'dwconv' = the stencil, which takes the lazy halo of its
-            # input and the layer's own 'same' zeros composed (a lazy pooling / up-sampling view is materialised first: the stencil
-            # reads a stored tensor); for a SeparableConv2D it has neither bias nor activation and writes a plan buffer that the
-            # training step keeps (the pointwise weight gradient reads it), and 'pwconv' = the 1 x 1 product on the matrix cores
-            # with the layer's bias and activation, which writes the model's output slot or a buffer of its own.
-            if lay in plan.sep_layers:
-                raise NotImplementedError('%s: a %s layer applied more than once is not implemented' % (lay.name, type(lay).__name__))
-            plan.sep_layers.append(lay)
-            v = ins[0]
-            if v.shape is not None and len(v.shape) != 3:
-                raise NotImplementedError('%s on a non-3D tensor %r' % (lay.name, v.shape))
-            if v.src_mode != SRC_DIRECT:
-                v = materialize(v.copy(halo=NO_HALO)).copy(halo=v.halo)
-            halo = v.halo
-            if lay.padding == 'same':
-                st, sb, sl, sr = lay.same_halo()
-                halo2 = _compose_halo(halo, ((st, sb), (sl, sr)), PAD_ZERO)
-                if halo2 is None:
-                    v = materialize(v)
-                    halo2 = Halo(st, sb, sl, sr, PAD_ZERO, PAD_ZERO)
-                halo = halo2
-            _, hl, wl = v.copy(halo=halo).logical
-            ho = hl - lay.dilation_rate[0] * (lay.kernel_size[0] - 1)
-            wo = wl - lay.dilation_rate[1] * (lay.kernel_size[1] - 1)
-            if ho < 1 or wo < 1:
-                raise ValueError('%s: kernel %r with dilation %r does not fit the input' % (lay.name, lay.kernel_size, lay.dilation_rate))
-            q = v.c * lay.depth_multiplier
-            sep = isinstance(lay, L.SeparableConv2D)
-            f = lay.filters if sep else q
-            if outs:
-                dst = OUT(outs[0])
-                plan.output_store[outs[0]] = (f, ho, wo)
-            else:
-                dst = plan.new_buffer(f, ho, wo)
-            mid = plan.new_buffer(q, ho, wo) if sep else dst
-            emit(PlanOp('dwconv', v.buf, mid, (v.c, v.h, v.w), layer=lay, halo=halo, act=0 if sep else ACT[lay.activation],
-                        in_c_off=v.c_off, in_c_total=v.c_total, out_c_off=0, out_c_total=q, out_shape=(q, ho, wo)))
-            if sep:
-                emit(PlanOp('pwconv', mid, dst, (q, ho, wo), layer=lay, act=ACT[lay.activation], in_c_off=0, in_c_total=q,
-                            out_c_off=0, out_c_total=f, out_shape=(f, ho, wo)))
-            views[t.uid] = View(dst, 0, f, f, ho, wo)
-        elif isinstance(lay, L.Conv2D):
-            v = ins[0]
-            if v.shape is not None and len(v.shape) != 3:
-                raise NotImplementedError('%s on a non-3D tensor %r' % (lay.name, v.shape))
-            if v.src_mode == SRC_MAXPOOL2 and _prefers_unfused_pool(v.c, lay):
-                # the Winograd kernels read plain tensors: pool once with the standalone kernel, keep the halo lazy
-                v = materialize(v.copy(halo=NO_HALO)).copy(halo=v.halo)
-            halo = v.halo
-            if lay.padding == 'same':
-                st, sb, sl, sr = lay.same_halo()
-                halo2 = _compose_halo(halo, ((st, sb), (sl, sr)), PAD_ZERO)
-                if halo2 is None:
-                    v = materialize(v)
-                    halo2 = Halo(st, sb, sl, sr, PAD_ZERO, PAD_ZERO)
-                halo = halo2
-            _, hl, wl = v.copy(halo=halo).logical
-            ho = hl - lay.dilation_rate[0] * (lay.kernel_size[0] - 1)
-            wo = wl - lay.dilation_rate[1] * (lay.kernel_size[1] - 1)
-            kh, kw = lay.kernel_size
-            alg = 2 * ho * wo * lay.filters * v.c * kh * kw
-            # ---- inference: a convolution on a 2x nearest-neighbour up-sampled tensor, restated on the tensor itself.
-            # (a) dilation 2, even halo: tap u of output row 2i + a reads source row i + u - top/2 whatever a is, so the
-            #     result is UpSampling2D(conv with dilation 1 and half the halo on the low-resolution tensor): a quarter
-            #     of the multiplies, and the up-sampling stays lazy for the consumer.
-            # both serve the training plan as well: (a) is a plain graph identity (forward, data and weight gradient of
-            # the layer then run on the low-resolution tensors); (b) trains through the adjoints of its two linear maps
-            # (dlwp_phase_weights_bwd, dlwp_space_to_depth2; training.py)
-            # (a mirror halo WITHOUT the border element -- TFPadding2D 'REFLECT' -- does not commute with the up-sampling:
-            #  up-sampled coordinate 2n reflects to source n - 1, low-resolution coordinate n to n - 2; the layer then keeps
-            #  the reference's formulation.  'SYMMETRIC', periodic, zero and edge halos commute.)
-            restate = (RESTATE_UPSAMPLED and v.src_mode == SRC_UPSAMPLE2 and
-                       halo.mode_h != PAD_REFLECT and halo.mode_w != PAD_REFLECT)
-            if (restate and tuple(lay.dilation_rate) == (2, 2) and
-                    all(p % 2 == 0 for p in halo[:4]) and ho % 2 == 0 and wo % 2 == 0):
-                h2 = Halo(halo.top // 2, halo.bottom // 2, halo.left // 2, halo.right // 2, halo.mode_h, halo.mode_w)
-                dst = plan.new_buffer(lay.filters, ho // 2, wo // 2)
-                emit(PlanOp('conv', v.buf, dst, (v.c, v.h, v.w), layer=lay, halo=h2, src_mode=SRC_DIRECT,
-                            act=ACT[lay.activation], in_c_off=v.c_off, in_c_total=v.c_total, out_c_off=0,
-                            out_c_total=lay.filters, out_shape=(lay.filters, ho // 2, wo // 2), dil=(1, 1), alg_flops=alg))
-                views[t.uid] = View(dst, 0, lay.filters, lay.filters, ho // 2, wo // 2, src_mode=SRC_UPSAMPLE2)
-            # (b) dilation 1: the k taps of an axis fall on k2 < k distinct source pixels; each of the 4 output phases is
-            #     a k2 x k2 kernel of summed weights over the SAME window, so the layer runs as one convolution with
-            #     4 x filters channels on the low-resolution tensor + a depth-to-space interleave (csrc/phase.hip).
-            elif (restate and tuple(lay.dilation_rate) == (1, 1) and
-                  ho == 2 * v.h and wo == 2 * v.w and
-                  _phase_geometry(kh, halo.top)[0] * _phase_geometry(kw, halo.left)[0] < kh * kw):
-                (kh2, lo_h, hi_h), (kw2, lo_w, hi_w) = _phase_geometry(kh, halo.top), _phase_geometry(kw, halo.left)
-                h2 = Halo(-lo_h, hi_h, -lo_w, hi_w, halo.mode_h, halo.mode_w)
-                pidx = len(plan.phase_params)
-                plan.phase_params.append({'layer': lay, 'w2_shape': (kh2, kw2, v.c, 4 * lay.filters),
-                                          'bias': lay.use_bias, 'pad_top': halo.top, 'pad_left': halo.left})
-                emit(PlanOp('phasew', STATE_IN, STATE_IN, (v.c, 0, 0), layer=lay, wparam=pidx, halo=halo,
-                            out_shape=(0, 0, 0)))
-                fold = inference and fuse_d2s and _supports_out_d2s((v.c, v.h, v.w), 4 * lay.filters, (kh2, kw2), h2,
-                                                           ACT[lay.activation], v.c_off, v.c_total)
-                if outs:
-                    dst = OUT(outs[0])
-                    plan.output_store[outs[0]] = (lay.filters, ho, wo)
-                else:
-                    dst = plan.new_buffer(lay.filters, ho, wo)
-                if fold:         # the convolution's epilogue stores the phases interleaved: no depth-to-space pass
-                    op = PlanOp('conv', v.buf, dst, (v.c, v.h, v.w), layer=lay, halo=h2, src_mode=SRC_DIRECT,
-                                act=ACT[lay.activation], in_c_off=v.c_off, in_c_total=v.c_total, out_c_off=0,
-                                out_c_total=lay.filters, out_shape=(lay.filters, ho, wo), dil=(1, 1),
-                                ksize=(kh2, kw2), filters=4 * lay.filters, wparam=pidx, alg_flops=alg, out_d2s=True)
-                    op.conv_out_shape = (4 * lay.filters, v.h, v.w)
-                    emit(op)
-                else:
-                    tmp = plan.new_buffer(4 * lay.filters, v.h, v.w)
-                    emit(PlanOp('conv', v.buf, tmp, (v.c, v.h, v.w), layer=lay, halo=h2, src_mode=SRC_DIRECT,
-                                act=ACT[lay.activation], in_c_off=v.c_off, in_c_total=v.c_total, out_c_off=0,
-                                out_c_total=4 * lay.filters, out_shape=(4 * lay.filters, v.h, v.w), dil=(1, 1),
-                                ksize=(kh2, kw2), filters=4 * lay.filters, wparam=pidx, alg_flops=alg))
-                    emit(PlanOp('d2s', tmp, dst, (lay.filters, v.h, v.w), out_c_off=0, out_c_total=lay.filters,
-                                out_shape=(lay.filters, ho, wo)))
-                views[t.uid] = View(dst, 0, lay.filters, lay.filters, ho, wo)
-            else:
-              if outs:
-                dst = OUT(outs[0])
-                plan.output_store[outs[0]] = (lay.filters, ho, wo)
-              else:
-                dst = plan.new_buffer(lay.filters, ho, wo)
-              emit(PlanOp('conv', v.buf, dst, (v.c, v.h, v.w), layer=lay, halo=halo, src_mode=v.src_mode,
-                        act=ACT[lay.activation], in_c_off=v.c_off, in_c_total=v.c_total, out_c_off=0,
-                        out_c_total=lay.filters, out_shape=(lay.filters, ho, wo)))
-              views[t.uid] = View(dst, 0, lay.filters, lay.filters, ho, wo)
-        elif isinstance(lay, L.Conv2DTranspose):
-            # keras Conv2DTranspose(strides=2) (csrc/tconv.hip): the 4 output phases are stride-1 cross-correlations of the layer's
-            # input (zero halo T - 1, T = ceil(k / 2)) with kernels that are a permutation of the layer's own (stored with the
-            # 3 x 3 / 5 x 5 taps the matrix-core kernels exist for, zero taps and a wider zero halo around: tconv_taps), so it runs as
-            # 'tphasew' (kernel -> derived kernel; plan.phase_params) + ONE convolution with 4 x filters channels (bias and
-            # activation in its epilogue) + 'd2sc', an interleave that also crops ('same' padding, the extra row / column of an odd
-            # kernel).  An inference plan lets the convolution store the phases interleaved where a kernel can and nothing is cropped.
-            if any(p['layer'] is lay for p in plan.phase_params):
-                raise NotImplementedError('%s: a Conv2DTranspose layer applied more than once is not implemented' % lay.name)
-            v = ins[0]
-            if v.shape is not None:
-                raise NotImplementedError('%s (Conv2DTranspose) on a reshaped (non-3D) tensor %r' % (lay.name, v.shape))
-            if v.src_mode != SRC_DIRECT:         # (its convolution reads a stored tensor; a halo in front may stay lazy)
-                v = materialize(v.copy(halo=NO_HALO)).copy(halo=v.halo)
-            kh, kw = lay.kernel_size
-            th, tw = (kh + 1) // 2, (kw + 1) // 2
-            sh, sw = tconv_taps(th, tw)
-            oh, ow = (sh - th) // 2, (sw - tw) // 2             # where the Th x Tw block sits in the stored taps
-            own = ((th - 1 + oh, th - 1 + sh - th - oh), (tw - 1 + ow, tw - 1 + sw - tw - ow))
-            halo = _compose_halo(v.halo, own, PAD_ZERO)
-            if halo is None:
-                v = materialize(v)
-                halo = Halo(own[0][0], own[0][1], own[1][0], own[1][1], PAD_ZERO, PAD_ZERO)
-            _, hl, wl = v.copy(halo=halo).logical
-            hp, wp = hl - sh + 1, wl - sw + 1                   # the phase tensor: (4F, h + Th - 1, w + Tw - 1)
-            hin, win = hp - th + 1, wp - tw + 1                 # what the layer sees as its input
-            same = lay.padding == 'same'
-            top, left = (max(kh - 2, 0) // 2, max(kw - 2, 0) // 2) if same else (0, 0)
-            ho = 2 * hin + (0 if same else max(kh - 2, 0))
-            wo = 2 * win + (0 if same else max(kw - 2, 0))
-            f = lay.filters
-            alg = 2 * hin * win * f * v.c * kh * kw
-            pidx = len(plan.phase_params)
-            plan.phase_params.append({'layer': lay, 'w2_shape': (sh, sw, v.c, 4 * f), 'bias': lay.use_bias, 'kind': 'tconv'})
-            emit(PlanOp('tphasew', STATE_IN, STATE_IN, (v.c, 0, 0), layer=lay, wparam=pidx, out_shape=(0, 0, 0)))
-            if outs:
-                dst = OUT(outs[0])
-                plan.output_store[outs[0]] = (f, ho, wo)
-            else:
-                dst = plan.new_buffer(f, ho, wo)
-            no_crop = top == 0 and left == 0 and ho == 2 * hp and wo == 2 * wp
-            fold = (inference and fuse_d2s and no_crop and
-                    _supports_out_d2s((v.c, v.h, v.w), 4 * f, (sh, sw), halo, ACT[lay.activation], v.c_off, v.c_total))
-            if fold:             # the convolution's epilogue stores the phases interleaved: no interleave pass
-                op = PlanOp('conv', v.buf, dst, (v.c, v.h, v.w), layer=lay, halo=halo, src_mode=SRC_DIRECT,
-                            act=ACT[lay.activation], in_c_off=v.c_off, in_c_total=v.c_total, out_c_off=0, out_c_total=f,
-                            out_shape=(f, ho, wo), dil=(1, 1), ksize=(sh, sw), filters=4 * f, wparam=pidx, alg_flops=alg,
-                            out_d2s=True)
-                op.conv_out_shape = (4 * f, hp, wp)
-                emit(op)
-            else:
-                tmp = plan.new_buffer(4 * f, hp, wp)
-                emit(PlanOp('conv', v.buf, tmp, (v.c, v.h, v.w), layer=lay, halo=halo, src_mode=SRC_DIRECT,
-                            act=ACT[lay.activation], in_c_off=v.c_off, in_c_total=v.c_total, out_c_off=0, out_c_total=4 * f,
-                            out_shape=(4 * f, hp, wp), dil=(1, 1), ksize=(sh, sw), filters=4 * f, wparam=pidx, alg_flops=alg))
-                emit(PlanOp('d2sc', tmp, dst, (f, hp, wp), layer=lay, act=ACT[lay.activation], crop=(top, left), out_c_off=0,
-                            out_c_total=f, out_shape=(f, ho, wo)))
-            views[t.uid] = View(dst, 0, f, f, ho, wo)
-        elif isinstance(lay, L.Cropping2D):
-            # keras Cropping2D: one launch of its own on a whole stored buffer (the adjoint of zero padding) -- or, directly behind
-            # a Conv2DTranspose whose interleave nothing else reads, a smaller window of that interleave (moves only: same bits)
-            v = ins[0]
-            if v.shape is not None:
-                raise NotImplementedError('%s (Cropping2D) on a reshaped (non-3D) tensor %r' % (lay.name, v.shape))
-            (ct, cb), (cl, cr) = lay.cropping
-            v = materialize(v)
-            if not v.full:
-                v = materialize(v, dst=plan.new_buffer(*v.logical))
-            ho, wo = v.h - ct - cb, v.w - cl - cr
-            if ho <= 0 or wo <= 0:
-                raise ValueError('%s (Cropping2D): cropping %r leaves nothing of %d x %d' % (lay.name, lay.cropping, v.h, v.w))
-            writers = [op for op in plan.ops if op.dst == v.buf]
-            w0 = writers[0] if len(writers) == 1 else None
-            if (w0 is not None and w0.kind == 'd2sc' and v.buf >= 0 and consumers[t.inputs[0].uid] == 1 and
-                    not out_index.get(t.inputs[0].uid) and not any(op.src == v.buf for op in plan.ops)):
-                w0.crop = (w0.crop[0] + ct, w0.crop[1] + cl)
-                w0.out_shape = (v.c, ho, wo)
-                if outs:                             # the interleave writes the model's output slot itself
-                    w0.dst = OUT(outs[0])
-                    plan.output_store[outs[0]] = (v.c, ho, wo)
-                else:
-                    plan.buffers[v.buf] = (v.c, ho, wo)
-                views[t.uid] = View(w0.dst, 0, v.c, v.c, ho, wo)
-            else:
-                if outs:
-                    dst = OUT(outs[0])
-                    plan.output_store[outs[0]] = (v.c, ho, wo)
-                else:
-                    dst = plan.new_buffer(v.c, ho, wo)
-                emit(PlanOp('crop', v.buf, dst, (v.c, v.h, v.w), halo=Halo(ct, cb, cl, cr, PAD_ZERO, PAD_ZERO), out_c_total=v.c,
-                            out_shape=(v.c, ho, wo)))
-                views[t.uid] = View(dst, 0, v.c, v.c, ho, wo)
-        elif isinstance(lay, L.RowConnected2D):
-            # DLWP.custom.RowConnected2D (reference custom.py:695-837): per-row filters, dlwp_rowconv2d_fwd.  Its kernels read a
-            # stored float32 tensor, directly or 2x up-sampled (a lazy pooling in front is materialised); the halo stays in the
-            # loader.
-            v = ins[0]
-            if v.shape is not None and len(v.shape) != 3:
-                raise NotImplementedError('%s on a non-3D tensor %r' % (lay.name, v.shape))
-            if v.src_mode == SRC_MAXPOOL2:           # (a 2x up-sampling in front is resolved by the row kernels' loaders)
-                v = materialize(v.copy(halo=NO_HALO)).copy(halo=v.halo)
-            _, hl, wl = v.logical
-            kh, kw = lay.kernel_size
-            ho, wo = hl - kh + 1, wl - kw + 1
-            if tuple(lay.kernel.shape) != (ho, kh, kw, v.c, lay.filters):
-                raise ValueError('%s: kernel %r does not fit the input (%d rows of output, %d channels)' %
-                                 (lay.name, tuple(lay.kernel.shape), ho, v.c))
-            if outs:
-                dst = OUT(outs[0])
-                plan.output_store[outs[0]] = (lay.filters, ho, wo)
-            else:
-                dst = plan.new_buffer(lay.filters, ho, wo)
-            emit(PlanOp('rowconv', v.buf, dst, (v.c, v.h, v.w), layer=lay, halo=v.halo, src_mode=v.src_mode,
-                        act=ACT[lay.activation], in_c_off=v.c_off, in_c_total=v.c_total, out_c_off=0,
-                        out_c_total=lay.filters, out_shape=(lay.filters, ho, wo)))
-            views[t.uid] = View(dst, 0, lay.filters, lay.filters, ho, wo)
-        elif isinstance(lay, L.BatchNormalization):
-            # keras BatchNormalization(axis=1) (csrc/batchnorm.hip): its input is materialised as a whole buffer (the statistics
-            # pass reads it, and the training plan keeps it for the backward); its output is a new buffer, so nothing lazy and no
-            # epilogue of the convolution in front (pooled store, pooled weight gradient) carries a value across it
-            if lay in plan.bn_layers:
-                raise NotImplementedError('%s: a BatchNormalization layer applied more than once is not implemented' % lay.name)
-            v = ins[0]
-            if v.shape is not None and len(v.shape) != 3:
-                raise NotImplementedError('%s on a non-3D tensor %r' % (lay.name, v.shape))
-            v = materialize(v)
-            if not v.full:
-                v = materialize(v, dst=plan.new_buffer(*v.logical))
-            if outs:
-                dst = OUT(outs[0])
-                plan.output_store[outs[0]] = (v.c, v.h, v.w)
-            else:
-                dst = plan.new_buffer(v.c, v.h, v.w)
-            plan.bn_layers.append(lay)
-            emit(PlanOp('bn', v.buf, dst, (v.c, v.h, v.w), layer=lay, out_c_total=v.c, out_shape=(v.c, v.h, v.w)))
-            views[t.uid] = View(dst, 0, v.c, v.c, v.h, v.w)
-        elif isinstance(lay, L.Flatten):
-            # keras Flatten (default data_format): the contiguous per-sample block read as one row -- a view, no launch.  The
-            # buffer keeps its stored shape (what its producer and that producer's backward know); only the logical shape changes.
-            v = materialize(ins[0])
-            if not v.full:
-                v = materialize(v, dst=plan.new_buffer(*v.logical))
-            views[t.uid] = v.copy(shape=tuple(t.shape))
-        elif isinstance(lay, L.Dense):
-            # keras Dense (csrc/dense.hip): reads a whole stored buffer as (n, k) rows, writes (n, units)
-            if lay in plan.dense_layers:
-                raise NotImplementedError('%s: a Dense layer applied more than once is not implemented' % lay.name)
-            v = materialize(ins[0])
-            if not v.full:
-                v = materialize(v, dst=plan.new_buffer(*v.logical))
-            if lay.kernel is not None and v.c * v.h * v.w != int(lay.kernel.shape[0]):
-                raise ValueError('%s: kernel for %d features on an input of %d' % (lay.name, lay.kernel.shape[0], v.c * v.h * v.w))
-            if outs:
-                dst = OUT(outs[0])
-                plan.output_store[outs[0]] = (lay.units, 1, 1)
-            else:
-                dst = plan.new_buffer(lay.units, 1, 1)
-            plan.dense_layers.append(lay)
-            emit(PlanOp('dense', v.buf, dst, (v.c, v.h, v.w), layer=lay, act=ACT[lay.activation], out_c_total=lay.units,
-                        out_shape=(lay.units, 1, 1)))
-            views[t.uid] = View(dst, 0, lay.units, lay.units, 1, 1, shape=tuple(t.shape))
-        elif isinstance(lay, L.Dropout):
-            # keras Dropout: the identity outside training -- an inference plan passes the view on.  The training plan gives it a
-            # launch and a buffer of its own (the executor runs it as a copy when the forward is not a training step's).
-            if lay in plan.dropout_layers:
-                raise NotImplementedError('%s: a Dropout layer applied more than once is not implemented' % lay.name)
-            plan.dropout_layers.append(lay)
-            if inference:
-                views[t.uid] = ins[0]
-            else:
-                shp = ins[0].shape
-                v = materialize(ins[0])
-                if not v.full:
-                    v = materialize(v, dst=plan.new_buffer(*v.logical))
-                if outs:
-                    dst = OUT(outs[0])
-                    plan.output_store[outs[0]] = (v.c, v.h, v.w)
-                else:
-                    dst = plan.new_buffer(v.c, v.h, v.w)
-                emit(PlanOp('dropout', v.buf, dst, (v.c, v.h, v.w), layer=lay, out_c_total=v.c, out_shape=(v.c, v.h, v.w)))
-                views[t.uid] = View(dst, 0, v.c, v.c, v.h, v.w, shape=shp)
-        elif isinstance(lay, L._ActivationLayer):
-            # keras activation layers (csrc/eltwise.hip): 'linear' passes the view on; every other kind reads its input as a whole
-            # flat buffer (materialised like BatchNormalization's: the training plan keeps it, the backward takes f' from it) and
-            # writes a new buffer or the model's output slot.  Nothing lazy crosses the layer, and no state: the same layer object
-            # may appear in any number of ops.
-            if lay.eltwise is None:
-                views[t.uid] = ins[0].copy()
-            else:
-                shp = ins[0].shape
-                v = materialize(ins[0])
-                if not v.full:
-                    v = materialize(v, dst=plan.new_buffer(*v.logical))
-                if outs:
-                    dst = OUT(outs[0])
-                    plan.output_store[outs[0]] = (v.c, v.h, v.w)
-                else:
-                    dst = plan.new_buffer(v.c, v.h, v.w)
-                if lay not in plan.eltwise_layers:
-                    plan.eltwise_layers.append(lay)
-                emit(PlanOp('act', v.buf, dst, (v.c, v.h, v.w), layer=lay, out_c_total=v.c, out_shape=(v.c, v.h, v.w)))
-                views[t.uid] = View(dst, 0, v.c, v.c, v.h, v.w, shape=shp)
-        elif isinstance(lay, L._Merge):
-            # keras merge layers (csrc/eltwise.hip): 2 to 4 whole flat buffers of one size -> a new buffer or the output slot
-            shp = ins[0].shape
-            vs = []
-            for v in ins:
-                v = materialize(v)
-                if not v.full:
-                    v = materialize(v, dst=plan.new_buffer(*v.logical))
-                vs.append(v)
-            v0 = vs[0]
-            if any(v.c * v.h * v.w != v0.c * v0.h * v0.w for v in vs):
-                raise ValueError('%s: inputs of different sizes' % lay.name)
-            if outs:
-                dst = OUT(outs[0])
-                plan.output_store[outs[0]] = (v0.c, v0.h, v0.w)
-            else:
-                dst = plan.new_buffer(v0.c, v0.h, v0.w)
-            if lay not in plan.eltwise_layers:
-                plan.eltwise_layers.append(lay)
-            emit(PlanOp('merge', v0.buf, dst, (v0.c, v0.h, v0.w), layer=lay, aux=tuple(v.buf for v in vs[1:]), out_c_total=v0.c,
-                        out_shape=(v0.c, v0.h, v0.w)))
-            views[t.uid] = View(dst, 0, v0.c, v0.c, v0.h, v0.w, shape=shp)
+    def whole(self, v):
+        """the view as a whole stored buffer: anything lazy in front is materialised, a channel window is extracted"""
+        v = self.materialize(v)
+        if not v.full:
+            v = self.materialize(v, dst=self.plan.new_buffer(*v.logical))
+        return v
+
+    def with_zero_halo(self, v, pads):
+        """(v, halo): a layer's own zero halo ((t, b), (l, r)) composed with the lazy halo of its input; where the two do not
+        compose, the input is materialised and the halo starts afresh"""
+        halo = _compose_halo(v.halo, pads, PAD_ZERO)
+        if halo is None:
+            v = self.materialize(v)
+            halo = Halo(pads[0][0], pads[0][1], pads[1][0], pads[1][1], PAD_ZERO, PAD_ZERO)
+        return v, halo
+
+    @staticmethod
+    def check_wrap(lay, halo, hh, ww):
+        if halo.mode_h == PAD_WRAP and max(halo.top, halo.bottom) > hh:
+            raise ValueError('%s: periodic row padding exceeds the input height %d' % (lay.name, hh))
+        if halo.mode_w == PAD_WRAP and max(halo.left, halo.right) > ww:
+            raise ValueError('%s: periodic column padding exceeds the input width %d' % (lay.name, ww))
+
+    def derived_kernel(self, op_kind, lay, cin, w2_shape, bias, halo=NO_HALO, **entry):
+        """A convolution restated on a derived kernel: the plan.phase_params entry and the op that fills it ('phasew' / 'tphasew' /
+        'sphasew'); returns the entry's index, the wparam of the convolution"""
+        pidx = len(self.plan.phase_params)
+        self.plan.phase_params.append(dict({'layer': lay, 'w2_shape': w2_shape, 'bias': bias}, **entry))
+        self.emit(PlanOp(op_kind, STATE_IN, STATE_IN, (cin, 0, 0), layer=lay, wparam=pidx, halo=halo, out_shape=(0, 0, 0)))
+        return pidx
+
+    def phase_conv(self, lay, v, outs, halo, taps, pidx, alg, phase_hw, out_hw, crop=None):
+        """The tail of a layer restated as ONE convolution with 4 x filters phase channels on derived kernels: the convolution
+        stores the phases interleaved itself (out_d2s: inference plans, where a kernel can and nothing is cropped) or writes a
+        temporary that 'd2s' (crop=None: an up-sampled Conv2D) / 'd2sc' (crop=(top, left): a Conv2DTranspose) interleaves.
+        Returns the destination.  The destination is allocated in front of the temporary (buffer numbers: see the class)."""
+        f, (hp, wp), (ho, wo), act = lay.filters, phase_hw, out_hw, ACT[lay.activation]
+        dst = self.out_or_new(outs, (f, ho, wo))
+        no_crop = crop is None or (crop[0] == 0 and crop[1] == 0 and ho == 2 * hp and wo == 2 * wp)
+        fold = (self.inference and self.fuse_d2s and no_crop and
+                _supports_out_d2s((v.c, v.h, v.w), 4 * f, taps, halo, act, v.c_off, v.c_total))
+        conv = dict(layer=lay, halo=halo, src_mode=SRC_DIRECT, act=act, in_c_off=v.c_off, in_c_total=v.c_total, out_c_off=0,
+                    dil=(1, 1), ksize=taps, filters=4 * f, wparam=pidx, alg_flops=alg)
+        if fold:                 # the convolution's epilogue stores the phases interleaved: no interleave pass
+            self.emit(PlanOp('conv', v.buf, dst, (v.c, v.h, v.w), out_c_total=f, out_shape=(f, ho, wo), out_d2s=True,
+                             conv_out_shape=(4 * f, hp, wp), **conv))
+            return dst
+        tmp = self.plan.new_buffer(4 * f, hp, wp)
+        self.emit(PlanOp('conv', v.buf, tmp, (v.c, v.h, v.w), out_c_total=4 * f, out_shape=(4 * f, hp, wp), **conv))
+        if crop is None:
+            self.emit(PlanOp('d2s', tmp, dst, (f, hp, wp), out_c_off=0, out_c_total=f, out_shape=(f, ho, wo)))
         else:
-            raise NotImplementedError('layer %s (%s) has no HIP lowering' % (lay.name, type(lay).__name__))
+            self.emit(PlanOp('d2sc', tmp, dst, (f, hp, wp), layer=lay, act=act, crop=crop, out_c_off=0, out_c_total=f,
+                             out_shape=(f, ho, wo)))
+        return dst
 
-        # a model output that was not produced in place by a conv / concatenate: materialise it into its slot
+    # -- one method per row of _LOWERINGS ---------------------------------------------------------------------------------------- #
+    def lower_pad2d(self, t, lay, ins, outs):
+        plan = self.plan
+        v = ins[0]
+        if v.shape is not None:
+            raise NotImplementedError('%s on a reshaped (non-3D) tensor' % lay.name)
+        if lay.data_format == 'channels_last':
+            # standalone only: buffer holds (H, W, C) per sample, rows of W*C floats
+            v = self.materialize(v)
+            hh, ww, cc = t.inputs[0].shape
+            (tp, bt), (lf, rt) = lay.padding
+            nb = plan.new_buffer(hh + tp + bt, ww + lf + rt, cc)
+            self.emit(PlanOp('pad', v.buf, nb, (1, hh, ww), halo=Halo(tp, bt, lf, rt, lay.mode, lay.mode), inner=cc,
+                             out_shape=(hh + tp + bt, ww + lf + rt, cc)))
+            self.views[t.uid] = View(nb, 0, hh + tp + bt, hh + tp + bt, ww + lf + rt, cc)
+            self.views[t.uid].shape = tuple(t.shape)
+        else:
+            halo = _compose_halo(v.halo, lay.padding, lay.mode)
+            if halo is None:
+                v = self.materialize(v)
+                halo = _compose_halo(NO_HALO, lay.padding, lay.mode)
+            self.check_wrap(lay, halo, *v.src_hw)
+            self.views[t.uid] = v.copy(halo=halo)
+
+    def lower_pad3d(self, t, lay, ins, outs):
+        # (T, C, H, W) stored as (T*C, H, W): a 3-D pad that leaves the first (channel) axis alone is the 2-D halo
+        v = ins[0]
+        if lay.data_format != 'channels_first':
+            raise NotImplementedError("%s: data_format='channels_first' is required" % lay.name)
+        if lay.padding[0] != (0, 0):
+            raise NotImplementedError('%s: padding of the first (channel) axis %r is not lowered to the HIP path'
+                                      % (lay.name, lay.padding[0]))
+        pad2 = (lay.padding[1], lay.padding[2])
+        halo = _compose_halo(v.halo, pad2, lay.mode)
+        if halo is None:
+            shp = v.shape
+            v = self.materialize(v)
+            v.shape = shp
+            halo = _compose_halo(NO_HALO, pad2, lay.mode)
+        self.check_wrap(lay, halo, *v.src_hw)
+        self.views[t.uid] = v.copy(halo=halo, shape=tuple(t.shape))
+
+    def lower_convlstm(self, t, lay, ins, outs):
+        """geometry, buffers and which launches run a step; the steps themselves: lstm_step_plain / _fused / _whole"""
+        plan = self.plan
+        v = ins[0]
+        t_len, cin = t.inputs[0].shape[0], t.inputs[0].shape[1]
+        if v.c != t_len * cin:
+            raise ValueError('%s: input view has %d channels, expected T*C = %d' % (lay.name, v.c, t_len * cin))
+        halo = v.halo
+        if lay.padding == 'same':
+            st, sb, sl, sr = lay.same_halo()
+            v, halo = self.with_zero_halo(v, ((st, sb), (sl, sr)))
+        _, hl, wl = v.copy(halo=halo).logical
+        ho = hl - lay.dilation_rate[0] * (lay.kernel_size[0] - 1)
+        wo = wl - lay.dilation_rate[1] * (lay.kernel_size[1] - 1)
+        f = lay.filters
+        hbuf = plan.new_buffer(t_len * f, ho, wo)           # h_0 .. h_{T-1}, the return_sequences output
+        # every step keeps its own pre-activations and cell state: they are the saved activations of the backward
+        # pass (dlwp_convlstm_gates_bwd) -- T is the reference's time_dim (2), so this costs little
+        cbufs = [plan.new_buffer(f, ho, wo) for _ in range(t_len)]
+        rk = ((lay.kernel_size[0] - 1) // 2, (lay.kernel_size[1] - 1) // 2)
+        act, rec_code = ACT[lay.activation], {'hard_sigmoid': 0, 'sigmoid': 1}[lay.recurrent_activation]
+        rhalo = Halo(rk[0], rk[0], rk[1], rk[1], PAD_ZERO, PAD_ZERO)
+        # bfloat16 inference: the convolution that completes a step's pre-activations applies the cell update in its
+        # epilogue (the input convolution on the first step, the recurrent one afterwards): z_h (z_x on the first step)
+        # is never stored and the gate kernel disappears.  The model input feeds the input convolution as float32.
+        fused = (self.inference and self.fuse_lstm and v.buf == STATE_IN and
+                 _supports_lstm_conv((cin, v.h, v.w), lay.input_part, halo, v.src_mode, act, rec_code, f,
+                                     v.c_off, v.c_total, 0, t_len * f, False) and
+                 (t_len == 1 or _supports_lstm_conv((f, ho, wo), lay.recurrent_part, rhalo, SRC_DIRECT, act,
+                                                    rec_code, f, 0, t_len * f, f, t_len * f, True)))
+        # ... and every later step as ONE launch where the library has the dual-source instance (octet layout; the executor
+        # falls back to the two launches when it cannot keep the h sequence in octets)
+        whole = (fused and self.fuse_lstm_step and t_len > 1 and os.environ.get('DLWP_LSTM_STEP', '1') != '0' and
+                 _supports_lstm_step(lay, f, ho, wo, t_len, cin, v, halo, act, rec_code))
+        zxs = [None if (fused and (step == 0 or whole)) else plan.new_buffer(4 * f, ho, wo) for step in range(t_len)]
+        zhs = [None] + [None if fused else plan.new_buffer(4 * f, ho, wo) for _ in range(t_len - 1)]
+        g = _LstmSteps(lay, v, halo, rhalo, cin, f, ho, wo, t_len, hbuf, cbufs, zxs, zhs, act, rec_code)
+        for step in range(t_len):
+            if not fused:
+                self.lstm_step_plain(g, step)
+            elif whole and step > 0:
+                self.lstm_step_whole(g, step)
+            else:
+                self.lstm_step_fused(g, step)
+        if lay.return_sequences:
+            self.views[t.uid] = View(hbuf, 0, t_len * f, t_len * f, ho, wo, shape=(t_len, f, ho, wo))
+        else:
+            self.views[t.uid] = View(hbuf, (t_len - 1) * f, f, t_len * f, ho, wo)
+
+    def lstm_input_conv(self, g, step):
+        """z_x of a step: the input convolution into the step's own pre-activation buffer"""
+        v, f = g.v, g.f
+        self.emit(PlanOp('conv', v.buf, g.zxs[step], (g.cin, v.h, v.w), layer=g.lay.input_part, halo=g.halo,
+                         src_mode=v.src_mode, act=0, in_c_off=v.c_off + step * g.cin, in_c_total=v.c_total, out_c_off=0,
+                         out_c_total=4 * f, out_shape=(4 * f, g.ho, g.wo)))
+
+    def lstm_step_plain(self, g, step):
+        """z_x, z_h (from the second step on) and the gate kernel"""
+        f, ho, wo, t_len = g.f, g.ho, g.wo, g.t_len
+        self.lstm_input_conv(g, step)
+        if step > 0:
+            self.emit(PlanOp('conv', g.hbuf, g.zhs[step], (f, ho, wo), layer=g.lay.recurrent_part, halo=g.rhalo,
+                             src_mode=SRC_DIRECT, act=0, in_c_off=(step - 1) * f, in_c_total=t_len * f, out_c_off=0,
+                             out_c_total=4 * f, out_shape=(4 * f, ho, wo)))
+        self.emit(PlanOp('lstm', g.zxs[step], g.hbuf, (f, ho, wo), act=g.act, rec_act=g.rec,
+                         aux=(g.zhs[step], g.cbufs[step - 1] if step > 0 else None, g.cbufs[step]),
+                         out_c_off=step * f, out_c_total=t_len * f, out_shape=(f, ho, wo)))
+
+    def lstm_step_fused(self, g, step):
+        """the cell update in the epilogue of the convolution that completes the pre-activations: the input convolution on the
+        first step, the recurrent one (behind a stored z_x) afterwards"""
+        v, f, ho, wo, t_len = g.v, g.f, g.ho, g.wo, g.t_len
+        if step == 0:
+            self.emit(PlanOp('conv', v.buf, g.hbuf, (g.cin, v.h, v.w), layer=g.lay.input_part, halo=g.halo, src_mode=v.src_mode,
+                             act=g.act, rec_act=g.rec, lstm_f=f, aux=(None, None, g.cbufs[0]),
+                             in_c_off=v.c_off, in_c_total=v.c_total, out_c_off=0, out_c_total=t_len * f,
+                             out_shape=(f, ho, wo)))
+            return
+        self.lstm_input_conv(g, step)
+        self.emit(PlanOp('conv', g.hbuf, g.hbuf, (f, ho, wo), layer=g.lay.recurrent_part, halo=g.rhalo, src_mode=SRC_DIRECT,
+                         act=g.act, rec_act=g.rec, lstm_f=f, aux=(g.zxs[step], g.cbufs[step - 1], g.cbufs[step]),
+                         in_c_off=(step - 1) * f, in_c_total=t_len * f, out_c_off=step * f, out_c_total=t_len * f,
+                         out_shape=(f, ho, wo)))
+
+    def lstm_step_whole(self, g, step):
+        """a step t >= 1 as ONE launch: the recurrent convolution with the cell update; src2 = the step's input convolution"""
+        v, f, ho, wo, t_len = g.v, g.f, g.ho, g.wo, g.t_len
+        self.emit(PlanOp('conv', g.hbuf, g.hbuf, (f, ho, wo), layer=g.lay.recurrent_part, halo=g.rhalo, src_mode=SRC_DIRECT,
+                         act=g.act, rec_act=g.rec, lstm_f=f, aux=(None, g.cbufs[step - 1], g.cbufs[step]),
+                         in_c_off=(step - 1) * f, in_c_total=t_len * f, out_c_off=step * f, out_c_total=t_len * f,
+                         out_shape=(f, ho, wo),
+                         src2={'buf': v.buf, 'xs': (g.cin, v.h, v.w), 'layer': g.lay.input_part, 'halo': g.halo,
+                               'in_c_off': v.c_off + step * g.cin, 'in_c_total': v.c_total}))
+
+    def lower_bilinear(self, t, lay, ins, outs):
+        # keras UpSampling2D(2, interpolation='bilinear') (csrc/halo.hip): always one launch of its own on a whole stored
+        # buffer -- anything lazy in front is materialised, a channel window is extracted first -- into a new buffer or the
+        # model's output slot.  Never SRC_UPSAMPLE2, never a restated decoder layer and never a convolution's epilogue: the
+        # convolution kernels know nearest up-sampling only.
+        v = ins[0]
+        if v.shape is not None:
+            raise NotImplementedError('%s on a reshaped tensor' % lay.name)
+        v = self.whole(v)
+        h2, w2 = 2 * v.h, 2 * v.w
+        dst = self.out_or_new(outs, (v.c, h2, w2))
+        self.emit(PlanOp('bilinear', v.buf, dst, (v.c, v.h, v.w), out_c_total=v.c, out_shape=(v.c, h2, w2)))
+        self.views[t.uid] = View(dst, 0, v.c, v.c, h2, w2)
+
+    def lower_pool_or_upsample(self, t, lay, ins, outs):
+        """MaxPooling2D(2) / nearest UpSampling2D(2): a lazy source mode of the view -- or, in an inference plan, the epilogue of the
+        convolution whose only consumer the pooling is"""
+        v = ins[0]
+        if v.shape is not None:
+            raise NotImplementedError('%s on a reshaped tensor' % lay.name)
+        if not v.plain:
+            v = self.materialize(v)
+        prod = self.producer.get(v.buf) if (self.inference and isinstance(lay, L.MaxPooling2D) and v.full and not outs) else None
+        if (prod is not None and self.consumers[t.inputs[0].uid] == 1 and not isinstance(prod.layer, L._ConvPart)
+                and not prod.out_pool and _supports_out_pool(prod)):
+            # the pooling runs in the producing convolution's epilogue: its buffer now holds the pooled tensor
+            prod.out_pool = True
+            c, h2, w2 = v.c, v.h // 2, v.w // 2
+            prod.conv_out_shape = prod.out_shape        # what the convolution computes (FLOP accounting)
+            prod.out_shape = (c, h2, w2)                # what it stores
+            self.plan.buffers[v.buf] = (c, h2, w2)
+            self.views[t.uid] = View(v.buf, 0, c, c, h2, w2)
+        else:
+            self.views[t.uid] = v.copy(src_mode=SRC_MAXPOOL2 if isinstance(lay, L.MaxPooling2D) else SRC_UPSAMPLE2)
+
+    def lower_avgpool(self, t, lay, ins, outs):
+        # keras AveragePooling2D(2) (csrc/halo.hip): always one launch of its own on a whole stored buffer -- anything lazy in
+        # front is materialised, a channel window is extracted first -- into a new buffer or the model's output slot.  Never a
+        # lazy source mode and never a convolution's epilogue: the convolution kernels know max-pooling only.
+        v = ins[0]
+        if v.shape is not None:
+            raise NotImplementedError('%s on a reshaped tensor' % lay.name)
+        v = self.whole(v)
+        h2, w2 = v.h // 2, v.w // 2
+        dst = self.out_or_new(outs, (v.c, h2, w2))
+        self.emit(PlanOp('avgpool', v.buf, dst, (v.c, v.h, v.w), out_c_total=v.c, out_shape=(v.c, h2, w2)))
+        self.views[t.uid] = View(dst, 0, v.c, v.c, h2, w2)
+
+    def lower_slice(self, t, lay, ins, outs):
+        v = ins[0]
+        if v.shape is not None:
+            raise NotImplementedError('slice_layer on a reshaped tensor')
+        lo, hi = lay.window(v.c)
+        self.views[t.uid] = v.copy(c_off=v.c_off + lo, c=hi - lo)
+
+    def lower_reshape(self, t, lay, ins, outs):
+        plan = self.plan
+        v = self.whole(ins[0])
+        c, h, w = _store_of(t.shape)
+        if (c * h * w) != v.c * v.h * v.w:
+            raise ValueError('Reshape size mismatch')
+        # relabel the same contiguous block
+        if v.buf >= 0:
+            plan.buffers[v.buf] = (c, h, w)
+            self.views[t.uid] = View(v.buf, 0, c, c, h, w, shape=tuple(t.shape) if len(t.shape) != 3 else None)
+        else:
+            nb = plan.new_buffer(v.c, v.h, v.w)
+            self.emit(PlanOp('copy', v.buf, nb, (v.c, v.h, v.w), in_c_total=v.c, out_c_total=v.c,
+                             out_shape=(v.c, v.h, v.w)))
+            plan.buffers[nb] = (c, h, w)
+            self.views[t.uid] = View(nb, 0, c, c, h, w, shape=tuple(t.shape) if len(t.shape) != 3 else None)
+
+    def lower_concatenate(self, t, lay, ins, outs):
+        c_tot = sum(v.logical[0] for v in ins)
+        _, hh, ww = ins[0].logical
+        dst = self.out_or_new(outs, (c_tot, hh, ww))
+        off = 0
+        for v in ins:
+            self.materialize(v, dst=dst, dst_c_off=off, dst_c_total=c_tot)
+            off += v.logical[0]
+        self.views[t.uid] = View(dst, 0, c_tot, c_tot, hh, ww)
+
+    def lower_strided_conv(self, t, lay, ins, outs):
+        # keras Conv2D(strides=2) (csrc/sconv.hip): a stride-1 'valid' convolution of the space-to-depth image P of the padded
+        # input (4 cin phase-major channels) with a kernel that is a permutation of the layer's own, stored with the 3 x 3 /
+        # 5 x 5 taps the matrix-core kernels exist for (tconv_taps; the T x T block at the origin, zero taps below / right, P
+        # that much longer).  Three ops: 'sphasew' (kernel -> derived kernel; plan.phase_params), 's2dp' (the lazy halo of the
+        # input + the layer's own 'same' zeros + the de-interleave in one pass) and ONE 'conv' on P with the layer's bias and
+        # activation in its epilogue.
+        plan = self.plan
+        if any(p['layer'] is lay for p in plan.phase_params):
+            raise NotImplementedError('%s: a Conv2D layer with strides=2 applied more than once is not implemented' % lay.name)
+        v = ins[0]
+        if v.shape is not None and len(v.shape) != 3:
+            raise NotImplementedError('%s on a non-3D tensor %r' % (lay.name, v.shape))
+        if v.src_mode != SRC_DIRECT:         # (the pass reads a stored tensor; a halo in front may stay lazy)
+            v = self.materialize(v.copy(halo=NO_HALO)).copy(halo=v.halo)
+        _, hl, wl = v.logical                                   # what the layer sees as its input
+        (th, pt, pb, ho), (tw, pl, pr, wo) = lay.strided_geometry(hl, wl)
+        v, halo = self.with_zero_halo(v, ((pt, pb), (pl, pr)))
+        kh, kw = lay.kernel_size
+        sh, sw = tconv_taps(th, tw)
+        hp, wp = ho + sh - 1, wo + sw - 1                       # the phase tensor the stored taps read
+        f = lay.filters
+        alg = 2 * ho * wo * f * v.c * kh * kw
+        pidx = self.derived_kernel('sphasew', lay, v.c, (sh, sw, 4 * v.c, f), False, kind='sconv')
+        # the phase tensor in front of the destination (buffer numbers), and one convolution with `filters` channels that reads
+        # it: no phase channels and no interleave, so not phase_conv
+        tmp = plan.new_buffer(4 * v.c, hp, wp)
+        self.emit(PlanOp('s2dp', v.buf, tmp, (v.c, v.h, v.w), halo=halo, in_c_off=v.c_off, in_c_total=v.c_total,
+                         out_c_total=4 * v.c, out_shape=(4 * v.c, hp, wp)))
+        dst = self.out_or_new(outs, (f, ho, wo))
+        self.emit(PlanOp('conv', tmp, dst, (4 * v.c, hp, wp), layer=lay, halo=NO_HALO, src_mode=SRC_DIRECT, act=ACT[lay.activation],
+                         in_c_off=0, in_c_total=4 * v.c, out_c_off=0, out_c_total=f, out_shape=(f, ho, wo), dil=(1, 1),
+                         ksize=(sh, sw), filters=f, wparam=pidx, alg_flops=alg, input_image=v.buf == STATE_IN))
+        self.producer.pop(dst, None)         # (a MaxPooling2D behind it stays a launch / a lazy source of its own)
+        self.views[t.uid] = View(dst, 0, f, f, ho, wo)
+
+    def lower_depthwise(self, t, lay, ins, outs):
+        # keras DepthwiseConv2D / SeparableConv2D (csrc/sepconv.hip): 'dwconv' = the stencil, which takes the lazy halo of its
+        # input and the layer's own 'same' zeros composed (a lazy pooling / up-sampling view is materialised first: the stencil
+        # reads a stored tensor); for a SeparableConv2D it has neither bias nor activation and writes a plan buffer that the
+        # training step keeps (the pointwise weight gradient reads it), and 'pwconv' = the 1 x 1 product on the matrix cores
+        # with the layer's bias and activation, which writes the model's output slot or a buffer of its own.
+        plan = self.plan
+        if lay in plan.sep_layers:
+            raise NotImplementedError('%s: a %s layer applied more than once is not implemented' % (lay.name, type(lay).__name__))
+        plan.sep_layers.append(lay)
+        v = ins[0]
+        if v.shape is not None and len(v.shape) != 3:
+            raise NotImplementedError('%s on a non-3D tensor %r' % (lay.name, v.shape))
+        if v.src_mode != SRC_DIRECT:
+            v = self.materialize(v.copy(halo=NO_HALO)).copy(halo=v.halo)
+        halo = v.halo
+        if lay.padding == 'same':
+            st, sb, sl, sr = lay.same_halo()
+            v, halo = self.with_zero_halo(v, ((st, sb), (sl, sr)))
+        _, hl, wl = v.copy(halo=halo).logical
+        ho = hl - lay.dilation_rate[0] * (lay.kernel_size[0] - 1)
+        wo = wl - lay.dilation_rate[1] * (lay.kernel_size[1] - 1)
+        if ho < 1 or wo < 1:
+            raise ValueError('%s: kernel %r with dilation %r does not fit the input' % (lay.name, lay.kernel_size, lay.dilation_rate))
+        q = v.c * lay.depth_multiplier
+        sep = isinstance(lay, L.SeparableConv2D)
+        f = lay.filters if sep else q
+        dst = self.out_or_new(outs, (f, ho, wo))
+        mid = plan.new_buffer(q, ho, wo) if sep else dst
+        self.emit(PlanOp('dwconv', v.buf, mid, (v.c, v.h, v.w), layer=lay, halo=halo, act=0 if sep else ACT[lay.activation],
+                         in_c_off=v.c_off, in_c_total=v.c_total, out_c_off=0, out_c_total=q, out_shape=(q, ho, wo)))
+        if sep:
+            self.emit(PlanOp('pwconv', mid, dst, (q, ho, wo), layer=lay, act=ACT[lay.activation], in_c_off=0, in_c_total=q,
+                             out_c_off=0, out_c_total=f, out_shape=(f, ho, wo)))
+        self.views[t.uid] = View(dst, 0, f, f, ho, wo)
+
+    def lower_conv2d(self, t, lay, ins, outs):
+        """the layer's geometry, then one of three forms: conv_upsampled_dilated (a), conv_upsampled_phases (b), conv_plain"""
+        v = ins[0]
+        if v.shape is not None and len(v.shape) != 3:
+            raise NotImplementedError('%s on a non-3D tensor %r' % (lay.name, v.shape))
+        if v.src_mode == SRC_MAXPOOL2 and _prefers_unfused_pool(v.c, lay):
+            # the Winograd kernels read plain tensors: pool once with the standalone kernel, keep the halo lazy
+            v = self.materialize(v.copy(halo=NO_HALO)).copy(halo=v.halo)
+        halo = v.halo
+        if lay.padding == 'same':
+            st, sb, sl, sr = lay.same_halo()
+            v, halo = self.with_zero_halo(v, ((st, sb), (sl, sr)))
+        _, hl, wl = v.copy(halo=halo).logical
+        ho = hl - lay.dilation_rate[0] * (lay.kernel_size[0] - 1)
+        wo = wl - lay.dilation_rate[1] * (lay.kernel_size[1] - 1)
+        kh, kw = lay.kernel_size
+        alg = 2 * ho * wo * lay.filters * v.c * kh * kw
+        # ---- inference: a convolution on a 2x nearest-neighbour up-sampled tensor, restated on the tensor itself: (a) and (b).
+        # both serve the training plan as well: (a) is a plain graph identity (forward, data and weight gradient of
+        # the layer then run on the low-resolution tensors); (b) trains through the adjoints of its two linear maps
+        # (dlwp_phase_weights_bwd, dlwp_space_to_depth2; training.py)
+        # (a mirror halo WITHOUT the border element -- TFPadding2D 'REFLECT' -- does not commute with the up-sampling:
+        #  up-sampled coordinate 2n reflects to source n - 1, low-resolution coordinate n to n - 2; the layer then keeps
+        #  the reference's formulation.  'SYMMETRIC', periodic, zero and edge halos commute.)
+        restate = (RESTATE_UPSAMPLED and v.src_mode == SRC_UPSAMPLE2 and
+                   halo.mode_h != PAD_REFLECT and halo.mode_w != PAD_REFLECT)
+        if (restate and tuple(lay.dilation_rate) == (2, 2) and
+                all(p % 2 == 0 for p in halo[:4]) and ho % 2 == 0 and wo % 2 == 0):
+            self.conv_upsampled_dilated(t, lay, v, halo, ho, wo, alg)
+        elif (restate and tuple(lay.dilation_rate) == (1, 1) and
+              ho == 2 * v.h and wo == 2 * v.w and
+              _phase_geometry(kh, halo.top)[0] * _phase_geometry(kw, halo.left)[0] < kh * kw):
+            self.conv_upsampled_phases(t, lay, v, outs, halo, ho, wo, alg)
+        else:
+            self.conv_plain(t, lay, v, outs, halo, ho, wo)
+
+    def conv_upsampled_dilated(self, t, lay, v, halo, ho, wo, alg):
+        # (a) dilation 2, even halo: tap u of output row 2i + a reads source row i + u - top/2 whatever a is, so the
+        #     result is UpSampling2D(conv with dilation 1 and half the halo on the low-resolution tensor): a quarter
+        #     of the multiplies, and the up-sampling stays lazy for the consumer.
+        h2 = Halo(halo.top // 2, halo.bottom // 2, halo.left // 2, halo.right // 2, halo.mode_h, halo.mode_w)
+        # (always a new buffer: the view is lazily up-sampled, so a model output is materialised from it by finish_outputs)
+        dst = self.plan.new_buffer(lay.filters, ho // 2, wo // 2)
+        self.emit(PlanOp('conv', v.buf, dst, (v.c, v.h, v.w), layer=lay, halo=h2, src_mode=SRC_DIRECT,
+                         act=ACT[lay.activation], in_c_off=v.c_off, in_c_total=v.c_total, out_c_off=0,
+                         out_c_total=lay.filters, out_shape=(lay.filters, ho // 2, wo // 2), dil=(1, 1), alg_flops=alg))
+        self.views[t.uid] = View(dst, 0, lay.filters, lay.filters, ho // 2, wo // 2, src_mode=SRC_UPSAMPLE2)
+
+    def conv_upsampled_phases(self, t, lay, v, outs, halo, ho, wo, alg):
+        # (b) dilation 1: the k taps of an axis fall on k2 < k distinct source pixels; each of the 4 output phases is
+        #     a k2 x k2 kernel of summed weights over the SAME window, so the layer runs as one convolution with
+        #     4 x filters channels on the low-resolution tensor + a depth-to-space interleave (csrc/phase.hip).
+        kh, kw = lay.kernel_size
+        (kh2, lo_h, hi_h), (kw2, lo_w, hi_w) = _phase_geometry(kh, halo.top), _phase_geometry(kw, halo.left)
+        h2 = Halo(-lo_h, hi_h, -lo_w, hi_w, halo.mode_h, halo.mode_w)
+        pidx = self.derived_kernel('phasew', lay, v.c, (kh2, kw2, v.c, 4 * lay.filters), lay.use_bias, halo=halo,
+                                   pad_top=halo.top, pad_left=halo.left)
+        dst = self.phase_conv(lay, v, outs, h2, (kh2, kw2), pidx, alg, (v.h, v.w), (ho, wo))
+        self.views[t.uid] = View(dst, 0, lay.filters, lay.filters, ho, wo)
+
+    def conv_plain(self, t, lay, v, outs, halo, ho, wo):
+        dst = self.out_or_new(outs, (lay.filters, ho, wo))
+        self.emit(PlanOp('conv', v.buf, dst, (v.c, v.h, v.w), layer=lay, halo=halo, src_mode=v.src_mode,
+                         act=ACT[lay.activation], in_c_off=v.c_off, in_c_total=v.c_total, out_c_off=0,
+                         out_c_total=lay.filters, out_shape=(lay.filters, ho, wo)))
+        self.views[t.uid] = View(dst, 0, lay.filters, lay.filters, ho, wo)
+
+    def lower_tconv(self, t, lay, ins, outs):
+        # keras Conv2DTranspose(strides=2) (csrc/tconv.hip): the 4 output phases are stride-1 cross-correlations of the layer's
+        # input (zero halo T - 1, T = ceil(k / 2)) with kernels that are a permutation of the layer's own (stored with the
+        # 3 x 3 / 5 x 5 taps the matrix-core kernels exist for, zero taps and a wider zero halo around: tconv_taps), so it runs as
+        # 'tphasew' (kernel -> derived kernel; plan.phase_params) + ONE convolution with 4 x filters channels (bias and
+        # activation in its epilogue) + 'd2sc', an interleave that also crops ('same' padding, the extra row / column of an odd
+        # kernel).  An inference plan lets the convolution store the phases interleaved where a kernel can and nothing is cropped.
+        if any(p['layer'] is lay for p in self.plan.phase_params):
+            raise NotImplementedError('%s: a Conv2DTranspose layer applied more than once is not implemented' % lay.name)
+        v = ins[0]
+        if v.shape is not None:
+            raise NotImplementedError('%s (Conv2DTranspose) on a reshaped (non-3D) tensor %r' % (lay.name, v.shape))
+        if v.src_mode != SRC_DIRECT:         # (its convolution reads a stored tensor; a halo in front may stay lazy)
+            v = self.materialize(v.copy(halo=NO_HALO)).copy(halo=v.halo)
+        kh, kw = lay.kernel_size
+        th, tw = (kh + 1) // 2, (kw + 1) // 2
+        sh, sw = tconv_taps(th, tw)
+        oh, ow = (sh - th) // 2, (sw - tw) // 2             # where the Th x Tw block sits in the stored taps
+        own = ((th - 1 + oh, th - 1 + sh - th - oh), (tw - 1 + ow, tw - 1 + sw - tw - ow))
+        v, halo = self.with_zero_halo(v, own)
+        _, hl, wl = v.copy(halo=halo).logical
+        hp, wp = hl - sh + 1, wl - sw + 1                   # the phase tensor: (4F, h + Th - 1, w + Tw - 1)
+        hin, win = hp - th + 1, wp - tw + 1                 # what the layer sees as its input
+        same = lay.padding == 'same'
+        top, left = (max(kh - 2, 0) // 2, max(kw - 2, 0) // 2) if same else (0, 0)
+        ho = 2 * hin + (0 if same else max(kh - 2, 0))
+        wo = 2 * win + (0 if same else max(kw - 2, 0))
+        f = lay.filters
+        alg = 2 * hin * win * f * v.c * kh * kw
+        pidx = self.derived_kernel('tphasew', lay, v.c, (sh, sw, v.c, 4 * f), lay.use_bias, kind='tconv')
+        dst = self.phase_conv(lay, v, outs, halo, (sh, sw), pidx, alg, (hp, wp), (ho, wo), crop=(top, left))
+        self.views[t.uid] = View(dst, 0, f, f, ho, wo)
+
+    def lower_crop(self, t, lay, ins, outs):
+        # keras Cropping2D: one launch of its own on a whole stored buffer (the adjoint of zero padding) -- or, directly behind
+        # a Conv2DTranspose whose interleave nothing else reads, a smaller window of that interleave (moves only: same bits)
+        plan = self.plan
+        v = ins[0]
+        if v.shape is not None:
+            raise NotImplementedError('%s (Cropping2D) on a reshaped (non-3D) tensor %r' % (lay.name, v.shape))
+        (ct, cb), (cl, cr) = lay.cropping
+        v = self.whole(v)
+        ho, wo = v.h - ct - cb, v.w - cl - cr
+        if ho <= 0 or wo <= 0:
+            raise ValueError('%s (Cropping2D): cropping %r leaves nothing of %d x %d' % (lay.name, lay.cropping, v.h, v.w))
+        writers = [op for op in plan.ops if op.dst == v.buf]
+        w0 = writers[0] if len(writers) == 1 else None
+        if (w0 is not None and w0.kind == 'd2sc' and v.buf >= 0 and self.consumers[t.inputs[0].uid] == 1 and
+                not self.out_index.get(t.inputs[0].uid) and not any(op.src == v.buf for op in plan.ops)):
+            w0.crop = (w0.crop[0] + ct, w0.crop[1] + cl)
+            w0.out_shape = (v.c, ho, wo)
+            if outs:                             # the interleave writes the model's output slot itself
+                w0.dst = OUT(outs[0])
+                plan.output_store[outs[0]] = (v.c, ho, wo)
+            else:
+                plan.buffers[v.buf] = (v.c, ho, wo)
+            self.views[t.uid] = View(w0.dst, 0, v.c, v.c, ho, wo)
+        else:
+            dst = self.out_or_new(outs, (v.c, ho, wo))
+            self.emit(PlanOp('crop', v.buf, dst, (v.c, v.h, v.w), halo=Halo(ct, cb, cl, cr, PAD_ZERO, PAD_ZERO), out_c_total=v.c,
+                             out_shape=(v.c, ho, wo)))
+            self.views[t.uid] = View(dst, 0, v.c, v.c, ho, wo)
+
+    def lower_rowconv(self, t, lay, ins, outs):
+        # DLWP.custom.RowConnected2D (reference custom.py:695-837): per-row filters, dlwp_rowconv2d_fwd.  Its kernels read a
+        # stored float32 tensor, directly or 2x up-sampled (a lazy pooling in front is materialised); the halo stays in the
+        # loader.
+        v = ins[0]
+        if v.shape is not None and len(v.shape) != 3:
+            raise NotImplementedError('%s on a non-3D tensor %r' % (lay.name, v.shape))
+        if v.src_mode == SRC_MAXPOOL2:           # (a 2x up-sampling in front is resolved by the row kernels' loaders)
+            v = self.materialize(v.copy(halo=NO_HALO)).copy(halo=v.halo)
+        _, hl, wl = v.logical
+        kh, kw = lay.kernel_size
+        ho, wo = hl - kh + 1, wl - kw + 1
+        if tuple(lay.kernel.shape) != (ho, kh, kw, v.c, lay.filters):
+            raise ValueError('%s: kernel %r does not fit the input (%d rows of output, %d channels)' %
+                             (lay.name, tuple(lay.kernel.shape), ho, v.c))
+        dst = self.out_or_new(outs, (lay.filters, ho, wo))
+        self.emit(PlanOp('rowconv', v.buf, dst, (v.c, v.h, v.w), layer=lay, halo=v.halo, src_mode=v.src_mode,
+                         act=ACT[lay.activation], in_c_off=v.c_off, in_c_total=v.c_total, out_c_off=0,
+                         out_c_total=lay.filters, out_shape=(lay.filters, ho, wo)))
+        self.views[t.uid] = View(dst, 0, lay.filters, lay.filters, ho, wo)
+
+    def lower_batchnorm(self, t, lay, ins, outs):
+        # keras BatchNormalization(axis=1) (csrc/batchnorm.hip): its input is materialised as a whole buffer (the statistics
+        # pass reads it, and the training plan keeps it for the backward); its output is a new buffer, so nothing lazy and no
+        # epilogue of the convolution in front (pooled store, pooled weight gradient) carries a value across it
+        if lay in self.plan.bn_layers:
+            raise NotImplementedError('%s: a BatchNormalization layer applied more than once is not implemented' % lay.name)
+        v = ins[0]
+        if v.shape is not None and len(v.shape) != 3:
+            raise NotImplementedError('%s on a non-3D tensor %r' % (lay.name, v.shape))
+        v = self.whole(v)
+        dst = self.out_or_new(outs, (v.c, v.h, v.w))
+        self.plan.bn_layers.append(lay)
+        self.emit(PlanOp('bn', v.buf, dst, (v.c, v.h, v.w), layer=lay, out_c_total=v.c, out_shape=(v.c, v.h, v.w)))
+        self.views[t.uid] = View(dst, 0, v.c, v.c, v.h, v.w)
+
+    def lower_flatten(self, t, lay, ins, outs):
+        # keras Flatten (default data_format): the contiguous per-sample block read as one row -- a view, no launch.  The
+        # buffer keeps its stored shape (what its producer and that producer's backward know); only the logical shape changes.
+        self.views[t.uid] = self.whole(ins[0]).copy(shape=tuple(t.shape))
+
+    def lower_dense(self, t, lay, ins, outs):
+        # keras Dense (csrc/dense.hip): reads a whole stored buffer as (n, k) rows, writes (n, units)
+        if lay in self.plan.dense_layers:
+            raise NotImplementedError('%s: a Dense layer applied more than once is not implemented' % lay.name)
+        v = self.whole(ins[0])
+        if lay.kernel is not None and v.c * v.h * v.w != int(lay.kernel.shape[0]):
+            raise ValueError('%s: kernel for %d features on an input of %d' % (lay.name, lay.kernel.shape[0], v.c * v.h * v.w))
+        dst = self.out_or_new(outs, (lay.units, 1, 1))
+        self.plan.dense_layers.append(lay)
+        self.emit(PlanOp('dense', v.buf, dst, (v.c, v.h, v.w), layer=lay, act=ACT[lay.activation], out_c_total=lay.units,
+                         out_shape=(lay.units, 1, 1)))
+        self.views[t.uid] = View(dst, 0, lay.units, lay.units, 1, 1, shape=tuple(t.shape))
+
+    def lower_dropout(self, t, lay, ins, outs):
+        # keras Dropout: the identity outside training -- an inference plan passes the view on.  The training plan gives it a
+        # launch and a buffer of its own (the executor runs it as a copy when the forward is not a training step's).
+        if lay in self.plan.dropout_layers:
+            raise NotImplementedError('%s: a Dropout layer applied more than once is not implemented' % lay.name)
+        self.plan.dropout_layers.append(lay)
+        if self.inference:
+            self.views[t.uid] = ins[0]
+        else:
+            shp = ins[0].shape
+            v = self.whole(ins[0])
+            dst = self.out_or_new(outs, (v.c, v.h, v.w))
+            self.emit(PlanOp('dropout', v.buf, dst, (v.c, v.h, v.w), layer=lay, out_c_total=v.c, out_shape=(v.c, v.h, v.w)))
+            self.views[t.uid] = View(dst, 0, v.c, v.c, v.h, v.w, shape=shp)
+
+    def lower_activation(self, t, lay, ins, outs):
+        # keras activation layers (csrc/eltwise.hip): 'linear' passes the view on; every other kind reads its input as a whole
+        # flat buffer (materialised like BatchNormalization's: the training plan keeps it, the backward takes f' from it) and
+        # writes a new buffer or the model's output slot.  Nothing lazy crosses the layer, and no state: the same layer object
+        # may appear in any number of ops.
+        if lay.eltwise is None:
+            self.views[t.uid] = ins[0].copy()
+        else:
+            shp = ins[0].shape
+            v = self.whole(ins[0])
+            dst = self.out_or_new(outs, (v.c, v.h, v.w))
+            if lay not in self.plan.eltwise_layers:
+                self.plan.eltwise_layers.append(lay)
+            self.emit(PlanOp('act', v.buf, dst, (v.c, v.h, v.w), layer=lay, out_c_total=v.c, out_shape=(v.c, v.h, v.w)))
+            self.views[t.uid] = View(dst, 0, v.c, v.c, v.h, v.w, shape=shp)
+
+    def lower_merge(self, t, lay, ins, outs):
+        # keras merge layers (csrc/eltwise.hip): 2 to 4 whole flat buffers of one size -> a new buffer or the output slot
+        shp = ins[0].shape
+        vs = [self.whole(v) for v in ins]
+        v0 = vs[0]
+        if any(v.c * v.h * v.w != v0.c * v0.h * v0.w for v in vs):
+            raise ValueError('%s: inputs of different sizes' % lay.name)
+        dst = self.out_or_new(outs, (v0.c, v0.h, v0.w))
+        if lay not in self.plan.eltwise_layers:
+            self.plan.eltwise_layers.append(lay)
+        self.emit(PlanOp('merge', v0.buf, dst, (v0.c, v0.h, v0.w), layer=lay, aux=tuple(v.buf for v in vs[1:]), out_c_total=v0.c,
+                         out_shape=(v0.c, v0.h, v0.w)))
+        self.views[t.uid] = View(dst, 0, v0.c, v0.c, v0.h, v0.w, shape=shp)
+
+    def finish_outputs(self, t, outs):
+        """a model output that was not produced in place by a conv / concatenate: materialise it into its slot"""
+        plan, views = self.plan, self.views
         for k, o in enumerate(outs):
             v = views[t.uid]
             if v.buf == OUT(o) and v.full:
@@ -1119,9 +1107,58 @@ def build_plan(inputs, outputs, inference=False, fuse_d2s=True, fuse_lstm=False,
                         views[uid] = views[uid].copy(buf=OUT(o))
                     views[t.uid] = View(OUT(o), 0, lc[0], lc[0], lc[1], lc[2], shape=v.shape)
                     continue
-            materialize(v, dst=OUT(o), dst_c_off=0, dst_c_total=lc[0])
+            self.materialize(v, dst=OUT(o), dst_c_off=0, dst_c_total=lc[0])
             if k == 0:
                 views[t.uid] = View(OUT(o), 0, lc[0], lc[0], lc[1], lc[2], shape=v.shape)
+
+
+# (class or predicate of the layer, lowering): the FIRST row that matches lowers the layer.  A new layer kind is one method of
+# _PlanBuilder and one row here.  Rows whose position matters say which later row they must stay in front of; every other row
+# matches a class that no other row's class is a base or a subclass of.
+_LOWERINGS = (
+    (L._Pad2DBase, _PlanBuilder.lower_pad2d),
+    (L._Pad3DBase, _PlanBuilder.lower_pad3d),
+    (L.ConvLSTM2D, _PlanBuilder.lower_convlstm),
+    # in front of UpSampling2D below: a bilinear UpSampling2D is never the lazy (nearest) source mode
+    (lambda lay: isinstance(lay, L.UpSampling2D) and lay.interpolation == 'bilinear', _PlanBuilder.lower_bilinear),
+    (L.MaxPooling2D, _PlanBuilder.lower_pool_or_upsample),
+    (L.UpSampling2D, _PlanBuilder.lower_pool_or_upsample),
+    (L.AveragePooling2D, _PlanBuilder.lower_avgpool),
+    (L.ChannelSlice, _PlanBuilder.lower_slice),
+    (L.Reshape, _PlanBuilder.lower_reshape),
+    (L.Concatenate, _PlanBuilder.lower_concatenate),
+    # in front of Conv2D below: the strided layer is the same class
+    (lambda lay: isinstance(lay, L.Conv2D) and tuple(lay.strides) == (2, 2), _PlanBuilder.lower_strided_conv),
+    (L.DepthwiseConv2D, _PlanBuilder.lower_depthwise),      # SeparableConv2D too: its subclass (neither is a Conv2D)
+    (L.Conv2D, _PlanBuilder.lower_conv2d),
+    (L.Conv2DTranspose, _PlanBuilder.lower_tconv),
+    (L.Cropping2D, _PlanBuilder.lower_crop),
+    (L.RowConnected2D, _PlanBuilder.lower_rowconv),
+    (L.BatchNormalization, _PlanBuilder.lower_batchnorm),
+    (L.Flatten, _PlanBuilder.lower_flatten),
+    (L.Dense, _PlanBuilder.lower_dense),
+    (L.Dropout, _PlanBuilder.lower_dropout),
+    (L._ActivationLayer, _PlanBuilder.lower_activation),
+    (L._Merge, _PlanBuilder.lower_merge),
+)
+
+
+def build_plan(inputs, outputs, inference=False, fuse_d2s=True, fuse_lstm=False, fuse_lstm_step=True, transform=None):
+    """inputs: [KTensor] (exactly one), outputs: [KTensor].  Returns a Plan.  inference=True additionally moves a
+    MaxPooling2D(2) that is the only consumer of a convolution into that convolution's epilogue (the pre-pooling tensor
+    is never written; the training plan keeps it because the backward pass needs it).
+    transform = (head, tail) (inference plans of a model with one output): the wrapper's imputer / scaler as launches of the model
+    call (csrc/scale.hip).  head: a 'scale' op in front reads the input state and writes a buffer of its own, which every consumer
+    of the model input reads instead; tail: a 'scale' op at the end rewrites the output slot in place.  The state a rollout feeds
+    back therefore stays in unscaled units."""
+    if len(inputs) != 1:
+        raise NotImplementedError('exactly one model input is supported')
+    head, tail = (bool(transform[0]), bool(transform[1])) if transform is not None else (False, False)
+    if (head or tail) and not inference:
+        raise ValueError('an input / output transform belongs to inference plans: training data is prepared on the host')
+    if tail and len(outputs) != 1:
+        raise ValueError('an output transform needs a model with exactly one output, got %d' % len(outputs))
+    plan = _PlanBuilder(inputs, outputs, inference, fuse_d2s, fuse_lstm, fuse_lstm_step, head).run()
     for o, st in enumerate(plan.output_store):
         if st is None:
             raise RuntimeError('output %d was never produced' % o)
