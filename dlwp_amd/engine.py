@@ -4,11 +4,11 @@ reference's wrappers use: compile / fit / fit_generator /
 set_weights / reset_states / summary / layers / outputs / stop_training / save.
 
 Forward execution = dlwp_amd.plan.Plan run by the Executor below: eager launches for predict, one captured hipGraph for
-the autoregressive rollout.  torch is plumbing only (device buffers, streams, H2D/D2H copies).
+the autoregressive rollout (what each op kind launches and encodes: forward.py).  torch is plumbing only (device buffers,
+streams, H2D/D2H copies).
 """
 import ctypes
 import os
-import struct
 
 import numpy as np
 import torch
@@ -58,6 +58,7 @@ class Executor(object):
                     raise ValueError("the plan's %s 'scale' op needs scaler parameters of %d features" % (op.role, f))
         self._bufs = {}
         self._descs = None
+        self._launch = None     # _launches(): every op with its descriptor and its eager launch
         self._pool2 = None      # _pooled_too(): convolutions of a training forward that store their pooled image as well
         self._bf16 = set(plan.bf16_buffers()) if activation_dtype == 'bfloat16' else set()
         self._phase = None       # derived (phase-summed) kernels of plan.phase_params: [(w2, b2 | None)]
@@ -82,10 +83,12 @@ class Executor(object):
         if b is None:
             if len(self._bufs) > 4:
                 self._bufs.clear()
-            b = [torch.empty((n,) + s, dtype=torch.bfloat16 if i in self._bf16 else torch.float32, device=self.device)
-                 for i, s in enumerate(self.plan.buffers)]
-            self._bufs[n] = b
+            b = self._bufs[n] = self._new_buffers(n)
         return b
+
+    def _new_buffers(self, n):
+        return [torch.empty((n,) + s, dtype=torch.bfloat16 if i in self._bf16 else torch.float32, device=self.device)
+                for i, s in enumerate(self.plan.buffers)]
 
     def alloc_outputs(self, n):
         return [torch.empty((n,) + s, dtype=torch.float32, device=self.device) for s in self.plan.output_store]
@@ -114,12 +117,8 @@ class Executor(object):
 
     def conv_weights(self, op):
         """(kernel, bias) tensors a conv launch multiplies with: the layer's, or the derived ones of a restated layer."""
-        if op.wparam is not None:
-            w2, b2 = self.phase_buffers()[op.wparam]
-            if self.plan.phase_params[op.wparam].get('kind') == 'sconv':      # (a strided Conv2D keeps its own bias)
-                return w2, op.layer.bias
-            return w2, b2
-        return op.layer.kernel, op.layer.bias
+        from . import forward
+        return forward.conv_weights(self, op)
 
     def _descriptors(self):
         from . import ops
@@ -289,7 +288,7 @@ class Executor(object):
             return outs[-2 - i]
         pooled_too = self._pooled_too() if prepared is not None or skip_ops else {}
         done = set()
-        for k, (op, d) in enumerate(zip(self.plan.ops, self._descriptors())):
+        for k, (op, d, launch) in enumerate(self._launches()):
             if (op.kind in ('phasew', 'tphasew', 'sphasew') and skip_phasew) or k in skip_ops or k in done:
                 continue
             src, dst = res(op.src), res(op.dst)
@@ -301,103 +300,15 @@ class Executor(object):
                               out_pool2=res(self.plan.ops[kp].dst)) is not None:
                     done.add(kp)
                     continue
-            if op.kind == 'conv' and op.src2 is not None:          # a whole ConvLSTM2D step (dlwp_convlstm_step_fwd)
-                if op.dst not in self._oct:
-                    raise RuntimeError('whole-step ConvLSTM2D launches need the h sequence in octets (Model.set_activation_dtype '
-                                       're-plans without them otherwise)')
-                kern, bias = self.conv_weights(op)
-                za, cp, co = op.aux
-                ops.convlstm_step(dst, res(op.src2['buf']), kern, op.src2['layer'].kernel, op.src2['layer'].bias, d,
-                                  self._descriptor2(op), res(cp), res(co), op.src2['xs'][0])
-            elif op.kind == 'conv' and op.lstm_f:
-                kern, bias = self.conv_weights(op)
-                za, cp, co = op.aux
-                ops.convlstm_conv(src, kern, bias, d, dst, res(co), z_add=res(za) if za is not None else None,
-                                  c_prev=res(cp) if cp is not None else None, x_channels=op.xs[0],
-                                  compute_bf16=(op.dst in self._bf16 and op.src not in self._bf16),
-                                  in_o8=op.src in self._oct, out_o8=op.dst in self._oct)
-            elif op.kind == 'conv':
-                kern, bias = self.conv_weights(op)
-                ops.conv2d(src, kern, bias, d, out=dst, x_channels=op.xs[0],
-                           compute_bf16=(op.dst in self._bf16 and op.src not in self._bf16),
-                           prepared=prepared.get(k) if prepared else None,
-                           in_o8=op.src in self._oct, out_o8=op.dst in self._oct)
-            elif op.kind == 'rowconv':
-                ops.rowconv2d(src, op.layer.kernel, op.layer.bias, d, out=dst, x_channels=op.xs[0])
-            elif op.kind == 'phasew':
-                w2, b2 = self.phase_buffers()[op.wparam]
-                ops.phase_weights(op.layer.kernel, op.layer.bias, op.halo.top, op.halo.left, w2=w2, b2=b2)
-                continue
-            elif op.kind == 'd2s':
-                ops.depth_to_space2(src, op.xs[0], out=dst, c_off=op.out_c_off)
-            elif op.kind == 'tphasew':        # Conv2DTranspose: kernel -> the kernel of its 4 F phase channels
-                w2, b2 = self.phase_buffers()[op.wparam]
-                ops.tconv_weights(op.layer.kernel, op.layer.bias, w2=w2, b2=b2)
-                continue
-            elif op.kind == 'd2sc':
-                ops.depth_to_space2_crop(src, op.xs[0], op.crop[0], op.crop[1], op.out_shape[1], op.out_shape[2], out=dst,
-                                         c_off=op.out_c_off)
-            elif op.kind == 'crop':
-                ops.crop2d(src, d, out=dst)
-            elif op.kind == 'sphasew':        # Conv2D(strides=2): kernel -> the kernel on its 4 cin phase channels
-                ops.sconv_weights(op.layer.kernel, w2=self.phase_buffers()[op.wparam][0])
-                continue
-            elif op.kind == 'dwconv':         # DepthwiseConv2D / the stencil of a SeparableConv2D (which has no bias of its own)
-                ops.depthwise2d(src, op.layer.depthwise_kernel, op.layer.depthwise_part.bias, d, out=dst)
-            elif op.kind == 'pwconv':         # the 1 x 1 product of a SeparableConv2D
-                ops.pointwise2d(src, op.layer.pointwise_kernel, op.layer.bias, d, out=dst)
-            elif op.kind == 's2dp':           # halo + 'same' zeros + de-interleave, one pass
-                ops.space_to_depth2_pad(src, op.xs[0], d, op.out_shape[1], op.out_shape[2], c_off=op.in_c_off, out=dst)
-            elif op.kind == 'pad':
-                if op.inner > 1:
-                    hh, ww = op.xs[1], op.xs[2]
-                    ops.pad2d(src.reshape(n, hh, ww, op.inner), d, channels_last=True, out=dst)
-                else:
-                    ops.pad2d(src, d, out=dst)
-            elif op.kind == 'maxpool':
-                ops.maxpool2(src, out=dst)
-            elif op.kind == 'avgpool':
-                ops.avgpool2(src, out=dst)
-            elif op.kind == 'upsample':
-                ops.upsample2(src, out=dst)
-            elif op.kind == 'bilinear':
-                ops.upsample2_bilinear(src, out=dst)
-            elif op.kind == 'copy':
-                if tuple(dst.shape[2:]) != tuple(src.shape[2:]) and dst.numel() == src.numel():
-                    dst = dst.view(src.shape)          # a Reshape relabelled the target: the same contiguous block
-                ops.copy_channels(src, dst, op.xs[0], op.in_c_off, op.out_c_off)
-            elif op.kind == 'dense':
-                ops.dense_fwd(src, op.layer.kernel, op.layer.bias, op.act, out=dst)
-            elif op.kind == 'dropout':         # (training plans only; outside a training step: rate 0 = a copy)
-                lay = op.layer
-                ops.dropout_fwd(src, lay.rate if training else 0.0, lay.mask_seed, self.plan.dropout_layers.index(lay),
-                                self.dropout_step, out=dst)
-            elif op.kind == 'bn':
-                lay = op.layer
-                if training:
-                    st = self.bn_state(k, n)
-                    ops.batchnorm_fwd_train(src, lay.gamma, lay.beta, lay.moving_mean, lay.moving_variance, st['mean'],
-                                            st['invstd'], st['ws'], lay.momentum, lay.epsilon, out=dst)
-                else:
-                    ops.batchnorm_fwd_infer(src, lay.gamma, lay.beta, lay.moving_mean, lay.moving_variance, lay.epsilon,
-                                            out=dst)
-            elif op.kind == 'act':            # keras activation layers: whole flat buffers (csrc/eltwise.hip)
-                ops.activation_fwd(src, *op.layer.eltwise, out=dst)
-            elif op.kind == 'merge':          # keras merge layers: 2 to 4 whole flat buffers of one size
-                ops.merge_fwd(op.layer.kind, [src] + [res(b) for b in op.aux], out=dst)
-            elif op.kind == 'scale':          # the wrapper's imputer + scaler in front, its inverse scaler behind (in place)
-                st = self.transform[op.role]
-                if op.role == 'head':
-                    ops.scale_fwd(src, st.kind, st.fill, st.shift, st.scale, out=dst)
-                else:
-                    ops.scale_inv(src, st.kind, st.shift, st.scale, out=dst)
-            elif op.kind == 'lstm':
-                zh, cp, co = op.aux
-                ops.convlstm_gates(src, res(zh) if zh is not None else None, res(cp) if cp is not None else None,
-                                   res(co), dst, op.xs[0], h_c_off=op.out_c_off, act=op.act, rec_act=op.rec_act)
-            else:
-                raise RuntimeError(op.kind)
+            launch(self, k, op, d, src, dst, res, prepared, training)
         return outs
+
+    def _launches(self):
+        """[(op, its descriptor, its launch of forward.LAUNCHES)] of the plan, resolved once; an op of unknown kind is an error"""
+        if self._launch is None:
+            from . import forward
+            self._launch = list(zip(self.plan.ops, self._descriptors(), forward.launches_of(self.plan)))
+        return self._launch
 
     # -- hipGraph rollout -------------------------------------------------------------------------------------------- #
     @staticmethod
@@ -482,7 +393,7 @@ class Executor(object):
     def _same_split_regime(self, n_a, n_b):
         """Do the plan's convolutions run in the same split-K regime (equal bits) at n_a and at n_b members per launch?"""
         from . import ops
-        dev = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        dev = ops._dev_index(self.device)
         for op, d in zip(self.plan.ops, self._descriptors()):
             if op.kind == 'conv' and not op.lstm_f and op.src2 is None:
                 dt = self._conv_dtype(op)
@@ -505,6 +416,13 @@ class Executor(object):
         with ops.few_wino_scope(self.few_wino(), self.device.index):
             return self._capture_rollout(state0, series, calls, groups, chain, span, ws, prepared, fed)
 
+    def encode_ops(self, n, bufs=None):
+        """(arr, table): the plan at n samples per launch as the _lib.Op records a rollout graph is captured from, and the tensors
+        they address by index -- `bufs` (default: scratch(n)) first, then every parameter (forward.OpTable).  Host work only."""
+        from . import forward
+        ot = forward.OpTable(self, n, self.scratch(n) if bufs is None else bufs)
+        return ot.encode(), ot.params
+
     def _capture_rollout(self, state0, series, calls, groups, chain, span, ws, prepared, fed):
         from . import _lib, ops
         _lib.drain_graveyard()          # a safe point: nothing is being captured yet
@@ -516,219 +434,50 @@ class Executor(object):
         if fed is not None:
             if n_out != 1 or chain is not None:
                 raise ValueError('a fed rollout is one member chain of a model with one output')
+            groups = 1                             # rows exchange data between the calls: one chain
         else:
             for s in self.plan.output_store:
                 if tuple(s) != tuple(self.plan._in_store):
                     raise ValueError('rollout needs every model output to have the input state shape %r, got %r' %
                                      (self.plan._in_store, s))
-        bufs = self.scratch(n) if chain is None else \
-            [torch.empty((n,) + s_, dtype=torch.bfloat16 if i in self._bf16 else torch.float32, device=self.device)
-             for i, s_ in enumerate(self.plan.buffers)]
-        table = [b for b in bufs]
-        widx = {}
-        for lay in self.plan.conv_layers:
-            widx[id(lay)] = (len(table), len(table) + 1 if lay.bias is not None else -1)
-            table.append(lay.kernel)
-            if lay.bias is not None:
-                table.append(lay.bias)
-        didx = {}                                  # Dense: kernel, bias (index | -1)
-        for lay in self.plan.dense_layers:
-            didx[id(lay)] = (len(table), len(table) + 1 if lay.bias is not None else -1)
-            table.append(lay.kernel)
-            if lay.bias is not None:
-                table.append(lay.bias)
-        bidx = {}                                  # BatchNormalization: gamma, beta, moving mean, moving variance (index | -1)
-        for lay in self.plan.bn_layers:
-            ent = []
-            for t in (lay.gamma, lay.beta, lay.moving_mean, lay.moving_variance):
-                ent.append(len(table) if t is not None else -1)
-                if t is not None:
-                    table.append(t)
-            bidx[id(lay)] = ent
-        sidx = {}                                  # scaler / imputer: shift, scale, fill (index | -1), float64, per role
-        for role, st in self.transform.items():
-            if st is not None:
-                ent = []
-                for t in st.tensors:
-                    ent.append(len(table) if t is not None else -1)
-                    if t is not None:
-                        table.append(t)
-                sidx[role] = ent
-        qidx = {}                                  # DepthwiseConv2D / SeparableConv2D: depthwise kernel, pointwise kernel | -1, bias | -1
-        for lay in self.plan.sep_layers:
-            ent = []
-            for t in (lay.depthwise_kernel, getattr(lay, 'pointwise_kernel', None), lay.bias):
-                ent.append(len(table) if t is not None else -1)
-                if t is not None:
-                    table.append(t)
-            qidx[id(lay)] = ent
-        pidx = []                                  # derived (phase-summed) kernels: (w2 index, b2 index | -1)
-        for w2, b2 in self.phase_buffers():
-            pidx.append((len(table), len(table) + 1 if b2 is not None else -1))
-            table.append(w2)
-            if b2 is not None:
-                table.append(b2)
-        kind = {'conv': _lib.OP_CONV2D, 'pad': _lib.OP_PAD2D, 'maxpool': _lib.OP_MAXPOOL2,
-                'upsample': _lib.OP_UPSAMPLE2, 'copy': _lib.OP_COPYCH, 'lstm': _lib.OP_LSTM_GATES,
-                'phasew': _lib.OP_PHASE_WEIGHTS, 'd2s': _lib.OP_DEPTH2SPACE, 'rowconv': _lib.OP_ROWCONV2D,
-                'bn': _lib.OP_BATCHNORM, 'dense': _lib.OP_DENSE, 'scale': _lib.OP_SCALE, 'act': _lib.OP_ACTIVATION,
-                'merge': _lib.OP_MERGE, 'avgpool': _lib.OP_AVGPOOL2, 'bilinear': _lib.OP_BILINEAR2,
-                'tphasew': _lib.OP_TCONV_WEIGHTS, 'd2sc': _lib.OP_DEPTH2SPACE_CROP, 'crop': _lib.OP_CROP2D,
-                'sphasew': _lib.OP_SCONV_WEIGHTS, 's2dp': _lib.OP_SPACE2DEPTH_PAD, 'dwconv': _lib.OP_DEPTHWISE2D,
-                'pwconv': _lib.OP_POINTWISE2D}
-        arr = (_lib.Op * len(self.plan.ops))()
-        for k, (op, d) in enumerate(zip(self.plan.ops, self._descriptors())):
-            o = arr[k]
-            o.kind, o.src, o.dst, o.w, o.b = kind[op.kind], op.src, op.dst, -1, -1
-            o.src2, o.w2 = _lib.BUF_NONE, -1
-            o.xs = _lib.Shape4(n, *op.xs)
-            if op.kind == 'conv':
-                o.w, o.b = pidx[op.wparam] if op.wparam is not None else widx[id(op.layer)]
-                if op.wparam is not None and self.plan.phase_params[op.wparam].get('kind') == 'sconv':
-                    o.b = widx[id(op.layer)][1]            # (a strided Conv2D keeps its own bias)
-                o.conv = d
-                o.aux[0] = self._conv_dtype(op)
-                if op.lstm_f:                          # cell update in the epilogue: z_add | NONE, c_prev | NONE, c_out
-                    za, cp, co = op.aux
-                    o.aux[1] = za if za is not None else _lib.BUF_NONE
-                    o.aux[2] = cp if cp is not None else _lib.BUF_NONE
-                    o.aux[3] = co
-                if op.src2 is not None:                # a whole step: the input convolution rides along
-                    il = op.src2['layer']
-                    o.src2, o.w2, o.xs2_c = op.src2['buf'], widx[id(il)][0], op.src2['xs'][0]
-                    o.conv2 = self._descriptor2(op)
-                    o.b = widx[id(il)][1]                  # the layer's bias belongs to its input convolution
-            elif op.kind == 'rowconv':                 # RowConnected2D: float32 buffers, per-row weights as stored
-                o.w, o.b = widx[id(op.layer)]
-                o.conv = d
-                o.aux[0] = _lib.F32
-            elif op.kind == 'phasew':                  # kernel -> derived kernel, once at the head of the graph
-                o.src, o.b = widx[id(op.layer)]
-                o.dst, b2i = pidx[op.wparam]
-                o.aux[0] = b2i if b2i >= 0 else _lib.BUF_NONE
-                kh, kw = op.layer.kernel_size
-                o.conv.cout, o.conv.kh, o.conv.kw = op.layer.filters, kh, kw
-                o.conv.halo.top, o.conv.halo.left = op.halo.top, op.halo.left
-                o.xs = _lib.Shape4(n, op.xs[0], 1, 1)
-            elif op.kind == 'd2s':
-                o.conv.out_c_off, o.conv.out_c_total = op.out_c_off, op.out_c_total
-            elif op.kind == 'tphasew':                 # Conv2DTranspose kernel -> derived kernel, once at the head of the graph
-                o.src, o.b = widx[id(op.layer)]
-                o.dst, b2i = pidx[op.wparam]
-                o.aux[0] = b2i if b2i >= 0 else _lib.BUF_NONE
-                o.conv.cout, o.conv.kh, o.conv.kw = op.layer.filters, op.layer.kernel_size[0], op.layer.kernel_size[1]
-                o.aux[1], o.aux[2] = self.plan.phase_params[op.wparam]['w2_shape'][:2]      # the stored taps
-                o.xs = _lib.Shape4(n, op.xs[0], 1, 1)
-            elif op.kind == 'd2sc':                    # the cropping interleave: aux = top, left, out_h, out_w
-                o.conv.out_c_off, o.conv.out_c_total = op.out_c_off, op.out_c_total
-                o.aux[0], o.aux[1], o.aux[2], o.aux[3] = op.crop[0], op.crop[1], op.out_shape[1], op.out_shape[2]
-            elif op.kind == 'crop':
-                o.pad = d
-            elif op.kind == 'sphasew':                 # Conv2D(strides=2) kernel -> derived kernel, once at the head of the graph
-                o.src = widx[id(op.layer)][0]
-                o.dst = pidx[op.wparam][0]
-                o.aux[0] = _lib.BUF_NONE
-                o.conv.cout, o.conv.kh, o.conv.kw = op.layer.filters, op.layer.kernel_size[0], op.layer.kernel_size[1]
-                o.aux[1], o.aux[2] = self.plan.phase_params[op.wparam]['w2_shape'][:2]      # the stored taps
-                o.xs = _lib.Shape4(n, op.xs[0], 1, 1)
-            elif op.kind == 'dwconv':                  # the depthwise stencil: conv = taps, dilation, halo, act, windows; aux[0] = dm
-                dk, pk, bi = qidx[id(op.layer)]
-                o.w, o.b = dk, (bi if pk < 0 else -1)      # (the bias of a SeparableConv2D belongs to its pointwise stage)
-                o.conv.kh, o.conv.kw, o.conv.dil_h, o.conv.dil_w = d.kh, d.kw, d.dil_h, d.dil_w
-                o.conv.halo, o.conv.act = d.halo, d.act
-                o.conv.in_c_off, o.conv.in_c_total, o.conv.out_c_off, o.conv.out_c_total = (d.in_c_off, d.in_c_total, d.out_c_off,
-                                                                                             d.out_c_total)
-                o.aux[0] = d.depth_multiplier
-            elif op.kind == 'pwconv':                  # the 1 x 1 product: conv = cout, act, windows
-                dk, pk, bi = qidx[id(op.layer)]
-                o.w, o.b = pk, bi
-                o.conv.cout, o.conv.act = d.o, d.act
-                o.conv.in_c_off, o.conv.in_c_total, o.conv.out_c_off, o.conv.out_c_total = (d.in_c_off, d.in_c_total, d.out_c_off,
-                                                                                             d.out_c_total)
-            elif op.kind == 's2dp':                    # the padded space-to-depth: pad = the halo, aux = hp, wp
-                o.pad = d
-                o.conv.in_c_off, o.conv.in_c_total = op.in_c_off, op.in_c_total
-                o.aux[0], o.aux[1] = op.out_shape[1], op.out_shape[2]
-            elif op.kind == 'dense':
-                o.w, o.b = didx[id(op.layer)]
-                o.conv.cout, o.conv.act = op.layer.units, op.act
-            elif op.kind == 'bn':                      # inference form: the moving statistics, read at every launch
-                g_i, b_i, o.aux[0], o.aux[1] = bidx[id(op.layer)]
-                o.w, o.b = g_i, b_i
-                o.aux[2] = struct.unpack('<i', struct.pack('<f', op.layer.epsilon))[0]
-            elif op.kind == 'act':                     # the kind, and alpha / max_value / theta as float bits
-                d_act = ops.activation_desc(*op.layer.eltwise)
-                o.conv.act = d_act.kind
-                for j, v in enumerate((d_act.alpha, d_act.max_value, d_act.theta)):
-                    o.aux[j] = struct.unpack('<i', struct.pack('<f', v))[0]
-            elif op.kind == 'merge':                   # the other sources ride in aux
-                o.conv.act = ops.MERGE_KINDS[op.layer.kind]
-                for j in range(3):
-                    o.aux[j] = op.aux[j] if j < len(op.aux) else _lib.BUF_NONE
-            elif op.kind == 'scale':                   # float64 parameters, read at every launch; the fill on the input side only
-                o.w, o.b, f_i = sidx[op.role]
-                o.aux[0] = f_i if (f_i >= 0 and op.role == 'head') else _lib.BUF_NONE
-                o.aux[1] = ops.SCALE_KINDS[self.transform[op.role].kind]
-                o.aux[2] = 0 if op.role == 'head' else 1
-            elif op.kind in ('maxpool', 'avgpool', 'bilinear'):
-                o.aux[0] = _lib.BF16 if op.src in self._bf16 else _lib.F32
-            elif op.kind == 'pad':
-                o.pad = d
-                if op.inner > 1:
-                    o.xs = _lib.Shape4(n, 1, op.xs[1], op.xs[2])
-                    o.conv.in_c_total = op.inner
-            elif op.kind == 'copy':
-                o.conv.in_c_off, o.conv.in_c_total = op.in_c_off, op.in_c_total
-                o.conv.out_c_off, o.conv.out_c_total = op.out_c_off, op.out_c_total
-            elif op.kind == 'lstm':
-                zh, cp, co = op.aux
-                o.aux[0] = zh if zh is not None else _lib.BUF_NONE
-                o.aux[1] = cp if cp is not None else _lib.BUF_NONE
-                o.aux[2], o.aux[3] = co, op.rec_act + (256 if op.dst in self._bf16 else 0) + \
-                    (512 if op.src in self._bf16 else 0)
-                o.conv.act = op.act
-                o.conv.out_c_off, o.conv.out_c_total = op.out_c_off, op.out_c_total
-        ptrs = (ctypes.c_void_p * max(1, len(table)))(*[t.data_ptr() for t in table])
+        groups = self.member_groups(n, self.plan._in_store[1] * self.plan._in_store[2]) if groups is None else int(groups)
+        bufs = self.scratch(n) if chain is None else self._new_buffers(n)       # (a chain's own: only the graph keeps them alive)
+        arr, table = self.encode_ops(n, bufs)
+        n_ops, n_tab = len(self.plan.ops), len(table)
+        ptrs = (ctypes.c_void_p * max(1, n_tab))(*[t.data_ptr() for t in table])
+        sample_bytes = (ctypes.c_size_t * max(1, n_tab))(
+            *[(t[0].numel() * t.element_size() if (i < len(bufs) and n > 0) else 0) for i, t in enumerate(table)])
         member = int(np.prod(self.plan._in_store))
         slot = member * n_total                    # elements between two time slots of the series (all members of the rollout)
-        out = ctypes.c_void_p()
-        dev = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        if fed is not None:
-            groups = 1                             # rows exchange data between the calls: one chain
-        groups = self.member_groups(n, self.plan._in_store[1] * self.plan._in_store[2]) if groups is None else int(groups)
-        nbuf = len(bufs)
-        sample_bytes = (ctypes.c_size_t * max(1, len(table)))(
-            *[(t[0].numel() * t.element_size() if (i < nbuf and n > 0) else 0) for i, t in enumerate(table)])
+        handle = _lib.handle(ops._dev_index(self.device))
         # prepared weights (Winograd / packed-N / bf16 layouts) live in memory WE own: the library allocates nothing
-        ws_bytes = int(_lib.lib.dlwp_rollout_workspace_bytes(_lib.handle(dev), arr, len(self.plan.ops), groups))
+        ws_bytes = int(_lib.lib.dlwp_rollout_workspace_bytes(handle, arr, n_ops, groups))
         if ws is None:
             ws = torch.empty(max(1, (ws_bytes + 3) // 4), dtype=torch.float32, device=self.device)
         elif ws.numel() * 4 < ws_bytes:
             raise ValueError('rollout workspace of %d bytes, %d needed' % (ws.numel() * 4, ws_bytes))
+        flags = _lib.F32 | (_lib.ROLLOUT_PREPARED if prepared else 0)
+        out = ctypes.c_void_p()
         if fed is not None:
             fb, state_b, sol, mean, total_calls = fed
             slot_out = int(np.prod(self.plan.output_store[0])) * n
             _lib.check(_lib.lib.dlwp_rollout_create_fed(
-                _lib.handle(dev), arr, len(self.plan.ops), ptrs, len(table), ctypes.c_void_p(state0.data_ptr()),
-                ctypes.c_void_p(state_b.data_ptr()), ctypes.c_void_p(series.data_ptr() + 4 * call0 * slot_out), slot_out,
-                int(calls), call0, int(call0 + calls < int(total_calls)), ctypes.byref(fb),
-                ctypes.c_void_p(sol.data_ptr() if sol is not None else 0),
-                ctypes.c_void_p(mean.data_ptr() if mean is not None else 0), _lib.F32 | (_lib.ROLLOUT_PREPARED if prepared else 0),
-                ctypes.c_void_p(ws.data_ptr()), ws_bytes, ctypes.byref(out)))
-            rg = RolloutGraph(out, keep=(table, state0, series, arr, ptrs, ws, fed), device=self.device)
-            rg.groups, rg.ws = 1, ws
-            return rg
-        # (a time slice: the state comes from the slot in front of its first one, its series starts at its own first slot)
-        state_ptr = state0.data_ptr() if call0 == 0 else series.data_ptr() + 4 * (call0 * n_out - 1) * slot
-        series_ptr = series.data_ptr() + 4 * call0 * n_out * slot
-        _lib.check(_lib.lib.dlwp_rollout_create_grouped(_lib.handle(dev), arr, len(self.plan.ops), ptrs, len(table),
-                                                        sample_bytes, groups, ctypes.c_void_p(state_ptr + 4 * first * member),
-                                                        ctypes.c_void_p(series_ptr + 4 * first * member), slot, int(calls), n_out,
-                                                        _lib.F32 | (_lib.ROLLOUT_PREPARED if prepared else 0),
-                                                        ctypes.c_void_p(ws.data_ptr()), ws_bytes, ctypes.byref(out)))
-        rg = RolloutGraph(out, keep=(table, state0, series, arr, ptrs, ws), device=self.device)
-        rg.groups = int(groups)
-        rg.ws = ws
+                handle, arr, n_ops, ptrs, n_tab, ctypes.c_void_p(state0.data_ptr()), ctypes.c_void_p(state_b.data_ptr()),
+                ctypes.c_void_p(series.data_ptr() + 4 * call0 * slot_out), slot_out, int(calls), call0,
+                int(call0 + calls < int(total_calls)), ctypes.byref(fb), ctypes.c_void_p(sol.data_ptr() if sol is not None else 0),
+                ctypes.c_void_p(mean.data_ptr() if mean is not None else 0), flags, ctypes.c_void_p(ws.data_ptr()), ws_bytes,
+                ctypes.byref(out)))
+        else:
+            # (a time slice: the state comes from the slot in front of its first one, its series starts at its own first slot)
+            state_ptr = state0.data_ptr() if call0 == 0 else series.data_ptr() + 4 * (call0 * n_out - 1) * slot
+            series_ptr = series.data_ptr() + 4 * call0 * n_out * slot
+            _lib.check(_lib.lib.dlwp_rollout_create_grouped(
+                handle, arr, n_ops, ptrs, n_tab, sample_bytes, groups, ctypes.c_void_p(state_ptr + 4 * first * member),
+                ctypes.c_void_p(series_ptr + 4 * first * member), slot, int(calls), n_out, flags, ctypes.c_void_p(ws.data_ptr()),
+                ws_bytes, ctypes.byref(out)))
+        # the graph holds raw addresses: it keeps what they point into
+        rg = RolloutGraph(out, keep=(table, state0, series, arr, ptrs, ws, fed), device=self.device)
+        rg.groups, rg.ws = groups, ws
         return rg
 
     def make_streamed_rollout(self, n, calls, head_chunks=1):
