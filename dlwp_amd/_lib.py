@@ -381,6 +381,9 @@ _sig('dlwp_ens_mean_spread', [_vp, _vp, _i, _i, _i, ctypes.c_longlong, ctypes.c_
 _sig('dlwp_ens_score_workspace', [_vp, _i, _i, _i], _sz)
 _sig('dlwp_ens_score_sums', [_vp, _vp, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, _vp, _i, _i, _i, _i,
                              ctypes.c_longlong, _vp, _vp, _vp, _vp, _sz, _vp])
+_sig('dlwp_ens_event_workspace', [_vp, _i, _i, _i, _i], _sz)
+_sig('dlwp_ens_event_counts', [_vp, _vp, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _i, _i, _i, _i, _i, _i,
+                               ctypes.c_longlong, _i, _vp, _vp, _vp, _sz, _vp])
 _sig('dlwp_ens_perturb', [_vp, _vp, _vp, _vp, EnsPerturb, _vp])
 
 

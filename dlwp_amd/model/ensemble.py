@@ -25,6 +25,32 @@ sums and the int64 histogram come back.  The device path covers 2 <= M <= 256 an
 value per lead) and the tuple that keeps the lead and the first field axis (one value per lead and variable); anything else runs
 the host code on downloaded arrays.
 
+Event verification (event_scores, ensemble_exceedance, finish_events; csrc/events.hip): with what probability
+does the ensemble say the field exceeds a threshold, and are those probabilities any good.  Thresholds are float32, K of them
+(1 <= K <= 8 on the device, any K >= 1 on the host).  A 1-D `thresholds` of K values applies to every point; anything with more
+axes is broadcast (numpy rules) to (K, *field): a threshold per point, such as climatological terciles, or per variable through
+shape (K, V, 1, 1).
+
+* event='above': member i shows the event when x_i > thr and the event verified when y > thr; event='below': x_i < thr and
+  y < thr.  Comparisons are made on the float32 values; ties are no event (the rank rule: ties count as not below).
+  n = #{i : event_i} in 0 .. M, and o = 1 if the event verified, else 0.
+* table[t, g, k, n, o] (int64): the columns of cell (t, g) with that n and o, over the columns where y is not NaN, no member is
+  NaN and thr is not NaN.  Everything below follows from it, so tables of several ranks or files can be added and finished.
+* prob[k, t, s, p] = float32(double(n) / double(M)); NaN where any member of the column is NaN or thr is NaN; y plays no part.
+* finish_events, in float64 from the integer table, cast once to float32.  Per cell and threshold, with N_n = table[n, 0] +
+  table[n, 1], O_n = table[n, 1], N = sum N_n, p_n = n / M and obar = sum O_n / N:
+    brier       = (1/N) sum_n [O_n (p_n - 1)^2 + (N_n - O_n) p_n^2]
+    fair_brier  = brier - (1/N) sum_n N_n n (M - n) / (M^2 (M - 1))                     (Ferro's finite-ensemble correction)
+    reliability = (1/N) sum_{N_n > 0} N_n (p_n - O_n / N_n)^2,   resolution = (1/N) sum_{N_n > 0} N_n (O_n / N_n - obar)^2
+    uncertainty = obar (1 - obar),   brier_skill = 1 - brier / uncertainty (NaN where uncertainty is 0),   base_rate = obar
+    obs_freq[n] = O_n / N_n (NaN where N_n = 0) and fcst_hist[n] = N_n (int64): the reliability diagram and its sharpness histogram
+    ROC, for j = 0 .. M + 1 and the decision "warn when n >= j": hit_rate[j] = sum_{n >= j} O_n / sum O_n, false_alarm_rate[j] =
+    sum_{n >= j} (N_n - O_n) / sum (N_n - O_n), roc_area the trapezoid over those M + 2 points; all three NaN where there are no
+    events or no non-events
+    rps = sum_k brier_k and fair_rps = sum_k fair_brier_k: the ranked probability score for ascending thresholds, NaN where the K
+    thresholds of a cell did not count the same N (NaN thresholds);   count = N (int64);   everything NaN where N = 0.
+  Both paths produce the same table and share finish_events: they return identical bits.
+
 The generator (perturb_members, ensemble_forecast; csrc/perturb.hip) MAKES such an ensemble:
 out[s, m, k, i, j] = x[s, k, i, j] + sign * sigma[k] * zeta, the product and the sum each rounded once to float32.
 
@@ -49,11 +75,18 @@ import torch
 from .verify import _common_device, _groups_run, _prod, _to_device, _to_host, _wants_device
 
 MAX_DEVICE_MEMBERS = 256
+MAX_DEVICE_THRESHOLDS = 8
 MAX_RADIUS = 16
 
 #: rmse_mean, mae_mean, spread, spread_skill (= spread / rmse_mean), crps, fair_crps: float32 (T,) or (T, G); rank_hist: int64
 #: (T[, G], M + 1); count: int64, the columns counted; crps_field: the per-column crps (T, S, *field) or None
 EnsembleScores = collections.namedtuple('EnsembleScores', 'rmse_mean mae_mean spread spread_skill crps fair_crps rank_hist count crps_field')
+
+#: brier .. roc_area: float32 (T[, G], K); rps, fair_rps: float32 (T[, G]); obs_freq (float32) and fcst_hist (int64): (T[, G], K,
+#: M + 1); hit_rate, false_alarm_rate: float32 (T[, G], K, M + 2); count: int64 (T[, G], K); table: int64 (T[, G], K, M + 1, 2);
+#: prob_field: float32 (K, T, S, *field) or None
+EventScores = collections.namedtuple('EventScores', 'brier fair_brier reliability resolution uncertainty brier_skill base_rate roc_area '
+                                     'rps fair_rps obs_freq fcst_hist hit_rate false_alarm_rate count table prob_field')
 
 
 def _layout(forecast, member_axis):
@@ -247,6 +280,193 @@ def ensemble_scores(forecast, valid, member_axis=2, axis=None, ddof=1, crps_fiel
     forecast, valid = np.asarray(forecast, dtype=np.float32), np.asarray(valid, dtype=np.float32)
     sums, hist, field_out = _scores_host(forecast, valid, member_axis, axis, crps_field)
     return finish(sums, hist, m, ddof, field_out)
+
+
+# -- event verification: thresholds, the host table, the finish ---------------------------------------------------------------------- #
+def _check_event(event):
+    if event not in ('above', 'below'):
+        raise ValueError("'event' must be 'above' or 'below', got %r" % (event,))
+    return event == 'below'
+
+
+def _thresholds(thresholds, field):
+    """(float32 thresholds, per_point): (K,) for a 1-D (or scalar) argument, else broadcast to (K, *field)"""
+    thr = np.asarray(_to_host(thresholds), dtype=np.float32)
+    if thr.ndim <= 1:
+        thr = thr.reshape(-1)
+        if thr.size < 1:
+            raise ValueError("'thresholds' is empty")
+        return np.ascontiguousarray(thr), False
+    if thr.ndim != 1 + len(field) or thr.shape[0] < 1:
+        raise ValueError("'thresholds' %r must be (K,) or broadcast to (K, *field) = (K,) + %r" % (thr.shape, tuple(field)))
+    try:
+        full = np.broadcast_to(thr, (thr.shape[0],) + tuple(field))
+    except ValueError:
+        raise ValueError("'thresholds' %r do not broadcast to (K, *field) = (%d,) + %r" % (thr.shape, thr.shape[0], tuple(field)))
+    return np.array(full, dtype=np.float32), True                  # a writable copy: broadcast_to returns a read-only view
+
+
+def _event_columns_host(x, thr, below):
+    """One lead.  x: float32 (S, M, *field), thr: float32 broadcastable to (S, *field) -> (n int64 (S, *field), bad bool (S, *field)):
+    the members that show the event, and where a member or the threshold is NaN"""
+    n = np.zeros(x.shape[:1] + x.shape[2:], np.int64)
+    with np.errstate(invalid='ignore'):
+        for i in range(x.shape[1]):
+            n += (x[:, i] < thr) if below else (x[:, i] > thr)
+    return n, np.isnan(x).any(axis=1) | np.isnan(thr)
+
+
+def _prob32(n, bad, members):
+    return np.where(bad, np.nan, n.astype(np.float64) / float(members)).astype(np.float32)
+
+
+def _events_host(forecast, valid, thr, per_point, below, member_axis, axis, want_field):
+    """(table (T, *keep, K, M + 1, 2) int64, prob (K, T, S, *field) float32 or None) over any `axis` of valid's axes that leaves the lead"""
+    t_n, s_n, m, field = _layout(forecast, member_axis)
+    ndim = valid.ndim
+    if axis is None:
+        red = tuple(range(1, ndim))
+    else:
+        red = tuple(sorted({int(a) + ndim if int(a) < 0 else int(a) for a in (axis if isinstance(axis, (tuple, list)) else (axis,))}))
+        if not red or red[0] < 1 or red[-1] >= ndim:
+            raise ValueError("'axis' %r must name axes 1 .. %d of 'valid' (the lead axis stays)" % (axis, ndim - 1))
+    keep = tuple(a for a in range(1, ndim) if a not in red)
+    keep_shape = tuple(valid.shape[a] for a in keep)
+    cells = _prod(keep_shape)
+    k_n = thr.shape[0]
+    order = tuple(a - 1 for a in keep) + tuple(a - 1 for a in red)
+    cell_of = np.arange(cells)[:, None]
+    bins = (m + 1) * 2
+    table = np.zeros((t_n, cells, k_n, m + 1, 2), np.int64)
+    prob = np.empty((k_n, t_n, s_n) + field, np.float32) if want_field else None
+    for t in range(t_n):
+        x, y = _members_second(forecast, t, member_axis), valid[t]
+        for k in range(k_n):
+            thr_k = thr[k][None] if per_point else thr[k]
+            n, bad = _event_columns_host(x, thr_k, below)
+            with np.errstate(invalid='ignore'):
+                o = ((y < thr_k) if below else (y > thr_k)).astype(np.int64)
+            ok = np.transpose(~(bad | np.isnan(y)), order).reshape(cells, -1)
+            index = (cell_of * bins + np.transpose(n * 2 + o, order).reshape(cells, -1))[ok]
+            table[t, :, k] = np.bincount(index, minlength=cells * bins).reshape(cells, m + 1, 2)
+            if want_field:
+                prob[k, t] = _prob32(n, bad, m)
+    return table.reshape((t_n,) + keep_shape + (k_n, m + 1, 2)), prob
+
+
+def finish_events64(table, members):
+    """The formulas of the module docstring in float64, before the cast: a dict of float64 arrays (fcst_hist, count int64)"""
+    table = np.asarray(table, dtype=np.int64)
+    m = int(members)
+    if m < 2 or table.ndim < 3 or table.shape[-2:] != (m + 1, 2):
+        raise ValueError('finish_events: the table %r must end in (K, %d, 2) for %d >= 2 members' % (table.shape, m + 1, m))
+    miss_i, o_i, n_i = table[..., 0], table[..., 1], table[..., 0] + table[..., 1]              # N_n - O_n, O_n, N_n: (..., K, M + 1)
+    count = n_i.sum(axis=-1)                                                                     # (..., K)
+    o_n, n_n = o_i.astype(np.float64), n_i.astype(np.float64)
+    k = np.arange(m + 1, dtype=np.float64)
+    p = k / m
+    zero = np.zeros(table.shape[:-2] + (1,), np.int64)
+    hits = np.concatenate((np.cumsum(o_i[..., ::-1], axis=-1)[..., ::-1], zero), axis=-1).astype(np.float64)       # sum_{n >= j} O_n
+    falses = np.concatenate((np.cumsum(miss_i[..., ::-1], axis=-1)[..., ::-1], zero), axis=-1).astype(np.float64)
+    with np.errstate(divide='ignore', invalid='ignore', over='ignore'):
+        n = np.where(count > 0, count, np.nan).astype(np.float64)
+        brier = (o_n * (p - 1.0) ** 2 + (n_n - o_n) * p * p).sum(axis=-1) / n
+        fair = brier - (n_n * (k * (m - k) / (float(m) * m * (m - 1.0)))).sum(axis=-1) / n
+        obar = o_n.sum(axis=-1) / n
+        hit = n_n > 0
+        freq = np.where(hit, o_n / np.where(hit, n_n, 1.0), np.nan)
+        rel = np.where(hit, n_n * (p - freq) ** 2, 0.0).sum(axis=-1) / n
+        res = np.where(hit, n_n * (freq - obar[..., None]) ** 2, 0.0).sum(axis=-1) / n
+        unc = obar * (1.0 - obar)
+        skill = np.where(unc > 0, 1.0 - brier / np.where(unc > 0, unc, 1.0), np.nan)
+        both = (hits[..., :1] > 0) & (falses[..., :1] > 0)
+        hit_rate = np.where(both, hits / np.where(both, hits[..., :1], 1.0), np.nan)
+        false_rate = np.where(both, falses / np.where(both, falses[..., :1], 1.0), np.nan)
+        area = ((false_rate[..., :-1] - false_rate[..., 1:]) * (hit_rate[..., :-1] + hit_rate[..., 1:]) * 0.5).sum(axis=-1)
+        same = (count == count[..., :1]).all(axis=-1) & (count[..., 0] > 0)
+        rps = np.where(same, brier.sum(axis=-1), np.nan)
+        fair_rps = np.where(same, fair.sum(axis=-1), np.nan)
+    return dict(brier=brier, fair_brier=fair, reliability=rel, resolution=res, uncertainty=unc, brier_skill=skill, base_rate=obar,
+                roc_area=area, rps=rps, fair_rps=fair_rps, obs_freq=freq, fcst_hist=n_i, hit_rate=hit_rate, false_alarm_rate=false_rate,
+                count=count, table=table)
+
+
+def finish_events(table, members, prob_field=None):
+    """The int64 table (..., K, M + 1, 2) -> EventScores by the formulas of the module docstring: float64 throughout
+    (finish_events64), one cast to float32, NaN where nothing was counted.  Tables of several ranks or files can be added and
+    finished."""
+    v = finish_events64(table, members)
+    return EventScores(prob_field=prob_field, **{name: a.astype(np.float32) if a.dtype == np.float64 else a for name, a in v.items()})
+
+
+def _events_device(forecast, valid, thr, per_point, below, dims, member_axis, groups, run, want_table, want_field, device):
+    """dlwp_ens_event_counts on device operands: (table (T, G, K, M + 1, 2) numpy int64 or None, prob (K, T, S, *field) or None)"""
+    from .. import ops
+    t_n, s_n, m, field = dims
+    named = (('forecast', forecast),) + ((('valid', valid),) if want_table else ())
+    dev = _device_of(named, device)
+    with torch.cuda.device(dev):
+        x = _to_device(forecast, dev)
+        y = _to_device(valid, dev) if want_table else None
+        thr_d = torch.from_numpy(thr if per_point else np.ascontiguousarray(np.repeat(thr[:, None], groups, axis=1))).to(dev)
+        table, prob = ops.ens_event_counts(x, ops.ens_strides(s_n, m, groups * run, member_axis), y, thr_d, per_point, below, t_n, s_n, m,
+                                           groups, run, want_table=want_table, want_prob=want_field)
+        table = table.cpu().numpy() if want_table else None
+        if want_field:
+            prob = prob.view((thr.shape[0], t_n, s_n) + field)
+            if not isinstance(forecast, torch.Tensor):
+                prob = prob.cpu().numpy()
+    return table, prob
+
+
+def event_scores(forecast, valid, thresholds, member_axis=2, axis=None, event='above', prob_field=False, device=None):
+    """Event scores of an ensemble forecast against the per-lead verification `valid` (T, S, *field), for the events "above" (or
+    "below") each of K thresholds: (K,) values for every point, or anything that broadcasts to (K, *field).  Shapes, the device-or-
+    host decision and `axis` are those of ensemble_scores.  Returns an EventScores (module docstring); with prob_field=True the
+    probability field (K, T, S, *field) comes back too (a CUDA tensor where `forecast` is one).  Only the integer table comes back
+    from the device, and finish_events is shared: both paths return identical bits."""
+    t_n, s_n, m, field = _layout(forecast, member_axis)
+    below = _check_event(event)
+    if tuple(int(s) for s in valid.shape) != (t_n, s_n) + field:
+        raise ValueError('event_scores: shapes %r (forecast, member_axis=%d) and %r (valid) do not match; valid must be %r'
+                         % (tuple(forecast.shape), member_axis, tuple(valid.shape), (t_n, s_n) + field))
+    thr, per_point = _thresholds(thresholds, field)
+    named = (('forecast', forecast), ('valid', valid))
+    if _wants_device(named, device):
+        gr = _groups_run(field, axis, 1) if m <= MAX_DEVICE_MEMBERS else None
+        if gr is not None:
+            if thr.shape[0] > MAX_DEVICE_THRESHOLDS:
+                raise ValueError('event_scores: %d thresholds, the device path takes 1 .. %d' % (thr.shape[0], MAX_DEVICE_THRESHOLDS))
+            table, prob = _events_device(forecast, valid, thr, per_point, below, (t_n, s_n, m, field), member_axis, gr[0], gr[1], True,
+                                         prob_field, device)
+            return finish_events(table[:, 0] if axis is None else table, m, prob)
+        forecast, valid = _to_host(forecast), _to_host(valid)
+    forecast, valid = np.asarray(forecast, dtype=np.float32), np.asarray(valid, dtype=np.float32)
+    table, prob = _events_host(forecast, valid, thr, per_point, below, member_axis, axis, prob_field)
+    return finish_events(table, m, prob)
+
+
+def ensemble_exceedance(forecast, thresholds, member_axis=2, event='above', device=None):
+    """The fraction of members above (or below) each threshold: float32 (K, T, S, *field) = float32(n / M), NaN where a member or the
+    threshold is NaN -- a CUDA tensor for a CUDA tensor, else a numpy array.  thresholds: as in event_scores."""
+    t_n, s_n, m, field = _layout(forecast, member_axis)
+    below = _check_event(event)
+    thr, per_point = _thresholds(thresholds, field)
+    named = (('forecast', forecast),)
+    if _wants_device(named, device):
+        if m <= MAX_DEVICE_MEMBERS:
+            if thr.shape[0] > MAX_DEVICE_THRESHOLDS:
+                raise ValueError('ensemble_exceedance: %d thresholds, the device path takes 1 .. %d' % (thr.shape[0], MAX_DEVICE_THRESHOLDS))
+            return _events_device(forecast, None, thr, per_point, below, (t_n, s_n, m, field), member_axis, 1, _prod(field), False, True,
+                                  device)[1]
+        forecast = _to_host(forecast)
+    forecast = np.asarray(forecast, dtype=np.float32)
+    prob = np.empty((thr.shape[0], t_n, s_n) + field, np.float32)
+    for t in range(t_n):
+        x = _members_second(forecast, t, member_axis)
+        for k in range(thr.shape[0]):
+            prob[k, t] = _prob32(*_event_columns_host(x, thr[k][None] if per_point else thr[k], below), m)
+    return prob
 
 
 # -- the member generator: the numpy statement of the definition (module docstring) ------------------------------------------------ #

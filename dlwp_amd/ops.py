@@ -1984,6 +1984,68 @@ def ens_score_sums(x, strides, y, leads, samples, members, groups, run, crps_fie
     return (sums, hist, crps) if crps_field else (sums, hist)
 
 
+# -- ensemble event verification (csrc/events.hip) ----------------------------------------------------------------------------------- #
+ENS_MAX_THRESHOLDS = 8
+
+
+def ens_event_workspace(device_index, leads, groups, members, thresholds):
+    """bytes of workspace dlwp_ens_event_counts needs on that device for a table (any sample count)"""
+    return int(_lib.lib.dlwp_ens_event_workspace(_lib.handle(int(device_index)), int(leads), int(groups), int(members), int(thresholds)))
+
+
+def ens_event_counts(x, strides, y, thr, per_point, below, leads, samples, members, groups, run, want_table=True, want_prob=False,
+                     ws=None):
+    """include/dlwp_hip.h: dlwp_ens_event_counts.  x: the ensemble as in ens_mean_spread; y: contiguous float32 device tensor of
+    leads * samples * groups * run elements (None where no table is wanted); thr: contiguous float32 device tensor whose first axis
+    is the K thresholds, K * groups elements, or K * groups * run with per_point.  Returns NEW device tensors (table (leads, groups,
+    K, members + 1, 2) int64 or None, prob (K, leads, samples, groups * run) float32 or None)."""
+    if not (want_table or want_prob):
+        raise ValueError('ens_event_counts: neither the table nor the probability field is wanted')
+    if want_table and y is None:
+        raise ValueError('ens_event_counts: the table needs the verification y')
+    y = y if want_table else None
+    _check_f32(*(t for t in (x, y, thr) if t is not None))
+    d = _dev(x)
+    for t in (y, thr):
+        if t is not None and _dev(t) != d:
+            raise ValueError('ens_event_counts: operands on devices %d and %d' % (d, _dev(t)))
+    leads, samples, members, groups, run = int(leads), int(samples), int(members), int(groups), int(run)
+    if not 2 <= members <= ENS_MAX_MEMBERS:
+        raise ValueError('ens_event_counts: %d members, expected 2 .. %d' % (members, ENS_MAX_MEMBERS))
+    if groups < 1 or run < 1:
+        raise ValueError('ens_event_counts: groups and run must be >= 1')
+    k_n = int(thr.shape[0]) if thr.dim() >= 1 else 0
+    if not 1 <= k_n <= ENS_MAX_THRESHOLDS:
+        raise ValueError('ens_event_counts: %d thresholds, expected 1 .. %d' % (k_n, ENS_MAX_THRESHOLDS))
+    _ens_check('ens_event_counts', x, strides, leads, samples, members, groups * run)
+    if y is not None and y.numel() != leads * samples * groups * run:
+        raise ValueError('ens_event_counts: the verification holds %d elements, expected %d' % (y.numel(), leads * samples * groups * run))
+    thr_need = k_n * groups * (run if per_point else 1)
+    if thr.numel() != thr_need:
+        raise ValueError('ens_event_counts: the thresholds hold %d elements, expected %d (%s)'
+                         % (thr.numel(), thr_need, 'K x groups x run' if per_point else 'K x groups'))
+    h = _lib.handle(d)
+    table = prob = None
+    ws_bytes = 0
+    if want_table:
+        need = max(int(_lib.lib.dlwp_ens_event_workspace(h, leads, groups, members, k_n)), 4)
+        if ws is None:
+            ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+        elif ws.numel() * ws.element_size() < need or ws.device != x.device:
+            raise ValueError('ens_event_counts: the workspace holds %d bytes on %s, expected %d on %s' % (ws.numel() * ws.element_size(),
+                                                                                                        ws.device, need, x.device))
+        ws_bytes = ws.numel() * ws.element_size()
+        table = torch.empty((leads, groups, k_n, members + 1, 2), dtype=torch.int64, device=x.device)
+    else:
+        ws = None
+    if want_prob:
+        prob = torch.empty((k_n, leads, samples, groups * run), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib.dlwp_ens_event_counts(h, _ptr(x), int(strides[0]), int(strides[1]), int(strides[2]), _ptr(y), _ptr(thr),
+                                              1 if per_point else 0, 1 if below else 0, leads, samples, members, groups, run, k_n,
+                                              _ptr(table), _ptr(prob), _ptr(ws), ws_bytes, _stream(x)))
+    return table, prob
+
+
 # -- the ensemble member generator (csrc/perturb.hip) -------------------------------------------------------------------------------- #
 ENS_MAX_RADIUS = _lib.ENS_MAX_RADIUS
 

@@ -1218,6 +1218,36 @@ int dlwp_ens_score_sums(dlwp_handle_t, const void* x, long long lead_stride, lon
                         const void* y, int leads, int samples, int members, int groups, long long run, void* sums, void* hist,
                         void* crps_out, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- ensemble EVENT verification on the device (csrc/events.hip): columns, strides, layouts and groups are
+ *      those of the block above, row = groups * run.  thr holds `thresholds` (K, 1 .. 8) float32 thresholds per group,
+ *      (K, groups), with thr_per_point == 0 -- uniform within a group, loaded once per block -- or per point, (K, groups * run), with
+ *      thr_per_point == 1.  With below == 0 member i shows the event where x_i > thr and the event verified where y > thr; with
+ *      below == 1 the tests are x_i < thr and y < thr.  Comparisons are made on the float32 values; ties are no event.
+ *        n = #{i : event_i} in 0 .. members,  o = 1 if the event verified, else 0
+ *        table[lead][group][k][n][o] = columns of the cell with that n and o, over the columns where y is not NaN, no member
+ *                                      is NaN and thr is not NaN                                                     (int64)
+ *        prob_out[k][lead][sample][p] = float32(double(n) / double(members)); NaN where a member or thr is NaN; y plays no part
+ *      table is (leads, groups, K, members + 1, 2); prob_out is (K, leads, samples, groups * run) float32; y is the contiguous
+ *      verification (leads, samples, groups * run).  y and table are both given or both NULL, at least one of table / prob_out
+ *      is given, and ws is needed only with table.  2 <= members <= 256.  One pass over the members with K counters per column in
+ *      registers; a lane owns four adjacent columns (16-byte accesses: run and the three strides multiples of 4, x, y, prob_out
+ *      and a per-point thr 16-byte aligned) or one.  A block keeps its table in LDS as up to 32 interleaved replicas (a lane
+ *      adds to replica lane mod replicas, so a wave's adds spread over the banks whatever the data are); where the table leaves
+ *      room for fewer than 16, a wave first aggregates equal bins (first remaining lane's bin, ballot, one add of the population
+ *      count; at most 4 rounds) and the lanes still left use plain LDS adds.  Each block writes its 32-bit partial table to ws
+ *      and a second launch adds a cell's partials in index order: no global atomics, repeated calls give identical bits.
+ *      dlwp_ens_event_workspace returns the bytes of ws for any sample count (a NULL handle counts 256 CUs), 0 for sizes outside
+ *      the ranges.  ws must be 4-byte aligned.  Refused without a launch, in this order: sizes or flags out of range (leads,
+ *      samples, groups, run >= 1; members 2 .. 256; thresholds 1 .. 8; both flags 0 or 1), negative strides, the null-pointer rules
+ *      above, more than 2^20 cells (or more columns per block than a 32-bit partial counts), a workspace too small or
+ *      misaligned, a null handle.  The caller guarantees that every addressed element exists (dlwp_amd.ops checks it).  Not
+ *      part of a training step: it marks a recording tape foreign.                                                            */
+size_t dlwp_ens_event_workspace(dlwp_handle_t, int leads, int groups, int members, int thresholds);
+int dlwp_ens_event_counts(dlwp_handle_t, const void* x, long long lead_stride, long long sample_stride, long long member_stride,
+                          const void* y, const void* thr, int thr_per_point, int below,
+                          int leads, int samples, int members, int groups, long long run, int thresholds,
+                          void* table, void* prob_out, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- the ensemble member generator (csrc/perturb.hip; the reference has no counterpart): a perturbed-
  *      initial-condition ensemble made in HBM.  x: float32 (samples, channels, height, width) contiguous; sigma: float32[channels];
  *        out[s * sample_stride + m * member_stride + (k * height + i) * width + j] = x[s, k, i, j] + sign * sigma[k] * zeta
