@@ -28,6 +28,14 @@ verification_from_samples / verification_from_series (one int64 row array from w
 dlwp_gather_rows_fill with the same bits; verification_tensor keeps the result in HBM for forecast_error), and the two host
 reshapes predictors_to_time_series / add_metadata_to_forecast.  DESIGN.md 5.30 has the kernels and the measurements.
 
+Beyond the reference module: forecast_skill / persistence_skill score the same series with a weight per latitude row and against a
+climatology -- one field, or a table per label (monthly_climatology, month_labels) -- and return a Skill tuple per lead (and variable):
+weighted mse, rmse, mae, the bias, the uncentred anomaly correlation of the reference's training metric (custom.anomaly_correlation)
+and the centred one.  On the device one pass of dlwp_verify_skill_sums (csrc/skill.hip) leaves ten float64 sums per lead and group,
+which finish_skill turns into the scores; the host path computes the same definition in numpy (float32 d = fc - ob, fa = fc - c,
+oa = ob - c, float64 sums) and is no fallback of the device path: both refuse an `axis` they do not cover.  An ensemble is scored
+through its mean: forecast_skill(ensemble.ensemble_mean_spread(series)[0], valid, ...).  DESIGN.md 5.38 has the kernel and the bounds.
+
 A caveat of return_device=True: the tensor may alias the cached series buffer of the model's captured rollout, which the next
 rollout of that model overwrites -- verify it (or clone it) before rolling the model out again.
 """
@@ -492,3 +500,226 @@ def verification_tensor(ds, all_ds=None, forecast_steps=1, dt=6, kind='series', 
         raise ValueError("'kind' must be 'series' or 'samples'")
     first, source = (1, 'predictors') if kind == 'series' else (0, 'targets')
     return _verification(ds, all_ds, forecast_steps, dt, first, source, device, True)
+
+
+# -- latitude-weighted skill: rmse, bias, anomaly correlation (csrc/skill.hip) --------------------------------------- #
+#: per lead (and group): float32 scores, int64 count of the pairs behind them; NaN where nothing was counted or sum w is 0
+Skill = collections.namedtuple('Skill', 'mse rmse mae bias acc acc_centered count')
+
+#: fc, ob: names of the operands; x_strides = (lead_stride, sample_stride, shift) as in Plan; label_strides = (lead_stride, shift):
+#: the label of pair (f, i) is labels[f * lead_stride + i + f * shift]
+SkillPlan = collections.namedtuple('SkillPlan', 'fc ob fc_strides ob_strides label_strides leads count0 count_dec groups run')
+
+
+def finish_skill(sums, grouped=True):
+    """(..., 10) float64 sums of dlwp_verify_skill_sums (include/dlwp_hip.h) -> Skill, computed in float64 and cast once.  Tables of
+    several ranks or chunks add before the finish.  grouped=False drops a groups axis of one: (leads, 1, 10) -> (leads,)."""
+    s = np.asarray(sums, dtype=np.float64)
+    s0, s1, s2, s3, s4, s5, s6, s7, s8, n = (s[..., k] for k in range(10))
+    with np.errstate(all='ignore'):
+        some = (n > 0) & (s0 > 0)
+        s0 = np.where(some, s0, np.nan)
+        mse = s2 / s0
+        m_f, m_o = s4 / s0, s5 / s0
+        den = np.sqrt(s7 * s8)
+        acc = np.where(den > 0, s6 / den, np.nan)
+        den = np.sqrt((s7 / s0 - m_f * m_f) * (s8 / s0 - m_o * m_o))
+        acc_c = np.where(den > 0, (s6 / s0 - m_f * m_o) / den, np.nan)
+        scores = [mse, np.sqrt(mse), s3 / s0, s1 / s0, np.where(some, acc, np.nan), np.where(some, acc_c, np.nan)]
+        scores = [v.astype(np.float32) for v in scores]
+    out = Skill(*(scores + [n.astype(np.int64)]))
+    return out if grouped else Skill(*(v[..., 0] for v in out))
+
+
+def area_weights(lats):
+    """cos(latitude) per row as float32, never negative: in float32 cos(90 degrees) is -4.37e-8, and a negative weight would break
+    both the scores and their error bounds"""
+    from .. import custom
+    return np.maximum(custom.latitude_weights(lats, 'cosine'), 0).astype(np.float32)
+
+
+def month_labels(times):
+    """calendar month - 1 (0 .. 11) of a datetime64 array of any shape, int32: the labels of monthly_climatology's table"""
+    return _months(times)
+
+
+def monthly_climatology(da, device=None):
+    """The (12, ...) float32 table monthly_climo_error builds internally: the NaN-skipping mean per calendar month over ALL of `da` (a
+    LabeledArray with a datetime64 'sample' or 'time' coordinate, which becomes the leading axis), the same bits.  device='cuda' or
+    CUDA values reduce on the device (dlwp_verify_label_nanmean); the result is a CUDA tensor for CUDA values and numpy otherwise."""
+    time_dim = 'sample' if 'sample' in da.dims else 'time'
+    ax = da.dims.index(time_dim)
+    months = _months(np.asarray(da.coords[time_dim]))
+    dev = _cuda_device(da.values, device)
+    if dev is None:
+        x = np.moveaxis(da.values, ax, 0)
+        if x.dtype != np.float32:
+            x = x.astype(np.float32)
+        return label_nanmean_host(x, months, 12)
+    from .. import ops
+    if not isinstance(da.values, torch.Tensor) and np.asarray(da.values).dtype != np.float32:
+        raise TypeError("'da' must be float32 on the device path, got %s" % np.asarray(da.values).dtype)
+    with torch.cuda.device(dev):
+        x = _to_device(da.values, dev)
+        if ax:
+            x = x.movedim(ax, 0).contiguous()
+        table = ops.verify_label_nanmean(x, months, 12)
+        return table if isinstance(da.values, torch.Tensor) else table.cpu().numpy()
+
+
+def _skill_groups_run(who, inner, axis, lead_axes):
+    gr = _groups_run(inner, axis, lead_axes)
+    if gr is None:
+        raise ValueError("%s: 'axis' must be None or the tuple that keeps the lead and the first inner axis of rows %r, got %r"
+                         % (who, tuple(inner), axis))
+    return gr
+
+
+def plan_forecast_skill(f_shape, v_shape, axis):
+    """forecast_skill as a SkillPlan over ('forecast', 'valid').  Pure host code; ValueError for shapes that do not match and for an
+    `axis` other than None or the tuple that keeps the lead and the first inner axis."""
+    f_shape, v_shape = tuple(int(s) for s in f_shape), tuple(int(s) for s in v_shape)
+    if len(f_shape) == len(v_shape):
+        if f_shape != v_shape or len(f_shape) < 3 or f_shape[0] < 1:
+            raise ValueError('forecast_skill: shapes %r and %r do not match' % (f_shape, v_shape))
+        groups, run = _skill_groups_run('forecast_skill', f_shape[2:], axis, 1)
+        n, row = f_shape[1], _prod(f_shape[2:])
+        return SkillPlan('forecast', 'valid', (n * row, row, 0), (n * row, row, 0), (n, 0), f_shape[0], n, 0, groups, run)
+    n, nv = (f_shape[1], v_shape[0]) if len(f_shape) >= 2 and v_shape else (0, 0)
+    if len(f_shape) != len(v_shape) + 1 or len(v_shape) < 2 or f_shape[0] < 1 or f_shape[2:] != v_shape[1:] or n < nv:
+        raise ValueError('forecast_skill: shapes %r and %r do not match' % (f_shape, v_shape))
+    groups, run = _skill_groups_run('forecast_skill', v_shape[1:], axis, 0)
+    row = _prod(v_shape[1:])
+    return SkillPlan('forecast', 'valid', (n * row, row, 0), (0, row, 1), (0, 1), f_shape[0], nv, 1, groups, run)
+
+
+def plan_persistence_skill(p_shape, v_shape, n_fhour, axis):
+    """persistence_skill as a SkillPlan over ('predictors', 'valid'): the forecast of every lead is predictors[i]"""
+    p_shape, v_shape = tuple(int(s) for s in p_shape), tuple(int(s) for s in v_shape)
+    if len(v_shape) < 2 or len(p_shape) != len(v_shape) or p_shape[1:] != v_shape[1:] or p_shape[0] < v_shape[0]:
+        raise ValueError('persistence_skill: shapes %r and %r do not match' % (p_shape, v_shape))
+    if int(n_fhour) < 1:
+        raise ValueError("persistence_skill: 'n_fhour' must be >= 1")
+    groups, run = _skill_groups_run('persistence_skill', v_shape[1:], axis, 0)
+    row = _prod(v_shape[1:])
+    return SkillPlan('predictors', 'valid', (0, row, 0), (0, row, 1), (0, 1), int(n_fhour), v_shape[0], 1, groups, run)
+
+
+def _skill_extras(who, plan, inner, label_shape, climatology, labels, weights):
+    """The optional arguments, checked on the host before anything is uploaded: (table (L, *inner) or None, flat int32 labels or None,
+    float32 weights or None).  A table of one field has no labels; a table of several needs labels of `label_shape`."""
+    from .. import ops
+    inner = tuple(inner)
+    table = None
+    if climatology is not None:
+        shape = tuple(climatology.shape)
+        if shape == inner:
+            if labels is not None:
+                raise ValueError("%s: 'labels' need a (L, ...) climatology table, got one field" % who)
+            table = climatology.reshape((1,) + inner)
+        elif shape[1:] == inner and 1 <= shape[0] <= ops.VERIFY_MAX_LABELS:
+            if labels is None:
+                raise ValueError("%s: a climatology table needs 'labels' of shape %r" % (who, tuple(label_shape)))
+            table = climatology
+        else:
+            raise ValueError("%s: 'climatology' must have the shape %r of a sample row or (L <= %d,) + that shape, got %r"
+                             % (who, inner, ops.VERIFY_MAX_LABELS, shape))
+    elif labels is not None:
+        raise ValueError("%s: 'labels' without a climatology table" % who)
+    if labels is not None:
+        if tuple(np.shape(labels)) != tuple(label_shape):
+            raise ValueError("%s: 'labels' must have shape %r, got %r" % (who, tuple(label_shape), tuple(np.shape(labels))))
+        labels = ops.skill_labels(labels, table.shape[0])
+    if weights is not None:
+        weights = ops.skill_weights(weights)
+        if len(inner) < 2 or weights.size != inner[-2] or plan.run % (inner[-2] * inner[-1]):
+            raise ValueError("%s: 'weights' must hold one weight per row of the second-to-last axis of %r inside a group, got %d"
+                             % (who, inner, weights.size))
+    return table, labels, weights
+
+
+def _skill_host(fc_rows, ob_rows, plan, inner, table, labels, weights):
+    """the definition in numpy: per lead the float32 d, fa, oa of the rows the plan pairs, float64 sums -> (leads, groups, 10)"""
+    out = np.zeros((plan.leads, plan.groups, 10), np.float64)
+    grouped = plan.groups > 1 or plan.run != _prod(inner)
+    w = 1.0 if weights is None else weights.astype(np.float64).reshape(-1, 1)
+    for f in range(plan.leads):
+        cnt = max(plan.count0 - f * plan.count_dec, 0)
+        if cnt == 0:
+            continue
+        fc, ob = fc_rows(f, cnt), ob_rows(f, cnt)
+        skip = np.zeros(cnt, bool)
+        with np.errstate(invalid='ignore'):
+            d = fc - ob
+            if table is None:
+                fa, oa = fc, ob
+            else:
+                if labels is None:
+                    c = table[0]
+                else:
+                    at = f * plan.label_strides[0] + f * plan.label_strides[1]
+                    lab = labels[at:at + cnt]
+                    skip = lab < 0
+                    c = table[np.maximum(lab, 0)]
+                fa, oa = fc - c, ob - c
+        assert d.dtype == fa.dtype == oa.dtype == np.float32
+        ok = ~(np.isnan(d) | np.isnan(fa) | np.isnan(oa)) & ~skip.reshape((cnt,) + (1,) * len(inner))
+        d, fa, oa = (np.where(ok, v, np.float32(0)).astype(np.float64) for v in (d, fa, oa))
+        wk = ok * w
+        ax = tuple(a for a in range(d.ndim) if not (grouped and a == 1))
+        with np.errstate(over='ignore', invalid='ignore'):
+            terms = (wk, wk * d, wk * d * d, wk * np.abs(d), wk * fa, wk * oa, wk * fa * oa, wk * fa * fa, wk * oa * oa, ok)
+            out[f] = np.stack([np.sum(t, axis=ax, dtype=np.float64) for t in terms], axis=-1).reshape(plan.groups, 10)
+    return out
+
+
+def _skill_device(plan, named, table, labels, weights, w_inner, device):
+    from .. import ops
+    dev = _common_device([v.device for _, v in named if isinstance(v, torch.Tensor)], device)
+    if dev is None or dev.index is None:
+        dev = torch.device('cuda', torch.cuda.current_device())
+    with torch.cuda.device(dev):
+        t = {k: _to_device(v, dev) for k, v in named}
+        sums = ops.verify_skill_sums(t[plan.fc], plan.fc_strides, t[plan.ob], plan.ob_strides, plan.leads, plan.count0, plan.count_dec,
+                                     plan.groups, plan.run, climo=None if table is None else _to_device(table, dev), labels=labels,
+                                     label_strides=plan.label_strides, weights=weights, w_inner=w_inner)
+        return sums.cpu().numpy()
+
+
+def _skill(who, plan, fc_name, forecast, valid, inner, label_shape, climatology, labels, weights, axis, device, fc_rows, ob_rows):
+    named = [(fc_name, forecast), ('valid', valid)] + ([] if climatology is None else [('climatology', climatology)])
+    on_device = _wants_device(named, device)
+    table, labels, weights = _skill_extras(who, plan, inner, label_shape, climatology, labels, weights)
+    if on_device:
+        sums = _skill_device(plan, named[:2], table, labels, weights, inner[-1], device)
+    else:
+        f32 = lambda x: None if x is None else np.asarray(x).astype(np.float32, copy=False)      # noqa: E731
+        forecast, valid, table = f32(forecast), f32(valid), f32(table)
+        sums = _skill_host(lambda f, cnt: fc_rows(forecast, f, cnt), lambda f, cnt: ob_rows(valid, f, cnt), plan, inner, table, labels,
+                           weights)
+    return finish_skill(sums, axis is not None)
+
+
+def forecast_skill(forecast, valid, climatology=None, labels=None, weights=None, axis=None, device=None):
+    """Weighted skill of a time-series forecast (forecast step first) per lead -- and per variable with the `axis` tuple that keeps the
+    lead and the first inner axis -- as a Skill tuple.  `valid` carries the same leading step axis, or is the plain verification
+    series: lead f of sample i then meets valid[i + f].  climatology: None, one field of the shape of a sample row, or a (L, ...) table
+    (L <= 64) with integer `labels` of the valid times, shaped (F, N) or (Nv,) like the leading axes of `valid`, entries in [-1, L),
+    -1 skips the pair.  weights: one weight per row of the second-to-last axis (area_weights(lats)), finite, >= 0, not all zero.
+    d = forecast - valid, fa = forecast - c, oa = valid - c in float32; pairs with a NaN among them are skipped; sums in float64.
+    CUDA float32 tensors, or numpy arrays with device='cuda', are reduced on the device; any other `axis` is a ValueError."""
+    plan = plan_forecast_skill(forecast.shape, valid.shape, axis)
+    per_lead = len(forecast.shape) == len(valid.shape)
+    inner = tuple(int(s) for s in valid.shape[2 if per_lead else 1:])
+    label_shape = tuple(valid.shape[:2]) if per_lead else tuple(valid.shape[:1])
+    ob_rows = (lambda v, f, cnt: v[f, :cnt]) if per_lead else (lambda v, f, cnt: v[f:f + cnt])
+    return _skill('forecast_skill', plan, 'forecast', forecast, valid, inner, label_shape, climatology, labels, weights, axis, device,
+                  lambda x, f, cnt: x[f, :cnt], ob_rows)
+
+
+def persistence_skill(predictors, valid, n_fhour, climatology=None, labels=None, weights=None, axis=None, device=None):
+    """forecast_skill of forecasting "no change": lead f compares predictors[i] with valid[i + f]; `labels` (Nv,) follow `valid`"""
+    plan = plan_persistence_skill(predictors.shape, valid.shape, n_fhour, axis)
+    inner = tuple(int(s) for s in valid.shape[1:])
+    return _skill('persistence_skill', plan, 'predictors', predictors, valid, inner, tuple(valid.shape[:1]), climatology, labels,
+                  weights, axis, device, lambda x, f, cnt: x[:cnt], lambda v, f, cnt: v[f:f + cnt])

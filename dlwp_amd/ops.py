@@ -1773,6 +1773,101 @@ def verify_error_sums(a, a_strides, b, b_strides, leads, count0, count_dec, grou
     return sums
 
 
+SKILL_SUMS = 10
+
+
+def verify_label_extent(strides, leads, count0, count_dec):
+    """Labels dlwp_verify_skill_sums reads through strides = (lead_stride, shift): one past the last index of a lead with pairs"""
+    ls, shift = (int(v) for v in strides)
+    need = 0
+    for f in range(int(leads)):
+        cnt = int(count0) - f * int(count_dec)
+        if cnt <= 0:
+            break
+        need = max(need, f * ls + cnt - 1 + f * shift + 1)
+    return need
+
+
+def skill_labels(labels, n_labels):
+    """HOST labels of dlwp_verify_skill_sums as a flat int32 array: an integer dtype, every entry in [-1, n_labels), -1 = skip the
+    pair.  ValueError otherwise."""
+    labels = np.asarray(labels)
+    if labels.dtype.kind not in 'iu':
+        raise ValueError('verify_skill_sums: labels must be integers, got %s' % labels.dtype)
+    if labels.size and (int(labels.min()) < -1 or int(labels.max()) >= int(n_labels)):
+        raise ValueError('verify_skill_sums: labels must lie in [-1, %d), got %d .. %d' % (n_labels, labels.min(), labels.max()))
+    return np.ascontiguousarray(labels.reshape(-1), dtype=np.int32)
+
+
+def skill_weights(weights):
+    """HOST weights of dlwp_verify_skill_sums as a float32 array: 1-D, finite, >= 0 and not all zero.  ValueError otherwise."""
+    weights = np.asarray(weights)
+    if weights.ndim != 1 or weights.size < 1 or weights.dtype.kind not in 'fiu':
+        raise ValueError('verify_skill_sums: weights must be a 1-D real array, got %s of shape %r' % (weights.dtype, weights.shape))
+    weights = np.ascontiguousarray(weights, dtype=np.float32)
+    if not np.isfinite(weights).all():
+        raise ValueError('verify_skill_sums: weights must be finite')
+    if (weights < 0).any():
+        raise ValueError('verify_skill_sums: weights must be >= 0, got %g' % weights.min())
+    if not (weights > 0).any():
+        raise ValueError('verify_skill_sums: weights are all zero')
+    return weights
+
+
+def verify_skill_sums(fc, fc_strides, ob, ob_strides, leads, count0, count_dec, groups, run, climo=None, labels=None,
+                      label_strides=(0, 0), weights=None, w_inner=1):
+    """include/dlwp_hip.h: dlwp_verify_skill_sums.  fc, ob: contiguous float32 device tensors read as flat arrays through
+    x_strides = (lead_stride, sample_stride, shift) in elements, as in verify_error_sums.  climo: a (n_labels, ...) float32 device
+    tensor whose rows hold groups * run floats, or None; labels: a HOST integer array read flat through label_strides =
+    (lead_stride, shift), entries in [-1, n_labels) with -1 = skip the pair, or None (label 0); weights: a HOST 1-D array, finite,
+    >= 0, not all zero -- element e of a run has weight weights[(e // w_inner) % len(weights)] -- or None.  Labels and weights are
+    checked here and then uploaded.  Returns a NEW (leads, groups, 10) float64 device tensor: sum w, w d, w d^2, w |d|, w fa, w oa,
+    w fa oa, w fa^2, w oa^2 and the pairs counted (d = fc - ob, fa = fc - c, oa = ob - c), enqueued on the current stream."""
+    _check_f32(fc, ob, climo)
+    d = _dev(fc)
+    if _dev(ob) != d or (climo is not None and _dev(climo) != d):
+        raise ValueError('verify_skill_sums: operands on different devices')
+    leads, count0, count_dec, groups, run = int(leads), int(count0), int(count_dec), int(groups), int(run)
+    if (leads < 1 or groups < 1 or run < 1 or count_dec < 0 or min(fc_strides) < 0 or min(ob_strides) < 0
+            or min(label_strides) < 0):
+        raise ValueError('verify_skill_sums: leads, groups, run must be >= 1; strides, shifts and count_dec >= 0')
+    for name, t, st in (('fc', fc, fc_strides), ('ob', ob, ob_strides)):
+        need = verify_extent(st, leads, count0, count_dec, groups, run)
+        if need > t.numel():
+            raise ValueError('verify_skill_sums: operand %s holds %d elements, the strides address %d' % (name, t.numel(), need))
+    n_labels = 0
+    if climo is not None:
+        n_labels, trow = _rows_of(climo, 'verify_skill_sums')
+        if trow != groups * run:
+            raise ValueError('verify_skill_sums: table rows of %d floats, sample rows of %d' % (trow, groups * run))
+        if n_labels > VERIFY_MAX_LABELS:
+            raise ValueError('verify_skill_sums: %d labels, at most %d' % (n_labels, VERIFY_MAX_LABELS))
+    elif labels is not None:
+        raise ValueError('verify_skill_sums: labels without a climatology table')
+    if labels is not None:
+        labels = skill_labels(labels, n_labels)
+        need = verify_label_extent(label_strides, leads, count0, count_dec)
+        if need > labels.size:
+            raise ValueError('verify_skill_sums: %d labels, the strides address %d' % (labels.size, need))
+    w_len, w_inner = 0, int(w_inner)
+    if weights is not None:
+        weights = skill_weights(weights)
+        w_len = int(weights.size)
+        if w_inner < 1 or run % (w_inner * w_len):
+            raise ValueError('verify_skill_sums: %d weights of %d elements each do not divide a run of %d' % (w_len, w_inner, run))
+    h = _lib.handle(d)
+    labels_d = None if labels is None else torch.from_numpy(labels).to(fc.device)
+    weights_d = None if weights is None else torch.from_numpy(weights).to(fc.device)
+    ws = torch.empty(max(int(_lib.lib.dlwp_verify_skill_workspace(h, leads, groups)), 8), dtype=torch.uint8, device=fc.device)
+    sums = torch.empty((leads, groups, SKILL_SUMS), dtype=torch.float64, device=fc.device)
+    _lib.check(_lib.lib.dlwp_verify_skill_sums(h, _ptr(fc), int(fc_strides[0]), int(fc_strides[1]), int(fc_strides[2]),
+                                               _ptr(ob), int(ob_strides[0]), int(ob_strides[1]), int(ob_strides[2]),
+                                               leads, count0, count_dec, groups, run, _ptr(climo), n_labels, _ptr(labels_d),
+                                               int(label_strides[0]), int(label_strides[1]), _ptr(weights_d), w_len, w_inner,
+                                               _ptr(sums), _ptr(ws), ws.numel(), _stream(fc)))
+    return sums
+
+
 def verify_nanmean_samples(x):
     """include/dlwp_hip.h: dlwp_verify_nanmean_samples.  x: (count, ...) contiguous float32 device tensor -> a NEW float32 tensor
     of x.shape[1:], the NaN-skipping mean over the first axis (float64 sums in sample order; NaN where no sample is finite-or-inf)."""

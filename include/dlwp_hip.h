@@ -1148,6 +1148,40 @@ int dlwp_verify_label_error_sums(dlwp_handle_t, const void* x, int count_x, long
 int dlwp_gather_rows_fill(dlwp_handle_t, const void* src, long long src_rows, long long row, const void* rows, long long n, void* dst,
                           void* stream);
 
+/* ---- latitude-weighted forecast skill (csrc/skill.hip; no counterpart in the reference module, which stops at unweighted mse / mae /
+ *      rmse; the anomaly correlation is the reference's training metric, DLWP/custom.py anomaly_correlation).  dlwp_verify_skill_sums
+ *      reads a forecast fc and an observation ob addressed exactly as a and b of dlwp_verify_error_sums (strides in ELEMENTS, all
+ *      >= 0; lead f has count_f = max(count0 - f * count_dec, 0) pairs of sample rows; row i of operand x starts at
+ *      x + f * x_lead_stride + (i + f * x_shift) * x_sample_stride; a sample row is groups x run contiguous floats) and adds
+ *        a climatology: climo (n_labels, groups * run) float32, n_labels in 1 .. 64, NULL = zero; labels a DEVICE int32 array, the
+ *          label of pair (f, i) is labels[f * label_lead_stride + i + f * label_shift], NULL = label 0.  A label outside
+ *          [0, n_labels) skips the pair and is never used as an address.  c = climo[label][position of the pair in its row];
+ *        weights: w_len DEVICE floats, NULL = all ones; element e of a group's run has weight weights[(e / w_inner) % w_len], and
+ *          run % (w_inner * w_len) == 0.  For an (..., H, W) row: w_len = H, w_inner = W.
+ *      Per pair d = fc - ob, fa = fc - c, oa = ob - c are each rounded once in float32 (fa, oa are the inputs themselves without a
+ *      table); a pair with a NaN among d, fa, oa is skipped in every sum and in the count, infinities follow IEEE; everything behind
+ *      that is float64.  sums (device, (leads, groups, 10) float64) <-
+ *        0: sum w      1: sum w d     2: sum w d^2    3: sum w |d|    4: sum w fa
+ *        5: sum w oa   6: sum w fa oa 7: sum w fa^2   8: sum w oa^2   9: pairs counted
+ *      and a lead without pairs launches no work and reports ten zeros.  The tree is dlwp_verify_error_sums': per-thread float64
+ *      sums and a 64-bit count, lanes, waves through LDS, one partial (ten doubles) per block in ws, a second kernel that adds the
+ *      partials of a cell in index order; no atomics, no host synchronisation, identical bits on repeated calls; max(1, 8 * CUs /
+ *      cells) blocks per cell over the cells of the leads that have pairs.  16-byte loads when run and the four operand strides are
+ *      multiples of 4 and fc, ob, climo are 16-byte aligned, scalar loads otherwise; with 16-byte loads the weight is looked up once
+ *      per unit when w_inner % 4 == 0 and per element otherwise (a unit may then straddle two latitude rows).
+ *      dlwp_verify_skill_workspace returns leads * groups * B * 80 bytes, B = ceil(8 * CUs / (leads * groups)) (a NULL handle counts
+ *      256 CUs); ws must be 8-byte aligned.  Refused without a launch, in this order: sizes < 1; negative strides, shifts or
+ *      count_dec; n_labels outside 1 .. 64 with a table; labels without a table; w_len < 1, w_inner < 1 or a run they do not
+ *      divide, with weights; null fc, ob or sums; more than 2^20 cells; a workspace too small or misaligned; a null handle.
+ *      The caller guarantees that every addressed element exists (dlwp_amd.ops.verify_skill_sums checks it).  Marks a recording
+ *      tape foreign.                                                                                                        */
+size_t dlwp_verify_skill_workspace(dlwp_handle_t, int leads, int groups);
+int dlwp_verify_skill_sums(dlwp_handle_t, const void* fc, long long fc_lead_stride, long long fc_sample_stride, int fc_shift,
+                           const void* ob, long long ob_lead_stride, long long ob_sample_stride, int ob_shift, int leads, int count0,
+                           int count_dec, int groups, long long run, const void* climo, int n_labels, const void* labels,
+                           long long label_lead_stride, int label_shift, const void* weights, int w_len, long long w_inner,
+                           void* sums, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- batches of a series generator cut out of an HBM-resident series (csrc/series.hip; DLWP/model/generators.py:323-629,
  *      SeriesDataGenerator.generate).  One launch fills X and every target block of a batch:
  *        dst[g.dst][i * row_d + g.dst_at + e] = src[g.src][(samples[i] + g.shift) * row_s + g.src_at + e],  e < g.len, i < n
