@@ -74,14 +74,19 @@ struct ConvArgs {
   int ksplit = 0, kchunks = 0;
   float* kslab = nullptr;
   unsigned* kcount = nullptr;
-#ifdef DLWP_PHASE_TIMING  // tools/microbench/wino_phase_timing.hip only: s_memtime stamps of wave 0, 8 per block
+  // Winograd forward body (conv_fwd_wino_kernel.h): exact reciprocals (multiplier, shift: wino_div) of tiles_w, tiles_h,
+  // cout_tiles and of an edge-pair launch's blocks per image, filled by wino_derive in the launch thunks -- the block
+  // decomposition stays on the scalar unit and never divides
+  unsigned rcp_tw = 0, rcp_th = 0, rcp_ct = 0, rcp_per = 0;
+  int rsh_tw = 31, rsh_th = 31, rsh_ct = 31, rsh_per = 31;
+#ifdef DLWP_PHASE_TIMING  // tools/microbench/wino_phase_timing.hip only: s_memtime stamps of wave 0, 16 slots per block
   long long* dbg = nullptr;
 #endif
 };
 #ifdef DLWP_PHASE_TIMING
 #define DLWP_STAMP(k)                                                                                   \
   do {                                                                                                  \
-    if (a.dbg && threadIdx.x == 0) a.dbg[(long long)blockIdx.x * 8 + (k)] = __builtin_amdgcn_s_memtime(); \
+    if (a.dbg && threadIdx.x == 0) a.dbg[(long long)blockIdx.x * 16 + (k)] = __builtin_amdgcn_s_memtime(); \
   } while (0)
 #else
 #define DLWP_STAMP(k) do { } while (0)

@@ -54,7 +54,7 @@ int launch_flat(const ConvArgs& a, int grid, hipStream_t s) {
                                         C::LDS_BYTES);
   if (prepared > 0) return prepared;
   prepared = 0;
-  hipLaunchKernelGGL((conv2d_fwd_wino_flat_f32<C>), dim3(grid), dim3(C::NT), C::LDS_BYTES, s, a);
+  hipLaunchKernelGGL((conv2d_fwd_wino_flat_f32<C>), dim3(grid), dim3(C::NT), C::LDS_BYTES, s, wino_derive(a));
   return 0;
 }
 

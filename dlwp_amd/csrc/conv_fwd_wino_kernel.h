@@ -132,6 +132,10 @@ struct WinoCfg {
   static constexpr int NUI = (CK * BN) / NT;       // (ci, co) filter items per thread
   static constexpr int NWI = 4 * NUI;              // float4 filter loads per thread and chunk
   static constexpr int HL = 16 * BNF;               // MFMAs per channel group
+  // accumulators (of the 16 positions) cleared under the memory latency of chunk 0; the others are cleared where the compiler
+  // puts them, in front of the loop: the prologue's temporaries -- chunk 1's loads, the first input transform -- need their
+  // registers, or the kernel's register count rises above the loop's own 214
+  static constexpr int ACC_EARLY = 12;
   // BNF = 2: two waves per SIMD (256 VGPRs each).  BNF = 4 (64 output channels per block: the input tile staged and
   // transformed once for twice the matrix work, 256 accumulator registers, ONE wave per SIMD) compiles but measured 1.56x
   // SLOWER on the 128->64 layer (1.075 vs 0.689 ms): a single wave cannot cover its own waits; no instance is registered.
@@ -144,6 +148,31 @@ struct WinoCfg {
   static_assert(LDS_BYTES <= 160 * 1024, "LDS tile too large");
 };
 
+// n / d without a division, for 0 <= n < 2^31 and the divisors of a launch's block decomposition (tiles per row, tile rows or runs
+// per image, blocks per image of an edge-pair launch, output-channel tiles): with l = ceil(log2 d), sh = 31 + l and
+// m = ceil(2^sh / d) -- which is below 2^32 because 2^(l-1) < d -- the product n m = n 2^sh / d + n e / d with e = m d - 2^sh < d
+// <= 2^l, and n e < 2^sh, so floor(n m / 2^sh) = floor(n / d) for EVERY such n: exact, not "exact over the grid".  On uniform
+// operands it is s_mul_hi_u32 + s_mul_i32 + s_lshr_b64; per lane v_mad_u64_u32 + v_lshrrev_b64.
+__host__ __device__ __forceinline__ int wino_div(int n, unsigned m, int sh) {
+  return (int)(unsigned)(((unsigned long long)(unsigned)n * m) >> sh);
+}
+inline void wino_reciprocal(int d, unsigned* m, int* sh) {
+  int l = 0;
+  while ((1ll << l) < (long long)d) ++l;
+  *sh = 31 + l;
+  *m = d > 0 ? (unsigned)(((1ull << *sh) + (unsigned long long)d - 1) / (unsigned long long)d) : 0u;
+}
+// The launch thunks' last word on a ConvArgs: the reciprocals of whatever tiles_h / tiles_w / cout_tiles the host logic settled on
+// (every launch of the body goes through one of them: wino_launch_thunk, the split-K and flat-run launchers, the fused pair).
+inline ConvArgs wino_derive(const ConvArgs& a) {
+  ConvArgs d = a;
+  wino_reciprocal(a.tiles_w, &d.rcp_tw, &d.rsh_tw);
+  wino_reciprocal(a.tiles_h, &d.rcp_th, &d.rsh_th);
+  wino_reciprocal(a.cout_tiles, &d.rcp_ct, &d.rsh_ct);
+  wino_reciprocal(a.tiles_w * (a.tiles_h - 1) + ((a.tiles_w + 1) >> 1), &d.rcp_per, &d.rsh_per);
+  return d;
+}
+
 // The kernel's body: workgroup `blk` of `nblk` (r4: a function of its own so that conv_pair.hip can run it beside a weight-gradient
 // body in ONE launch; conv2d_fwd_wino_f32 below is this body on blockIdx.x / gridDim.x -- the same code after inlining).
 template <class C>
@@ -155,9 +184,26 @@ __device__ __forceinline__ void conv2d_fwd_wino_body(const ConvArgs& a, const in
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   DLWP_STAMP(0);
 
+  // ---- which block this is.  Every value here is the same for all lanes: it is kept on the SCALAR unit (blk / nblk are pinned to
+  //      SGPRs) and never divides at run time -- the quotients by the launch's divisors are a multiply and a shift with the exact
+  //      reciprocals the launch thunks put into ConvArgs (wino_derive below; wino_div).  The vector ALU's division -- a
+  //      v_cvt / v_rcp_iflag / v_cvt chain and a v_readfirstlane per quotient, five of them -- stood in front of the first
+  //      global load, each instruction waiting its turn behind the co-resident wave's MFMAs.
+  // One argument fetch: every ConvArgs field the set-up reads is asked for here, in one round of scalar loads behind one wait
+  // (left to itself the compiler fetches each where its basic block first needs it: three to five dependent rounds, each a
+  // scalar-cache round trip in front of the first global load).
+#define DLWP_WINO_PIN(f) asm volatile("" ::"s"(a.f))
+  DLWP_WINO_PIN(x); DLWP_WINO_PIN(w); DLWP_WINO_PIN(Cin); DLWP_WINO_PIN(Hs); DLWP_WINO_PIN(Ws); DLWP_WINO_PIN(H); DLWP_WINO_PIN(W);
+  DLWP_WINO_PIN(Cout); DLWP_WINO_PIN(in_c_off); DLWP_WINO_PIN(in_c_total); DLWP_WINO_PIN(pad_top); DLWP_WINO_PIN(pad_left);
+  DLWP_WINO_PIN(mode_h); DLWP_WINO_PIN(mode_w); DLWP_WINO_PIN(src_mode); DLWP_WINO_PIN(tiles_h); DLWP_WINO_PIN(tiles_w);
+  DLWP_WINO_PIN(cout_tiles); DLWP_WINO_PIN(col0); DLWP_WINO_PIN(pair_vw); DLWP_WINO_PIN(rcp_tw); DLWP_WINO_PIN(rcp_th);
+  DLWP_WINO_PIN(rcp_ct); DLWP_WINO_PIN(rcp_per); DLWP_WINO_PIN(rsh_tw); DLWP_WINO_PIN(rsh_th); DLWP_WINO_PIN(rsh_ct);
+  DLWP_WINO_PIN(rsh_per);
+#undef DLWP_WINO_PIN
+  asm volatile("" ::"s"(nblk));   // (the grid size is a kernel argument too)
   int L;
   {
-    const int b = blk, nb = nblk;
+    const int b = __builtin_amdgcn_readfirstlane(blk), nb = __builtin_amdgcn_readfirstlane(nblk);
     const int xcd = b & 7, idx = b >> 3, q = nb >> 3, r = nb & 7;
     L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
   }
@@ -176,27 +222,31 @@ __device__ __forceinline__ void conv2d_fwd_wino_body(const ConvArgs& a, const in
   [[maybe_unused]] const int ftiles = ((a.Ho + 1) >> 1) * a.tiles_w;
   [[maybe_unused]] int ft0 = 0, fr0 = 0;
   if constexpr (C::FLAT) {
-    const int run = L % a.tiles_h;
-    L /= a.tiles_h;
+    const int img = wino_div(L, a.rcp_th, a.rsh_th);
+    const int run = L - img * a.tiles_h;
+    L = img;
     ft0 = run * C::T;
-    fr0 = ft0 / a.tiles_w;
+    fr0 = wino_div(ft0, a.rcp_tw, a.rsh_tw);
     th = tw = 0;
   } else if constexpr (C::EP) {
     const int full = a.tiles_w * (a.tiles_h - 1), per = full + ((a.tiles_w + 1) >> 1);
-    const int t = L % per;
-    L /= per;
+    const int img = wino_div(L, a.rcp_per, a.rsh_per);
+    const int t = L - img * per;
+    L = img;
     ep = t >= full;
-    th = ep ? a.tiles_h - 1 : t / a.tiles_w;
+    th = ep ? a.tiles_h - 1 : wino_div(t, a.rcp_tw, a.rsh_tw);
     tw = ep ? 2 * (t - full) : t - th * a.tiles_w;
   } else {
-    tw = L % a.tiles_w;
-    L /= a.tiles_w;
-    th = L % a.tiles_h;
-    L /= a.tiles_h;
+    int qd = wino_div(L, a.rcp_tw, a.rsh_tw);
+    tw = L - qd * a.tiles_w;
+    L = qd;
+    qd = wino_div(L, a.rcp_th, a.rsh_th);
+    th = L - qd * a.tiles_h;
+    L = qd;
   }
   constexpr int HR = C::TH / 2 + 2 * C::DIL;    // EP: input rows of one half (4 output rows + halo)
-  const int ct = L % a.cout_tiles;
-  const int n = L / a.cout_tiles;
+  const int n = wino_div(L, a.rcp_ct, a.rsh_ct);
+  const int ct = L - n * a.cout_tiles;
   const int i0 = th * C::TH, j0 = a.col0 + tw * C::TW, n0 = ct * C::BN;
 
   // ---- input loader bookkeeping: byte offset inside a channel plane (0x7ffffff0 = out of range = reads 0) and the LDS
@@ -293,54 +343,9 @@ __device__ __forceinline__ void conv2d_fwd_wino_body(const ConvArgs& a, const in
   const int n_s = a.pair_vw ? 2 * n : n;          // first (only) sample of this block
   const char* xn = (const char*)a.x + ((long long)n_s * a.in_c_total + a.in_c_off + c_base) * plane * ESZ;
   const unsigned plane_bytes = (unsigned)plane * ESZ;
-
-  // ---- this lane's tile (= its MFMA A-operand row) and the LDS offset of the tile's 4x4 patch origin, channel l>>4
-  int v_src;
-  if constexpr (C::FLAT) {
-    // tile g of the image: tile row g / tiles_w (LDS row 2 (row - fr0); up-sampled source: the patch's source rows are LDS rows
-    // row - fr0 + {0, 1, 1, 2}, see vt_read), tile column tc: LDS column 2 tc (up-sampled: up-sampled column 2 tc - 1 = slot 2 tc + 2).
-    // Tiles past the image compute tile ft0 again and are not stored.
-    int g = ft0 + wave * 16 + (lane & 15);
-    if (g >= ftiles) g = ft0;
-    const int tr = g / a.tiles_w, tc = g - tr * a.tiles_w;
-    v_src = (lane >> 4) * C::PS + (C::UPS ? (tr - fr0) : 2 * (tr - fr0)) * C::LCP + 2 * tc + (C::UPS ? 2 : 0);
-  } else {
-    const int t = wave * 16 + (lane & 15);
-    const int tt = t < C::T ? t : 0;
-    const int pc = tt / (C::RTH * C::RTW), rem = tt - pc * (C::RTH * C::RTW);
-    const int ti = rem / C::RTW, tj = rem - ti * C::RTW;
-    const int pi = pc / C::DIL, pj = pc - pi * C::DIL;
-    // (EP, edge pair: tile row ti = wave w holds rows 2 (w & 1), + 1 of half w >> 1, whose input rows start at LDS row HR (w >> 1))
-    const int trow = (C::EP && ep) ? HR * (ti >> 1) + 2 * (ti & 1) : ti * 2;
-    v_src = (lane >> 4) * C::PS + ((pi * C::DIL + pj) * C::LRP + trow + C::XROW0) * C::LCP + tj * 2 + C::XCOL0;
-  }
-  // ---- filter items -> (ci, co): byte offset in the transformed filter (chunk 0, xy quad 0) and LDS slot
-  unsigned u_off[C::NUI];
-  int u_dst[C::NUI];
-#pragma unroll
-  for (int k = 0; k < C::NUI; ++k) {
-    const int e = tid + k * C::NT;
-    const int ci = e / C::BN, co = e - ci * C::BN;
-    u_off[k] = (unsigned)((ci * 4 * a.Cout + n0 + co) * 16);
-    u_dst[k] = (ci * C::BN + co) * 4;
-  }
-  const __amdgpu_buffer_rsrc_t u_rsrc =
-      __builtin_amdgcn_make_buffer_rsrc((void*)(a.w + (long long)c_base * a.Cout * 16), 0, cin_l * a.Cout * 64, 0x00020000);
-  const int b_lane = ((lane >> 4) * C::BN + (lane & 15)) * 4;
   const int last_c0 = ((cin_l + C::CK - 1) / C::CK - 1) * C::CK;   // (Cin may be ragged: the planes past it read 0)
-
-  // (Measured, r2e: starting the accumulation from a literal-zero C operand in a peeled first chunk instead of clearing the
-  // accumulators -- 128 v_mov per lane -- costs 23 registers and a third copy of the loop body and gained nothing.)
-  f32x4 acc[16][C::BNF];
-#pragma unroll
-  for (int xy = 0; xy < 16; ++xy)
-#pragma unroll
-    for (int g = 0; g < C::BNF; ++g)
-      if (!(C::UPS && (xy / 4 == 2 || xy % 4 == 2))) acc[xy][g] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
   float xr[C::CK][C::XRW];
   float xq[C::UPSQ ? C::NQ : 1];
-  f32x4 ur[C::NUI][2];  // two xy quads at a time: (0,1) loaded a chunk ahead, (2,3) half a chunk ahead
   // element i of the chunk starting at channel c0 (uniform; clamped to the last chunk).  ONE buffer descriptor for the
   // sample's channel window (num_records = Cin planes); the channel is selected by the SCALAR offset, so a load costs one
   // s_add instead of ~10 scalar instructions of per-plane descriptor arithmetic -- the wave's own issue slots are what
@@ -365,6 +370,81 @@ __device__ __forceinline__ void conv2d_fwd_wino_body(const ConvArgs& a, const in
     else
       xr[ci][q] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(x_rsrc, goff[q], soff, 0));
   };
+  auto load_q = [&](int c0, int k) {      // UPSQ: source element k of the chunk starting at channel c0
+    xq[k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(x_rsrc, qoff[k], (unsigned)min(c0, last_c0) * plane_bytes, 0));
+  };
+  // ---- loads first: the input tile of chunk 0 leaves as soon as its addresses exist, then all four filter quads; everything the
+  //      loads do not need -- patch origin, LDS read bases, the 128 accumulator clears -- runs BEHIND them, under their latency
+  //      (it used to stand in front: ~370 instructions, issued in the slots a co-resident wave's loop leaves, before the first
+  //      byte was asked for).  The scheduling fences keep the compiler from sinking the loads to their first use again.
+  if constexpr (C::UPSQ) {
+#pragma unroll
+    for (int k = 0; k < C::NQ; ++k) load_q(0, k);
+  } else {
+#pragma unroll
+    for (int i = 0; i < C::NXI; ++i) load_x(0, i);
+  }
+  // ---- filter items -> (ci, co): byte offset in the transformed filter (chunk 0, xy quad 0) and LDS slot
+  unsigned u_off[C::NUI];
+  int u_dst[C::NUI];
+#pragma unroll
+  for (int k = 0; k < C::NUI; ++k) {
+    const int e = tid + k * C::NT;
+    const int ci = e / C::BN, co = e - ci * C::BN;
+    u_off[k] = (unsigned)((ci * 4 * a.Cout + n0 + co) * 16);
+    u_dst[k] = (ci * C::BN + co) * 4;
+  }
+  const __amdgpu_buffer_rsrc_t u_rsrc =
+      __builtin_amdgcn_make_buffer_rsrc((void*)(a.w + (long long)c_base * a.Cout * 16), 0, cin_l * a.Cout * 64, 0x00020000);
+  f32x4 up[C::NUI][4];   // (the loop's two filter staging slots would serialise three memory latencies here; the prologue has the
+                         //  registers for all four quads)
+#pragma unroll
+  for (int k = 0; k < C::NUI; ++k)
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      if (!(C::UPS && r == 2))
+        up[k][r] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(u_rsrc, u_off[k], r * a.Cout * 16, 0));
+  __builtin_amdgcn_sched_barrier(0);
+  DLWP_STAMP(7);
+
+  // ---- this lane's tile (= its MFMA A-operand row) and the LDS offset of the tile's 4x4 patch origin, channel l>>4
+  int v_src;
+  if constexpr (C::FLAT) {
+    // tile g of the image: tile row g / tiles_w (LDS row 2 (row - fr0); up-sampled source: the patch's source rows are LDS rows
+    // row - fr0 + {0, 1, 1, 2}, see vt_read), tile column tc: LDS column 2 tc (up-sampled: up-sampled column 2 tc - 1 = slot 2 tc + 2).
+    // Tiles past the image compute tile ft0 again and are not stored.
+    int g = ft0 + wave * 16 + (lane & 15);
+    if (g >= ftiles) g = ft0;
+    const int tr = wino_div(g, a.rcp_tw, a.rsh_tw), tc = g - tr * a.tiles_w;
+    v_src = (lane >> 4) * C::PS + (C::UPS ? (tr - fr0) : 2 * (tr - fr0)) * C::LCP + 2 * tc + (C::UPS ? 2 : 0);
+  } else {
+    const int t = wave * 16 + (lane & 15);
+    const int tt = t < C::T ? t : 0;
+    const int pc = tt / (C::RTH * C::RTW), rem = tt - pc * (C::RTH * C::RTW);
+    const int ti = rem / C::RTW, tj = rem - ti * C::RTW;
+    const int pi = pc / C::DIL, pj = pc - pi * C::DIL;
+    // (EP, edge pair: tile row ti = wave w holds rows 2 (w & 1), + 1 of half w >> 1, whose input rows start at LDS row HR (w >> 1))
+    const int trow = (C::EP && ep) ? HR * (ti >> 1) + 2 * (ti & 1) : ti * 2;
+    v_src = (lane >> 4) * C::PS + ((pi * C::DIL + pj) * C::LRP + trow + C::XROW0) * C::LCP + tj * 2 + C::XCOL0;
+  }
+  const int b_lane = ((lane >> 4) * C::BN + (lane & 15)) * 4;
+
+  // (Measured, r2e: starting the accumulation from a literal-zero C operand in a peeled first chunk instead of clearing the
+  // accumulators -- 128 v_mov per lane -- costs 23 registers and a third copy of the loop body and gained nothing.)
+  f32x4 acc[16][C::BNF];
+#pragma unroll
+  for (int xy = 0; xy < 16; ++xy)
+#pragma unroll
+    for (int g = 0; g < C::BNF; ++g)
+      if (!(C::UPS && (xy / 4 == 2 || xy % 4 == 2))) {
+        acc[xy][g] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        // (pinned HERE: left to itself the compiler re-materialises the zeros in the loop's preheader, behind every wait of the
+        //  prologue -- 128 v_mov with nothing to hide behind instead of 128 v_mov under the memory latency of chunk 0)
+        if (xy < C::ACC_EARLY) asm volatile("" : "+v"(acc[xy][g]));
+      }
+  __builtin_amdgcn_sched_barrier(0);
+
+  f32x4 ur[C::NUI][2];  // two xy quads at a time: (0,1) loaded a chunk ahead, (2,3) half a chunk ahead
   auto load_u = [&](int c0, int k, int r) {
     if (C::UPS && r == 2) return;  // (r is an unrolled constant)
     const int soff = (min(c0, last_c0) * 4 + r) * a.Cout * 16;
@@ -380,9 +460,6 @@ __device__ __forceinline__ void conv2d_fwd_wino_body(const ConvArgs& a, const in
       lds[xdst + ci * C::PS + loff1[q]] = xr[ci][2 * q + 1];
     } else
       lds[xdst + ci * C::PS + loff[q]] = C::IN16 ? bf16_bits_to_f32(__builtin_bit_cast(unsigned, xr[ci][q])) : xr[ci][q];
-  };
-  auto load_q = [&](int c0, int k) {      // UPSQ: source element k of the chunk starting at channel c0
-    xq[k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(x_rsrc, qoff[k], (unsigned)min(c0, last_c0) * plane_bytes, 0));
   };
   auto stage_q = [&](int xdst, int j) {   // ... into slot j & 3 of element j >> 2: (row, column) = (j >> 1 & 1, j & 1)
     const int k = j >> 2;
@@ -434,24 +511,8 @@ __device__ __forceinline__ void conv2d_fwd_wino_body(const ConvArgs& a, const in
   };
 
   // ---- prologue: chunk 0 staged, chunk 1 in registers, V(group 0, chunk 0) and the first B fragments loaded
-  //      Every global load of chunk 0 -- the input tile AND all four filter quads -- is in flight before the first wait
-  //      (the loop's two filter staging slots would serialise three memory latencies here; the prologue has the registers
-  //      for all four quads, nothing else is live yet).
-  if constexpr (C::UPSQ) {
-#pragma unroll
-    for (int k = 0; k < C::NQ; ++k) load_q(0, k);
-  } else {
-#pragma unroll
-    for (int i = 0; i < C::NXI; ++i) load_x(0, i);
-  }
+  //      (every global load of chunk 0 -- the input tile AND all four filter quads -- has been in flight since "loads first" above)
   {
-    f32x4 up[C::NUI][4];
-#pragma unroll
-    for (int k = 0; k < C::NUI; ++k)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        if (!(C::UPS && r == 2))
-          up[k][r] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(u_rsrc, u_off[k], r * a.Cout * 16, 0));
     if constexpr (C::UPSQ) {
 #pragma unroll
       for (int j = 0; j < 4 * C::NQ; ++j) stage_q(0, j);
@@ -466,6 +527,7 @@ __device__ __forceinline__ void conv2d_fwd_wino_body(const ConvArgs& a, const in
         if (!(C::UPS && r == 2))
           *(f32x4*)(lds + US0 + u_dst[k] + (C::UPS && r == 3 ? 2 : r) * C::CK * C::BN * 4) = up[k][r];
   }
+  DLWP_STAMP(8);
   __syncthreads();
   if constexpr (C::UPSQ) {
 #pragma unroll
@@ -724,7 +786,7 @@ __device__ __forceinline__ void conv2d_fwd_wino_body(const ConvArgs& a, const in
     //      width: the rows are not 8-byte aligned; the column past an odd width is dropped)
     static_assert(C::NT == 4 * C::T, "one thread per (channel parity, tile row, tile)");
     const int t = tid & (C::T - 1), aa = (tid / C::T) & 1, cb = tid / (2 * C::T);
-    const int g = ft0 + t, tr = g / a.tiles_w, tc = g - tr * a.tiles_w;
+    const int g = ft0 + t, tr = wino_div(g, a.rcp_tw, a.rsh_tw), tc = g - tr * a.tiles_w;
     const int oh = 2 * tr + aa, ow = 2 * tc;
     const unsigned plane_b = (unsigned)(a.Ho * a.Wo) * 4u;
     float* yb = a.y + ((long long)n * a.out_c_total + a.out_c_off + n0) * a.Ho * a.Wo;
@@ -1084,7 +1146,7 @@ DLWP_WINO_SPLITK_DECL(1, 4, 32, 2, 2)
 
 template <class C>
 static void wino_launch_thunk(const ConvArgs& a, int grid, hipStream_t s) {
-  hipLaunchKernelGGL((conv2d_fwd_wino_f32<C>), dim3(grid), dim3(C::NT), C::LDS_BYTES, s, a);
+  hipLaunchKernelGGL((conv2d_fwd_wino_f32<C>), dim3(grid), dim3(C::NT), C::LDS_BYTES, s, wino_derive(a));
 }
 
 template <class C>

@@ -61,7 +61,7 @@ int launch_pair(const dlwp_pair_state& p, hipStream_t s) {
                                : 0;
   if (prepared != 0) return -1;
   const int nw_pad = (p.w_grid + 7) & ~7;
-  hipLaunchKernelGGL((conv2d_pair_wgrad_dgrad_f32<CW, CF>), dim3(nw_pad + p.f_grid), dim3(NT), LDS, s, p.wa, p.fa, p.w_grid, nw_pad);
+  hipLaunchKernelGGL((conv2d_pair_wgrad_dgrad_f32<CW, CF>), dim3(nw_pad + p.f_grid), dim3(NT), LDS, s, p.wa, wino_derive(p.fa), p.w_grid, nw_pad);
   return 1;
 }
 

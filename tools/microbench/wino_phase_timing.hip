@@ -1,15 +1,23 @@
-// wino_phase_timing.hip -- where does a block of the Winograd forward kernel spend its life?  s_memtime stamps of wave 0:
-//   0 entry | 1 prologue done (index math, chunk 0 staged, chunk 1 in flight, first transform) | 2 loop done |
-//   3 barrier | 4 output transform + activation written to LDS | 5 barrier | 6 stores issued
-// Shapes = the cfg2 U-Net layers that run the 16-position instance at 256 members (layer 2: 32->64 @44x90 with the pooling
-// epilogue; restated layer 5: 64->32 @44x90).  Random data; only the timing is meaningful.
-// Build: hipcc -O3 -std=c++17 -fno-slp-vectorize --offload-arch=gfx950 -DDLWP_PHASE_TIMING -o wino_phase_timing.bin wino_phase_timing.hip
-#include "../../dlwp_amd/csrc/conv_fwd_wino_kernel.h"
+// wino_phase_timing.hip -- where does a block of the Winograd forward kernel spend its life?  s_memtime stamps of wave 0
+// (DLWP_STAMP in conv_fwd_wino_kernel.h; 16 slots per block), in the order they are taken:
+//   0 entry | 7 every global load of chunk 0 issued | 8 chunk 0 written to LDS (its data has landed) | 1 in front of the first MFMA |
+//   2 behind the last MFMA | 3 barrier | 4 output transform + activation written to LDS | 5 barrier | 6 last store issued
+// Shapes = the four launches of the cfg2 U-Net's 256-member forward that run conv2d_fwd_wino_body, on the instances the library
+// takes for them: layers 2 and 5 (44 x 90) on the column-pair + edge-pair 8 x 32 instance, layer 3 (22 x 45) and layer 4 (up-sampled
+// 22 x 45 -> 44 x 90) on flat runs.  Random data; only the timing is meaningful.
+// Build: hipcc -O3 -std=c++17 -fno-slp-vectorize -mllvm -pragma-unroll-threshold=1000000 --offload-arch=gfx950 -DDLWP_PHASE_TIMING
+//        -o wino_phase_timing.bin wino_phase_timing.hip
+#include "../../dlwp_amd/csrc/conv_fwd_wino_flat.hip"
 #include <algorithm>
 #include <cstdio>
 #include <vector>
 
 void dlwp_set_error(const char*, ...) {}
+
+template <class C>
+__global__ __launch_bounds__(C::NT, C::WAVES_PER_SIMD) void timed_kernel(const ConvArgs a) {
+  conv2d_fwd_wino_body<C>(a, blockIdx.x, gridDim.x);
+}
 
 template <class C>
 static void run(const char* what, int N, int Cin, int Cout, int H, int W, int out_pool, int src_mode) {
@@ -32,49 +40,58 @@ static void run(const char* what, int N, int Cin, int Cout, int H, int W, int ou
   a.in_c_off = 0; a.in_c_total = Cin; a.out_c_off = 0; a.out_c_total = Cout;
   a.pad_top = 1; a.pad_left = 1; a.mode_h = DLWP_PAD_ZERO; a.mode_w = DLWP_PAD_WRAP;
   a.src_mode = src_mode; a.act = DLWP_ACT_TANH;
-  a.tiles_h = (Ho + C::TH - 1) / C::TH; a.tiles_w = (Wo + C::TW - 1) / C::TW; a.cout_tiles = Cout / C::BN;
   a.out_pool = out_pool; a.Hp = Hp; a.Wp = Wp; a.in_bf16 = 0; a.out_bf16 = 0; a.compute_bf16 = 0; a.col0 = 0;
-  const int grid = a.tiles_h * a.tiles_w * a.cout_tiles * N;
+  a.cout_tiles = Cout / C::BN;
+  int grid;
+  if constexpr (C::FLAT) {            // as conv_fwd.hip fills a flat launch
+    a.tiles_w = (Wo + 1) / 2;
+    a.tiles_h = (a.tiles_w * ((Ho + 1) / 2) + 63) / 64;
+    grid = N * a.tiles_h * a.cout_tiles;
+  } else {                            // ... and an edge-pair launch
+    a.tiles_h = (Ho + C::TH - 1) / C::TH; a.tiles_w = (Wo + C::TW - 1) / C::TW;
+    a.edge_pairs = C::EP ? 1 : 0;
+    grid = (C::EP ? a.tiles_w * (a.tiles_h - 1) + (a.tiles_w + 1) / 2 : a.tiles_h * a.tiles_w) * a.cout_tiles * N;
+  }
+  a = wino_derive(a);
   long long* dbg;
-  hipMalloc(&dbg, sizeof(long long) * 8 * grid);
-  hipMemset(dbg, 0, sizeof(long long) * 8 * grid);
+  hipMalloc(&dbg, sizeof(long long) * 16 * grid);
+  hipMemset(dbg, 0, sizeof(long long) * 16 * grid);
   if (C::LDS_BYTES > 64 * 1024)
-    hipFuncSetAttribute((const void*)conv2d_fwd_wino_f32<C>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
+    hipFuncSetAttribute((const void*)timed_kernel<C>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
   a.dbg = nullptr;
-  for (int i = 0; i < 3; ++i) hipLaunchKernelGGL((conv2d_fwd_wino_f32<C>), dim3(grid), dim3(C::NT), C::LDS_BYTES, 0, a);
+  for (int i = 0; i < 3; ++i) hipLaunchKernelGGL((timed_kernel<C>), dim3(grid), dim3(C::NT), C::LDS_BYTES, 0, a);
   hipEvent_t e0, e1;
   hipEventCreate(&e0); hipEventCreate(&e1);
   hipEventRecord(e0);
-  for (int i = 0; i < 10; ++i) hipLaunchKernelGGL((conv2d_fwd_wino_f32<C>), dim3(grid), dim3(C::NT), C::LDS_BYTES, 0, a);
+  for (int i = 0; i < 10; ++i) hipLaunchKernelGGL((timed_kernel<C>), dim3(grid), dim3(C::NT), C::LDS_BYTES, 0, a);
   hipEventRecord(e1);
   hipDeviceSynchronize();
   float ms = 0; hipEventElapsedTime(&ms, e0, e1); ms /= 10;
   a.dbg = dbg;
-  hipLaunchKernelGGL((conv2d_fwd_wino_f32<C>), dim3(grid), dim3(C::NT), C::LDS_BYTES, 0, a);
-  hipDeviceSynchronize();
-  std::vector<long long> h(8 * (size_t)grid);
+  hipLaunchKernelGGL((timed_kernel<C>), dim3(grid), dim3(C::NT), C::LDS_BYTES, 0, a);
+  if (hipDeviceSynchronize() != hipSuccess) { printf("%s: the launch failed\n", what); exit(1); }
+  std::vector<long long> h(16 * (size_t)grid);
   hipMemcpy(h.data(), dbg, sizeof(long long) * h.size(), hipMemcpyDeviceToHost);
-  double ph[6] = {0, 0, 0, 0, 0, 0};
-  long long tmin = h[0], tmax = 0;
+  static const int order[9] = {0, 7, 8, 1, 2, 3, 4, 5, 6};
+  double ph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   for (int bI = 0; bI < grid; ++bI) {
-    for (int k = 0; k < 6; ++k) ph[k] += (double)(h[bI * 8 + k + 1] - h[bI * 8 + k]);
-    tmin = std::min(tmin, h[bI * 8]); tmax = std::max(tmax, h[bI * 8 + 6]);
+    for (int k = 0; k < 8; ++k) ph[k] += (double)(h[bI * 16 + order[k + 1]] - h[bI * 16 + order[k]]);
   }
   double life = 0;
-  for (int k = 0; k < 6; ++k) { ph[k] /= grid; life += ph[k]; }
+  for (int k = 0; k < 8; ++k) { ph[k] /= grid; life += ph[k]; }
   const int chunks = (Cin + 7) / 8;
-  printf("%s: grid %d, %d chunks, %.4f ms per launch (untimed run); kernel span %lld cycles; mean block life %.0f cycles\\n", what, grid,
-         chunks, ms, (long long)(tmax - tmin), life);
-  printf("   prologue %.0f | loop %.0f (%.0f per chunk; matrix-only floor 2048 x co-resident blocks) | barrier %.0f | transform+act %.0f | "
-         "barrier %.0f | stores %.0f\\n", ph[0], ph[1], ph[1] / chunks, ph[2], ph[3], ph[4], ph[5]);
-  printf("   resident blocks on average = sum of lives / span / 256 CUs = %.2f\\n", life * grid / (double)(tmax - tmin) / 256.0);
+  printf("%s: grid %d, %d chunks, %.4f ms per launch (unstamped runs); mean block life %.0f cycles\n", what, grid, chunks, ms, life);
+  printf("   entry -> chunk-0 loads issued %.0f | -> chunk 0 in LDS %.0f | -> first MFMA %.0f | loop %.0f (%.0f per chunk) | barrier %.0f | "
+         "transform+act %.0f | barrier %.0f | stores %.0f   [in front of the first MFMA %.0f, behind the last %.0f]\n",
+         ph[0], ph[1], ph[2], ph[3], ph[3] / chunks, ph[4], ph[5], ph[6], ph[7], ph[0] + ph[1] + ph[2], ph[4] + ph[5] + ph[6] + ph[7]);
   hipFree(x); hipFree(u); hipFree(y); hipFree(b); hipFree(dbg);
 }
 
 int main() {
-  run<WinoCfg<1, 8, 32, 4, 2, 8, false, false>>("layer 2  32->64 @44x90, pooled epilogue", 256, 32, 64, 44, 90, 1, 0);
-  run<WinoCfg<1, 8, 32, 4, 2, 8, false, false>>("layer 5r 64->32 @44x90", 256, 64, 32, 44, 90, 0, 0);
-  run<WinoCfg<1, 8, 32, 4, 2, 8, false, false>>("layer 3  64->128 @22x45 (all columns on the 8x32 instance)", 256, 64, 128, 22, 45, 0, 0);
-  run<WinoCfg<1, 8, 32, 4, 4, 8, false, true>>("layer 4  128->64 @44x90 up-sampled source, 9 positions, 64 channels / block", 256, 128, 64, 44, 90, 0, 1);
+  typedef WinoCfg<1, 8, 32, 4, 2, 8, false, false, false, false, false, true, false, true> PairEdge;
+  run<PairEdge>("layer 2  32->64 @44x90, pooled epilogue (column pairs + edge pairs)", 256, 32, 64, 44, 90, 1, 0);
+  run<WinoFlatCfg<false, 2>>("layer 3  64->128 @22x45 (flat runs)", 256, 64, 128, 22, 45, 0, 0);
+  run<WinoFlatCfg<true, 4>>("layer 4  128->64 @44x90 up-sampled source (flat runs, 64 channels / block)", 256, 128, 64, 44, 90, 0, 1);
+  run<PairEdge>("layer 5  64->32 @44x90 (column pairs + edge pairs)", 256, 64, 32, 44, 90, 0, 0);
   return 0;
 }
