@@ -35,6 +35,9 @@ and the centred one.  On the device one pass of dlwp_verify_skill_sums (csrc/ski
 which finish_skill turns into the scores; the host path computes the same definition in numpy (float32 d = fc - ob, fa = fc - c,
 oa = ob - c, float64 sums) and is no fallback of the device path: both refuse an `axis` they do not cover.  An ensemble is scored
 through its mean: forecast_skill(ensemble.ensemble_mean_spread(series)[0], valid, ...).  DESIGN.md 5.38 has the kernel and the bounds.
+forecast_skill_map / persistence_skill_map give the same scores at every grid point, reduced over the samples of a lead
+(dlwp_verify_skill_map, csrc/skill_map.hip, finishes them on the device: CUDA arguments give CUDA maps); skill_map_sums returns the
+nine float64 planes, which add over ranks or sample chunks, and finish_skill_map finishes them.  DESIGN.md 5.40.
 
 A caveat of return_device=True: the tensor may alias the cached series buffer of the model's captured rollout, which the next
 rollout of that model overwrites -- verify it (or clone it) before rolling the model out again.
@@ -723,3 +726,127 @@ def persistence_skill(predictors, valid, n_fhour, climatology=None, labels=None,
     inner = tuple(int(s) for s in valid.shape[1:])
     return _skill('persistence_skill', plan, 'predictors', predictors, valid, inner, tuple(valid.shape[:1]), climatology, labels,
                   weights, axis, device, lambda x, f, cnt: x[:cnt], lambda v, f, cnt: v[f:f + cnt])
+
+
+# -- skill per grid point: the same sums reduced over the samples of a lead (csrc/skill_map.hip) ---------------------- #
+def _skill_map_host(fc_rows, ob_rows, plan, inner, table, labels):
+    """the definition in numpy: per lead the float32 d, fa, oa of the rows the plan pairs, float64 sums over the samples at every
+    point -> (leads, 9) + inner"""
+    out = np.zeros((plan.leads, 9) + tuple(inner), np.float64)
+    for f in range(plan.leads):
+        cnt = max(plan.count0 - f * plan.count_dec, 0)
+        if cnt == 0:
+            continue
+        fc, ob = fc_rows(f, cnt), ob_rows(f, cnt)
+        skip = np.zeros(cnt, bool)
+        with np.errstate(invalid='ignore'):
+            d = fc - ob
+            if table is None:
+                fa, oa = fc, ob
+            else:
+                if labels is None:
+                    c = table[0]
+                else:
+                    at = f * plan.label_strides[0] + f * plan.label_strides[1]
+                    lab = labels[at:at + cnt]
+                    skip = lab < 0
+                    c = table[np.maximum(lab, 0)]
+                fa, oa = fc - c, ob - c
+        assert d.dtype == fa.dtype == oa.dtype == np.float32
+        ok = ~(np.isnan(d) | np.isnan(fa) | np.isnan(oa)) & ~skip.reshape((cnt,) + (1,) * len(inner))
+        d, fa, oa = (np.where(ok, v, np.float32(0)).astype(np.float64) for v in (d, fa, oa))
+        with np.errstate(over='ignore', invalid='ignore'):
+            terms = (d, d * d, np.abs(d), fa, oa, fa * oa, fa * fa, oa * oa, ok)
+            out[f] = np.stack([np.sum(t, axis=0, dtype=np.float64) for t in terms])
+    return out
+
+
+def finish_skill_map(sums):
+    """A (leads, 9, ...) float64 table of skill_map_sums -> Skill with fields of shape (leads, ...): finish_skill's formulas with
+    S0 = the count, computed in float64 and cast once.  Tables of several ranks or sample chunks add before the finish.  A numpy table
+    is finished in numpy, a CUDA tensor on the device (dlwp_verify_skill_map_finish) and stays there."""
+    if isinstance(sums, torch.Tensor):
+        from .. import ops
+        if sums.dim() < 3 or sums.shape[1] != 9:
+            raise ValueError('finish_skill_map: expected a (leads, 9, ...) table, got %r' % (tuple(sums.shape),))
+        shape = (sums.shape[0],) + tuple(sums.shape[2:])
+        with torch.cuda.device(sums.device):
+            scores, counts = ops.verify_skill_map_finish(sums.contiguous())
+        return Skill(*([scores[:, k].reshape(shape) for k in range(6)] + [counts.reshape(shape).to(torch.int64)]))
+    s = np.asarray(sums, dtype=np.float64)
+    if s.ndim < 3 or s.shape[1] != 9:
+        raise ValueError('finish_skill_map: expected a (leads, 9, ...) table, got %r' % (s.shape,))
+    s = np.moveaxis(s, 1, -1)
+    return finish_skill(np.concatenate([s[..., 8:], s], axis=-1))
+
+
+def _skill_map(who, plan, fc_name, forecast, valid, inner, label_shape, climatology, labels, device, split, fc_rows, ob_rows, want):
+    """want: 'sums' -> the (leads, 9) + inner table; 'scores' -> the Skill.  CUDA arguments give CUDA results, numpy ones numpy."""
+    split = int(split)
+    if split < 0:
+        raise ValueError("%s: 'split' must be >= 0, got %d" % (who, split))
+    named = [(fc_name, forecast), ('valid', valid)] + ([] if climatology is None else [('climatology', climatology)])
+    on_device = _wants_device(named, device)
+    table, labels, _ = _skill_extras(who, plan, inner, label_shape, climatology, labels, None)
+    if not on_device:
+        f32 = lambda x: None if x is None else np.asarray(x).astype(np.float32, copy=False)      # noqa: E731
+        forecast, valid, table = f32(forecast), f32(valid), f32(table)
+        sums = _skill_map_host(lambda f, cnt: fc_rows(forecast, f, cnt), lambda f, cnt: ob_rows(valid, f, cnt), plan, inner, table,
+                               labels)
+        return sums if want == 'sums' else finish_skill_map(sums)
+    from .. import ops
+    stay = any(isinstance(v, torch.Tensor) for _, v in named)
+    dev = _common_device([v.device for _, v in named if isinstance(v, torch.Tensor)], device)
+    if dev is None or dev.index is None:
+        dev = torch.device('cuda', torch.cuda.current_device())
+    shape = (plan.leads,) + tuple(inner)
+    with torch.cuda.device(dev):
+        t = {k: _to_device(v, dev) for k, v in named[:2]}
+        sums, scores, counts = ops.verify_skill_map(t[plan.fc], plan.fc_strides, t[plan.ob], plan.ob_strides, plan.leads, plan.count0,
+                                                    plan.count_dec, plan.run, climo=None if table is None else _to_device(table, dev),
+                                                    labels=labels, label_strides=plan.label_strides, split=split,
+                                                    want_sums=want == 'sums', want_scores=want == 'scores')
+        if want == 'sums':
+            sums = sums.reshape((plan.leads, 9) + tuple(inner))
+            return sums if stay else sums.cpu().numpy()
+        if stay:
+            return Skill(*([scores[:, k].reshape(shape) for k in range(6)] + [counts.reshape(shape).to(torch.int64)]))
+        scores, counts = scores.cpu().numpy(), counts.cpu().numpy()      # 28 bytes per point
+        return Skill(*([scores[:, k].reshape(shape) for k in range(6)] + [counts.reshape(shape).astype(np.int64)]))
+
+
+def _forecast_skill_map(who, forecast, valid, climatology, labels, device, split, want):
+    plan = plan_forecast_skill(forecast.shape, valid.shape, None)
+    per_lead = len(forecast.shape) == len(valid.shape)
+    inner = tuple(int(s) for s in valid.shape[2 if per_lead else 1:])
+    label_shape = tuple(valid.shape[:2]) if per_lead else tuple(valid.shape[:1])
+    ob_rows = (lambda v, f, cnt: v[f, :cnt]) if per_lead else (lambda v, f, cnt: v[f:f + cnt])
+    return _skill_map(who, plan, 'forecast', forecast, valid, inner, label_shape, climatology, labels, device, split,
+                      lambda x, f, cnt: x[f, :cnt], ob_rows, want)
+
+
+def forecast_skill_map(forecast, valid, climatology=None, labels=None, device=None):
+    """forecast_skill at every grid point: per lead the scores over the SAMPLES at each point of a sample row, as a Skill tuple whose
+    fields have the shape (leads,) + the shape of a sample row (count: int64).  Shapes, the two forms of `valid`, `climatology`,
+    `labels` and the refusals are forecast_skill's; there are no weights (a weight is constant per point and cancels) and no `axis`.
+    d = forecast - valid, fa = forecast - c, oa = valid - c in float32; a pair with a NaN among them, or with label -1, is skipped at
+    that point; sums in float64.  NaN where nothing was counted or a variance is not positive (a single sample).  CUDA float32
+    tensors are reduced on the device (csrc/skill_map.hip) and give CUDA tensors; numpy arrays give numpy arrays, computed in numpy,
+    or on the device with device='cuda'."""
+    return _forecast_skill_map('forecast_skill_map', forecast, valid, climatology, labels, device, 0, 'scores')
+
+
+def persistence_skill_map(predictors, valid, n_fhour, climatology=None, labels=None, device=None):
+    """forecast_skill_map of forecasting "no change": lead f compares predictors[i] with valid[i + f]; `labels` (Nv,) follow `valid`"""
+    plan = plan_persistence_skill(predictors.shape, valid.shape, n_fhour, None)
+    inner = tuple(int(s) for s in valid.shape[1:])
+    return _skill_map('persistence_skill_map', plan, 'predictors', predictors, valid, inner, tuple(valid.shape[:1]), climatology, labels,
+                      device, 0, lambda x, f, cnt: x[:cnt], lambda v, f, cnt: v[f:f + cnt], 'scores')
+
+
+def skill_map_sums(forecast, valid, climatology=None, labels=None, device=None, split=0):
+    """The (leads, 9) + row-shape float64 table behind forecast_skill_map: sum d, d^2, |d|, fa, oa, fa oa, fa^2, oa^2 and the pairs
+    counted, per point.  Tables of several ranks or sample chunks add; finish_skill_map makes the scores.  split (device path): 0 =
+    the library's rule, a positive number = that many chunks of the sample axis, each added in sample order and the chunks in chunk
+    order -- callers that compare or add tables fix it."""
+    return _forecast_skill_map('skill_map_sums', forecast, valid, climatology, labels, device, split, 'sums')

@@ -1868,6 +1868,78 @@ def verify_skill_sums(fc, fc_strides, ob, ob_strides, leads, count0, count_dec, 
     return sums
 
 
+SKILL_MAP_SUMS, SKILL_MAP_SCORES = 9, 6
+
+
+def verify_skill_map(fc, fc_strides, ob, ob_strides, leads, count0, count_dec, row, climo=None, labels=None, label_strides=(0, 0),
+                     split=0, want_sums=True, want_scores=True):
+    """include/dlwp_hip.h: dlwp_verify_skill_map.  Operands, table and labels as in verify_skill_sums with groups = 1 and run = row:
+    checked here (every addressed element exists, labels in [-1, n_labels)) before anything is uploaded or launched.  split: 0 = the
+    library's rule, a positive number = that many chunks of the sample axis (capped at count0).  Returns (sums, scores, counts):
+    NEW device tensors (leads, 9, row) float64, (leads, 6, row) float32 and (leads, row) int32, enqueued on the current stream; sums
+    is None without want_sums, scores and counts are None without want_scores."""
+    _check_f32(fc, ob, climo)
+    d = _dev(fc)
+    if _dev(ob) != d or (climo is not None and _dev(climo) != d):
+        raise ValueError('verify_skill_map: operands on different devices')
+    leads, count0, count_dec, row, split = int(leads), int(count0), int(count_dec), int(row), int(split)
+    if leads < 1 or row < 1 or count_dec < 0 or min(fc_strides) < 0 or min(ob_strides) < 0 or min(label_strides) < 0:
+        raise ValueError('verify_skill_map: leads and row must be >= 1; strides, shifts and count_dec >= 0')
+    if split < 0:
+        raise ValueError('verify_skill_map: split must be >= 0, got %d' % split)
+    if not (want_sums or want_scores):
+        raise ValueError('verify_skill_map: neither sums nor scores wanted')
+    for name, t, st in (('fc', fc, fc_strides), ('ob', ob, ob_strides)):
+        need = verify_extent(st, leads, count0, count_dec, 1, row)
+        if need > t.numel():
+            raise ValueError('verify_skill_map: operand %s holds %d elements, the strides address %d' % (name, t.numel(), need))
+    n_labels = 0
+    if climo is not None:
+        n_labels, trow = _rows_of(climo, 'verify_skill_map')
+        if trow != row:
+            raise ValueError('verify_skill_map: table rows of %d floats, sample rows of %d' % (trow, row))
+        if n_labels > VERIFY_MAX_LABELS:
+            raise ValueError('verify_skill_map: %d labels, at most %d' % (n_labels, VERIFY_MAX_LABELS))
+    elif labels is not None:
+        raise ValueError('verify_skill_map: labels without a climatology table')
+    if labels is not None:
+        labels = skill_labels(labels, n_labels)
+        need = verify_label_extent(label_strides, leads, count0, count_dec)
+        if need > labels.size:
+            raise ValueError('verify_skill_map: %d labels, the strides address %d' % (labels.size, need))
+    h = _lib.handle(d)
+    labels_d = None if labels is None else torch.from_numpy(labels).to(fc.device)
+    ws = torch.empty(max(int(_lib.lib.dlwp_verify_skill_map_workspace(h, leads, count0, row, split)), 8), dtype=torch.uint8,
+                     device=fc.device)
+    sums = torch.empty((leads, SKILL_MAP_SUMS, row), dtype=torch.float64, device=fc.device) if want_sums else None
+    scores = torch.empty((leads, SKILL_MAP_SCORES, row), dtype=torch.float32, device=fc.device) if want_scores else None
+    counts = torch.empty((leads, row), dtype=torch.int32, device=fc.device) if want_scores else None
+    _lib.check(_lib.lib.dlwp_verify_skill_map(h, _ptr(fc), int(fc_strides[0]), int(fc_strides[1]), int(fc_strides[2]),
+                                              _ptr(ob), int(ob_strides[0]), int(ob_strides[1]), int(ob_strides[2]),
+                                              leads, count0, count_dec, row, _ptr(climo), n_labels, _ptr(labels_d),
+                                              int(label_strides[0]), int(label_strides[1]), split, _ptr(sums), _ptr(scores),
+                                              _ptr(counts), _ptr(ws), ws.numel(), _stream(fc)))
+    return sums, scores, counts
+
+
+def verify_skill_map_finish(sums):
+    """include/dlwp_hip.h: dlwp_verify_skill_map_finish on a (leads, 9, ...) float64 device table (one that was added over ranks or
+    sample chunks): one launch per lead on the current stream.  Returns NEW (leads, 6, row) float32 scores and (leads, row) int32
+    counts with row = the points of a plane."""
+    if not isinstance(sums, torch.Tensor) or sums.dtype != torch.float64 or not sums.is_contiguous():
+        raise TypeError('verify_skill_map_finish: expected a contiguous float64 tensor')
+    if sums.dim() < 3 or sums.shape[1] != SKILL_MAP_SUMS or sums.shape[0] < 1 or sums[0, 0].numel() < 1:
+        raise ValueError('verify_skill_map_finish: expected (leads >= 1, 9, ...) with non-empty planes, got %r' % (tuple(sums.shape),))
+    leads, row = int(sums.shape[0]), int(sums[0, 0].numel())
+    h = _lib.handle(_dev(sums))
+    scores = torch.empty((leads, SKILL_MAP_SCORES, row), dtype=torch.float32, device=sums.device)
+    counts = torch.empty((leads, row), dtype=torch.int32, device=sums.device)
+    stream = _stream(sums)
+    for f in range(leads):
+        _lib.check(_lib.lib.dlwp_verify_skill_map_finish(h, _ptr(sums[f]), row, _ptr(scores[f]), _ptr(counts[f]), stream))
+    return scores, counts
+
+
 def verify_nanmean_samples(x):
     """include/dlwp_hip.h: dlwp_verify_nanmean_samples.  x: (count, ...) contiguous float32 device tensor -> a NEW float32 tensor
     of x.shape[1:], the NaN-skipping mean over the first axis (float64 sums in sample order; NaN where no sample is finite-or-inf)."""

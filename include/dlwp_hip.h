@@ -1182,6 +1182,44 @@ int dlwp_verify_skill_sums(dlwp_handle_t, const void* fc, long long fc_lead_stri
                            long long label_lead_stride, int label_shift, const void* weights, int w_len, long long w_inner,
                            void* sums, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- forecast skill per grid point (csrc/skill_map.hip): the sums of dlwp_verify_skill_sums reduced over the SAMPLES of a lead at
+ *      every point of the sample row, and the scores made from them on the device.  fc, ob, climo and labels are addressed exactly as
+ *      in dlwp_verify_skill_sums with groups = 1 and run = row; there are no weights (a weight is constant per point and cancels).
+ *      Per pair d = fc - ob, fa = fc - c, oa = ob - c are each rounded once in float32; a pair with a NaN among them, or with a label
+ *      outside [0, n_labels), is skipped for that point only and is never used as an address; everything behind that is float64.
+ *        sums   (leads, 9, row) float64 planes   0: sum d    1: sum d^2   2: sum |d|   3: sum fa   4: sum oa   5: sum fa oa
+ *                                                6: sum fa^2 7: sum oa^2  8: pairs counted
+ *        scores (leads, 6, row) float32 planes   mse, rmse, mae, bias, acc, acc_centered: the formulas of dlwp_amd.model.verify.
+ *                                                finish_skill with S0 = the count, each operation rounded once in float64 (nothing
+ *                                                is contracted into a fused multiply-add), cast once; NaN where nothing was counted
+ *                                                or a denominator is not positive
+ *        counts (leads, row) int32
+ *      Each of the three may be NULL, not all of them.  A lead without pairs stores zero sums, NaN scores and zero counts.
+ *      A thread owns one unit of one lead -- four adjacent points with 16-byte loads when row and the four operand strides are
+ *      multiples of 4 and fc, ob, climo are 16-byte aligned, else one point (the two routes give the same bits) -- and adds that lead's
+ *      samples in sample order, several in flight; the label is the same in every lane.  The sample axis is cut into `split` chunks
+ *      [cnt_f k / split, cnt_f (k + 1) / split): split = 0 asks for min(max(1, 8 CUs / (leads * tiles)), count0) with tiles =
+ *      ceil(units / 256), i.e. the samples are split only when leads x column tiles do not fill the chip; a positive split is taken as
+ *      given; either is capped at count0 and is at least 1.  With one chunk the launch finishes by itself; with more, the chunks'
+ *      planes go to ws and a second launch adds them in chunk order and finishes.  No atomics, no host synchronisation, identical
+ *      bits on repeated calls (a different split is a different order of additions).  dlwp_verify_skill_map_workspace returns
+ *      leads * split * 9 * row * 8 bytes for the split the call will use (0 for one chunk; for split = 0 that of the 16-byte route,
+ *      the larger one; a NULL handle counts 256 CUs); ws must be 8-byte aligned.  Refused without a launch, in this order: leads or
+ *      row < 1; negative strides, shifts or count_dec; n_labels outside 1 .. 64 with a table; labels without a table; null fc or
+ *      ob, or all three outputs NULL; split < 0; a row too long for one grid (leads * split * tiles >= 2^31); a workspace too small or
+ *      misaligned; a null handle.  The caller guarantees that every addressed element exists (dlwp_amd.ops.verify_skill_map checks).
+ *      dlwp_verify_skill_map_finish does the last step alone, for tables that were added over ranks or sample chunks: sums is ONE
+ *      table of 9 planes of `cells` float64 (one lead of the layout above, cells = row), scores 6 planes of `cells` float32, counts
+ *      `cells` int32, either of the two may be NULL.  Refused in this order: cells < 1; null sums or no output; too many cells for one
+ *      grid; a null handle.  Both mark a recording tape foreign.                                                                    */
+size_t dlwp_verify_skill_map_workspace(dlwp_handle_t, int leads, int count0, long long row, int split);
+int dlwp_verify_skill_map(dlwp_handle_t, const void* fc, long long fc_lead_stride, long long fc_sample_stride, int fc_shift,
+                          const void* ob, long long ob_lead_stride, long long ob_sample_stride, int ob_shift, int leads, int count0,
+                          int count_dec, long long row, const void* climo, int n_labels, const void* labels,
+                          long long label_lead_stride, int label_shift, int split, void* sums, void* scores, void* counts, void* ws,
+                          size_t ws_bytes, void* stream);
+int dlwp_verify_skill_map_finish(dlwp_handle_t, const void* sums, long long cells, void* scores, void* counts, void* stream);
+
 /* ---- batches of a series generator cut out of an HBM-resident series (csrc/series.hip; DLWP/model/generators.py:323-629,
  *      SeriesDataGenerator.generate).  One launch fills X and every target block of a batch:
  *        dst[g.dst][i * row_d + g.dst_at + e] = src[g.src][(samples[i] + g.shift) * row_s + g.src_at + e],  e < g.len, i < n
