@@ -384,6 +384,9 @@ _sig('dlwp_verify_skill_map_workspace', [_vp, _i, _i, ctypes.c_longlong, _i], _s
 _sig('dlwp_verify_skill_map', [_vp, _vp, ctypes.c_longlong, ctypes.c_longlong, _i, _vp, ctypes.c_longlong, ctypes.c_longlong, _i,
                                _i, _i, _i, ctypes.c_longlong, _vp, _i, _vp, ctypes.c_longlong, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp])
 _sig('dlwp_verify_skill_map_finish', [_vp, _vp, ctypes.c_longlong, _vp, _vp, _vp])
+_sig('dlwp_verify_spectrum_workspace', [_vp, _i, _i, _i], _sz)
+_sig('dlwp_verify_spectrum_sums', [_vp, _vp, ctypes.c_longlong, ctypes.c_longlong, _i, _vp, ctypes.c_longlong, ctypes.c_longlong, _i,
+                                   _i, _i, _i, _i, ctypes.c_longlong, _i, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp])
 _sig('dlwp_ens_mean_spread', [_vp, _vp, _i, _i, _i, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, _i,
                               _vp, _vp, _vp])
 _sig('dlwp_ens_score_workspace', [_vp, _i, _i, _i], _sz)

@@ -38,6 +38,11 @@ through its mean: forecast_skill(ensemble.ensemble_mean_spread(series)[0], valid
 forecast_skill_map / persistence_skill_map give the same scores at every grid point, reduced over the samples of a lead
 (dlwp_verify_skill_map, csrc/skill_map.hip, finishes them on the device: CUDA arguments give CUDA maps); skill_map_sums returns the
 nine float64 planes, which add over ranks or sample chunks, and finish_skill_map finishes them.  DESIGN.md 5.40.
+forecast_spectrum / persistence_spectrum look at the same pairs by scale, which no point-wise score does: per lead (and variable) the
+zonal power spectrum of the forecast beside that of the truth, the power of the error and the coherence at every wavenumber, as a
+Spectrum tuple.  On the device dlwp_verify_spectrum_sums (csrc/spectrum.hip) transforms the longitude rows of valid and of d =
+forecast - valid on the fp32 matrix cores and leaves four float64 sums per wavenumber; spectrum_sums returns them (they add over ranks
+or sample chunks), finish_spectrum finishes them; the host path states the definition with np.fft.rfft in float64.  DESIGN.md 5.41.
 
 A caveat of return_device=True: the tensor may alias the cached series buffer of the model's captured rollout, which the next
 rollout of that model overwrites -- verify it (or clone it) before rolling the model out again.
@@ -815,14 +820,21 @@ def _skill_map(who, plan, fc_name, forecast, valid, inner, label_shape, climatol
         return Skill(*([scores[:, k].reshape(shape) for k in range(6)] + [counts.reshape(shape).astype(np.int64)]))
 
 
-def _forecast_skill_map(who, forecast, valid, climatology, labels, device, split, want):
-    plan = plan_forecast_skill(forecast.shape, valid.shape, None)
+def _forecast_rows(forecast, valid):
+    """how a forecast (step first) meets either form of `valid`: (inner shape of a sample row, shape of the labels, rows of the
+    forecast, rows of `valid`), the last two as functions of (array, lead, count)"""
     per_lead = len(forecast.shape) == len(valid.shape)
     inner = tuple(int(s) for s in valid.shape[2 if per_lead else 1:])
     label_shape = tuple(valid.shape[:2]) if per_lead else tuple(valid.shape[:1])
     ob_rows = (lambda v, f, cnt: v[f, :cnt]) if per_lead else (lambda v, f, cnt: v[f:f + cnt])
-    return _skill_map(who, plan, 'forecast', forecast, valid, inner, label_shape, climatology, labels, device, split,
-                      lambda x, f, cnt: x[f, :cnt], ob_rows, want)
+    return inner, label_shape, (lambda x, f, cnt: x[f, :cnt]), ob_rows
+
+
+def _forecast_skill_map(who, forecast, valid, climatology, labels, device, split, want):
+    plan = plan_forecast_skill(forecast.shape, valid.shape, None)
+    inner, label_shape, fc_rows, ob_rows = _forecast_rows(forecast, valid)
+    return _skill_map(who, plan, 'forecast', forecast, valid, inner, label_shape, climatology, labels, device, split, fc_rows, ob_rows,
+                      want)
 
 
 def forecast_skill_map(forecast, valid, climatology=None, labels=None, device=None):
@@ -850,3 +862,142 @@ def skill_map_sums(forecast, valid, climatology=None, labels=None, device=None, 
     the library's rule, a positive number = that many chunks of the sample axis, each added in sample order and the chunks in chunk
     order -- callers that compare or add tables fix it."""
     return _forecast_skill_map('skill_map_sums', forecast, valid, climatology, labels, device, split, 'sums')
+
+
+# -- zonal power spectra per lead: power by wavenumber, error power, coherence (csrc/spectrum.hip; DESIGN.md 5.41) ------------------- #
+#: per lead (and group): wavenumber (K,) int64; float32 (leads[, groups], K) power of the forecast, of the truth and of the error (their
+#: sums over k are the weighted means of fc^2, ob^2, d^2), ratio = power_forecast / power_valid and the coherence |<F conj O>|^2 /
+#: (<|F|^2> <|O|^2>); int64 count of the longitude rows behind them.  NaN where nothing was counted or a denominator is not positive
+Spectrum = collections.namedtuple('Spectrum', 'wavenumber power_forecast power_valid power_error ratio coherence count')
+
+
+def finish_spectrum(sums, norm, grouped=True):
+    """(..., 4, K) float64 sums and (..., 2) norm of spectrum_sums / dlwp_verify_spectrum_sums (include/dlwp_hip.h) -> Spectrum,
+    computed in float64 and cast once.  Tables of several ranks or sample chunks add before the finish.  grouped=False drops a groups
+    axis of one: (leads, 1, 4, K) -> fields of (leads, K)."""
+    s, nrm = np.asarray(sums, dtype=np.float64), np.asarray(norm, dtype=np.float64)
+    if s.ndim < 2 or s.shape[-2] != 4 or nrm.shape != s.shape[:-2] + (2,):
+        raise ValueError('finish_spectrum: expected sums (..., 4, K) and norm (..., 2), got %r and %r' % (s.shape, nrm.shape))
+    sw, n = nrm[..., 0], nrm[..., 1]
+    with np.errstate(all='ignore'):
+        some = (n > 0) & (sw > 0)
+        den = np.where(some, sw, np.nan)[..., None]
+        s0, s1, s2, s3 = (s[..., q, :] / den for q in range(4))
+        p_f = s0 + s1 + 2.0 * s2
+        ratio = np.where(s0 > 0, p_f / s0, np.nan)
+        dd = p_f * s0
+        coh = np.where(dd > 0, ((s0 + s2) ** 2 + s3 ** 2) / dd, np.nan)
+        fields = [v.astype(np.float32) for v in (p_f, s0, s1, ratio, coh)]
+    out = Spectrum(*([np.arange(s.shape[-1], dtype=np.int64)] + fields + [n.astype(np.int64)]))
+    if grouped:
+        return out
+    return Spectrum(*([out.wavenumber] + [v[..., 0, :] for v in out[1:6]] + [out.count[..., 0]]))
+
+
+def _spectrum_host(fc_rows, ob_rows, plan, inner, weights):
+    """the definition in numpy: per lead the float32 d = fc - ob of the rows the plan pairs, np.fft.rfft of ob and d in float64 along the
+    last axis, longitude rows with a non-finite fc, ob or d skipped -> (leads, groups, 4, K) sums, (leads, groups, 2) norm"""
+    width = int(inner[-1])
+    k = width // 2 + 1
+    c = np.full(k, 2.0)
+    c[0] = 1.0
+    if width % 2 == 0:
+        c[-1] = 1.0
+    c /= float(width) * float(width)
+    sums = np.zeros((plan.leads, plan.groups, 4, k), np.float64)
+    norm = np.zeros((plan.leads, plan.groups, 2), np.float64)
+    lat = plan.run // width if weights is None else weights.size
+    w_lat = np.ones(lat, np.float64) if weights is None else weights.astype(np.float64)
+    for f in range(plan.leads):
+        cnt = max(plan.count0 - f * plan.count_dec, 0)
+        if cnt == 0:
+            continue
+        shape = (cnt, plan.groups, plan.run // (lat * width), lat, width)
+        fc, ob = fc_rows(f, cnt).reshape(shape), ob_rows(f, cnt).reshape(shape)
+        with np.errstate(invalid='ignore', over='ignore'):
+            d = fc - ob
+        assert d.dtype == np.float32
+        ok = np.isfinite(fc).all(axis=-1) & np.isfinite(ob).all(axis=-1) & np.isfinite(d).all(axis=-1)
+        o_k = np.fft.rfft(np.where(ok[..., None], ob, np.float32(0)).astype(np.float64), axis=-1)
+        d_k = np.fft.rfft(np.where(ok[..., None], d, np.float32(0)).astype(np.float64), axis=-1)
+        w = ok * w_lat
+        cross = d_k * np.conj(o_k)
+        terms = (o_k.real ** 2 + o_k.imag ** 2, d_k.real ** 2 + d_k.imag ** 2, cross.real, cross.imag)
+        for q, term in enumerate(terms):
+            sums[f, :, q] = np.einsum('sgrh,sgrhk->gk', w, term) * c
+        norm[f, :, 0] = w.sum(axis=(0, 2, 3))
+        norm[f, :, 1] = ok.sum(axis=(0, 2, 3))
+    return sums, norm
+
+
+def _spectrum_device(plan, named, width, weights, device):
+    from .. import ops
+    dev = _common_device([v.device for _, v in named if isinstance(v, torch.Tensor)], device)
+    if dev is None or dev.index is None:
+        dev = torch.device('cuda', torch.cuda.current_device())
+    with torch.cuda.device(dev):
+        t = {k: _to_device(v, dev) for k, v in named}
+        sums, norm = ops.verify_spectrum_sums(t[plan.fc], plan.fc_strides, t[plan.ob], plan.ob_strides, plan.leads, plan.count0,
+                                              plan.count_dec, plan.groups, plan.run, width, weights=weights)
+        return sums.cpu().numpy(), norm.cpu().numpy()
+
+
+def _spectrum_sums(who, plan, fc_name, forecast, valid, inner, weights, device, fc_rows, ob_rows):
+    """(sums, norm) as float64 numpy; every refusal happens here, before anything is uploaded"""
+    from .. import ops
+    named = [(fc_name, forecast), ('valid', valid)]
+    on_device = _wants_device(named, device)
+    if len(inner) < 2:
+        raise ValueError('%s: a sample row needs a latitude and a longitude axis, got rows of shape %r' % (who, tuple(inner)))
+    width = int(inner[-1])
+    if width < ops.SPECTRUM_MIN_WIDTH:
+        raise ValueError('%s: rows of %d longitudes, at least %d expected' % (who, width, ops.SPECTRUM_MIN_WIDTH))
+    if on_device and width > ops.SPECTRUM_MAX_WIDTH:
+        raise ValueError('%s: rows of %d longitudes, the device path takes at most %d (the host path has no limit; a resident series '
+                         'is not downloaded silently)' % (who, width, ops.SPECTRUM_MAX_WIDTH))
+    _, _, weights = _skill_extras(who, plan, inner, (), None, None, weights)
+    if on_device:
+        return _spectrum_device(plan, named, width, weights, device)
+    f32 = lambda x: np.asarray(x).astype(np.float32, copy=False)      # noqa: E731
+    forecast, valid = f32(forecast), f32(valid)
+    return _spectrum_host(lambda f, cnt: fc_rows(forecast, f, cnt), lambda f, cnt: ob_rows(valid, f, cnt), plan, inner, weights)
+
+
+def spectrum_sums(forecast, valid, weights=None, axis=None, device=None, n_fhour=None):
+    """The float64 tables behind forecast_spectrum (n_fhour=None) or persistence_spectrum (n_fhour given; `forecast` holds the
+    predictors): sums (leads, groups, 4, K) = sum w c_k |O_k|^2, sum w c_k |D_k|^2, sum w c_k Re(D_k conj O_k), sum w c_k Im(D_k conj
+    O_k) with O = rfft(valid), D = rfft(forecast - valid) along the last axis, K = W // 2 + 1, c_k the one-sided Parseval factors over
+    W^2; norm (leads, groups, 2) = sum w and the longitude rows counted.  groups is 1 for axis=None.  Numpy arrays either way; tables
+    of several ranks or sample chunks add, finish_spectrum makes the Spectrum."""
+    forecast, valid = (x if isinstance(x, torch.Tensor) else np.asarray(x) for x in (forecast, valid))      # lists and the like
+    if n_fhour is None:
+        plan = plan_forecast_skill(forecast.shape, valid.shape, axis)
+        inner, _, fc_rows, ob_rows = _forecast_rows(forecast, valid)
+        return _spectrum_sums('forecast_spectrum', plan, 'forecast', forecast, valid, inner, weights, device, fc_rows, ob_rows)
+    plan = plan_persistence_skill(forecast.shape, valid.shape, n_fhour, axis)
+    inner = tuple(int(s) for s in valid.shape[1:])
+    return _spectrum_sums('persistence_spectrum', plan, 'predictors', forecast, valid, inner, weights, device,
+                          lambda x, f, cnt: x[:cnt], lambda v, f, cnt: v[f:f + cnt])
+
+
+def forecast_spectrum(forecast, valid, weights=None, axis=None, device=None):
+    """Zonal power spectra of a time-series forecast (forecast step first) per lead -- and per variable with the `axis` tuple that keeps
+    the lead and the first inner axis -- as a Spectrum tuple.  A sample row is (..., H, W): the last axis is longitude (periodic), the
+    second-to-last latitude.  `valid` carries the same leading step axis, or is the plain verification series: lead f of sample i then
+    meets valid[i + f].  Per longitude row d = forecast - valid is rounded once in float32 and valid and d are transformed along
+    longitude (the forecast's transform is their sum): power_valid, power_error and power_forecast sum over the wavenumbers to the
+    weighted means of valid^2, d^2 and forecast^2; ratio = power_forecast / power_valid falls below 1 where a forecast is smoothed;
+    coherence says up to which wavenumber the forecast still carries the phase of the truth.  weights: one weight per latitude row
+    (area_weights(lats)), finite, >= 0, not all zero.  A longitude row with a non-finite value in forecast, valid or d is skipped
+    whole; `count` says how many rows were counted.  Needs W >= 4.  CUDA float32 tensors, or numpy arrays with device='cuda', are
+    transformed on the device (csrc/spectrum.hip, W <= 512; a wider row is a ValueError, never a silent download); the result is a
+    tuple of numpy arrays either way."""
+    return finish_spectrum(*spectrum_sums(forecast, valid, weights, axis, device), grouped=axis is not None)
+
+
+def persistence_spectrum(predictors, valid, n_fhour, weights=None, axis=None, device=None):
+    """forecast_spectrum of forecasting "no change": lead f compares predictors[i] with valid[i + f]"""
+    n_fhour = int(n_fhour)
+    if n_fhour < 1:
+        raise ValueError("persistence_spectrum: 'n_fhour' must be >= 1")
+    return finish_spectrum(*spectrum_sums(predictors, valid, weights, axis, device, n_fhour=n_fhour), grouped=axis is not None)

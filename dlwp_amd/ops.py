@@ -1940,6 +1940,75 @@ def verify_skill_map_finish(sums):
     return scores, counts
 
 
+SPECTRUM_MIN_WIDTH, SPECTRUM_MAX_WIDTH = 4, 512
+
+
+def spectrum_twiddles(width):
+    """HOST table of dlwp_verify_spectrum_sums: cos(2 pi m / width) for m < width, then sin(2 pi m / width), computed in float64 and
+    rounded once to float32"""
+    a = 2.0 * np.pi * np.arange(int(width), dtype=np.float64) / float(width)
+    return np.concatenate([np.cos(a), np.sin(a)]).astype(np.float32)
+
+
+_SPECTRUM_TWIDDLES = {}
+
+
+def _spectrum_twiddles_on(device, width):
+    """the table of spectrum_twiddles(width) on `device`, made and uploaded once per (device, width) and never written afterwards"""
+    key = (device.index, int(width))
+    tw = _SPECTRUM_TWIDDLES.get(key)
+    if tw is None:
+        tw = _SPECTRUM_TWIDDLES[key] = torch.from_numpy(spectrum_twiddles(width)).to(device)
+    return tw
+
+
+def verify_spectrum_sums(fc, fc_strides, ob, ob_strides, leads, count0, count_dec, groups, run, width, weights=None):
+    """include/dlwp_hip.h: dlwp_verify_spectrum_sums.  fc, ob: contiguous float32 device tensors read as flat arrays through
+    x_strides = (lead_stride, sample_stride, shift) in elements, as in verify_skill_sums; a group's run is run / width longitude rows
+    of `width` floats, 4 <= width <= 512.  weights: a HOST 1-D array, finite, >= 0, not all zero, whose length divides run / width --
+    longitude row r of a run has weight weights[r % len(weights)] -- or None.  Everything is checked here (every addressed element
+    exists) before anything is uploaded or launched.  Returns NEW device tensors (sums (leads, groups, 4, width // 2 + 1), norm
+    (leads, groups, 2)), float64, enqueued on the current stream."""
+    _check_f32(fc, ob)
+    d = _dev(fc)
+    if _dev(ob) != d:
+        raise ValueError('verify_spectrum_sums: operands on different devices')
+    leads, count0, count_dec, groups, run, width = int(leads), int(count0), int(count_dec), int(groups), int(run), int(width)
+    if leads < 1 or groups < 1 or run < 1 or count_dec < 0 or min(fc_strides) < 0 or min(ob_strides) < 0:
+        raise ValueError('verify_spectrum_sums: leads, groups, run must be >= 1; strides, shifts and count_dec >= 0')
+    if width < SPECTRUM_MIN_WIDTH or width > SPECTRUM_MAX_WIDTH:
+        raise ValueError('verify_spectrum_sums: rows of %d longitudes, the device kernel takes %d .. %d'
+                         % (width, SPECTRUM_MIN_WIDTH, SPECTRUM_MAX_WIDTH))
+    if run % width:
+        raise ValueError('verify_spectrum_sums: rows of %d longitudes do not divide a run of %d' % (width, run))
+    if max(count0, 0) * (run // width) >= 2 ** 31 - 32 or leads * groups > 2 ** 20:
+        raise ValueError('verify_spectrum_sums: %d longitude rows in a cell, %d cells: at most 2^31 and 2^20'
+                         % (max(count0, 0) * (run // width), leads * groups))
+    for name, t, st in (('fc', fc, fc_strides), ('ob', ob, ob_strides)):
+        need = verify_extent(st, leads, count0, count_dec, groups, run)
+        if need > t.numel():
+            raise ValueError('verify_spectrum_sums: operand %s holds %d elements, the strides address %d' % (name, t.numel(), need))
+    w_len = 0
+    if weights is not None:
+        weights = skill_weights(weights)
+        w_len = int(weights.size)
+        if (run // width) % w_len:
+            raise ValueError('verify_spectrum_sums: %d weights do not divide the %d longitude rows of a run' % (w_len, run // width))
+    h = _lib.handle(d)
+    weights_d = None if weights is None else torch.tensor(weights, device=fc.device)      # a copy: the caller's array may be read-only
+    tw = _spectrum_twiddles_on(fc.device, width)
+    k = width // 2 + 1
+    ws = torch.empty(max(int(_lib.lib.dlwp_verify_spectrum_workspace(h, leads, groups, width)), 8), dtype=torch.uint8,
+                     device=fc.device)
+    sums = torch.empty((leads, groups, 4, k), dtype=torch.float64, device=fc.device)
+    norm = torch.empty((leads, groups, 2), dtype=torch.float64, device=fc.device)
+    _lib.check(_lib.lib.dlwp_verify_spectrum_sums(h, _ptr(fc), int(fc_strides[0]), int(fc_strides[1]), int(fc_strides[2]),
+                                                  _ptr(ob), int(ob_strides[0]), int(ob_strides[1]), int(ob_strides[2]),
+                                                  leads, count0, count_dec, groups, run, width, _ptr(weights_d), w_len, _ptr(tw),
+                                                  _ptr(sums), _ptr(norm), _ptr(ws), ws.numel(), _stream(fc)))
+    return sums, norm
+
+
 def verify_nanmean_samples(x):
     """include/dlwp_hip.h: dlwp_verify_nanmean_samples.  x: (count, ...) contiguous float32 device tensor -> a NEW float32 tensor
     of x.shape[1:], the NaN-skipping mean over the first axis (float64 sums in sample order; NaN where no sample is finite-or-inf)."""

@@ -1220,6 +1220,41 @@ int dlwp_verify_skill_map(dlwp_handle_t, const void* fc, long long fc_lead_strid
                           size_t ws_bytes, void* stream);
 int dlwp_verify_skill_map_finish(dlwp_handle_t, const void* sums, long long cells, void* scores, void* counts, void* stream);
 
+/* ---- zonal power spectra of a forecast and its verification (csrc/spectrum.hip; no counterpart in the reference module).  fc and ob
+ *      are addressed exactly as in dlwp_verify_skill_sums (strides in ELEMENTS, all >= 0; lead f has count_f = max(count0 - f *
+ *      count_dec, 0) pairs of sample rows; row i of operand x starts at x + f * x_lead_stride + (i + f * x_shift) * x_sample_stride; a
+ *      sample row is groups x run contiguous floats).  A group's run is run / width LONGITUDE ROWS of `width` floats (4 <= width <=
+ *      512, run % width == 0); longitude row r of a run has weight weights[r % w_len] (w_len DEVICE floats, (run / width) % w_len ==
+ *      0; NULL = all ones).  twiddles: 2 * width DEVICE floats, cos(2 pi m / width) for m < width, then sin(2 pi m / width), computed
+ *      in float64 and rounded once (dlwp_amd.ops.spectrum_twiddles).
+ *      Per longitude row, d = fc - ob is rounded once in float32; O = rfft(ob), D = rfft(d) at the K = width / 2 + 1 wavenumbers (the
+ *      forecast's transform is O + D).  A row with a non-finite value among fc, ob, d is skipped whole, in every sum and in the count.
+ *      With c_0 = 1, c_k = 2, c_{width/2} = 1 for an even width, all over width^2 (sum_k c_k |X_k|^2 is the mean of x^2 of a row):
+ *        sums (device, (leads, groups, 4, K) float64) <-  0: sum w c_k |O_k|^2          1: sum w c_k |D_k|^2
+ *                                                          2: sum w c_k Re(D_k conj O_k) 3: sum w c_k Im(D_k conj O_k)
+ *        norm (device, (leads, groups, 2) float64)    <-  sum w, longitude rows counted
+ *      over the longitude rows of all pairs of the lead; a lead without pairs launches no work and reports zeros.
+ *      The transform is a product on v_mfma_f32_32x32x2_f32 (exact float32, a j-ordered fmaf chain): the row's mean m = fl32(float64
+ *      row sum / width) is taken out first, y_j = fl32(x_j - m), and X_0 is the float64 row sum itself; the row is folded, e_j = y_j +
+ *      y_{width-j} against the cosines and o_j = y_j - y_{width-j} against the sines, j <= width / 2, so a coefficient is a chain of
+ *      K products (padded with zeros to an even number); the twiddle of (j, k) is entry (j k) mod width of the table, gathered from
+ *      LDS.  Behind the product everything is float64: re and im widened, the four terms weighted and added over the rows of a
+ *      32-row tile in registers, per thread over the tiles of a block, one partial (4 K + 2 doubles) per block in ws, a second launch
+ *      that adds the partials of a cell in index order.  No atomics, no host synchronisation, identical bits on repeated calls;
+ *      max(1, 8 * CUs / cells) blocks per cell over the cells of the leads that have pairs, at most one per 32-row tile of lead 0.
+ *      16-byte loads when width and the four operand strides are multiples of 4 and fc, ob are 16-byte aligned, scalar loads
+ *      otherwise (the same bits).  dlwp_verify_spectrum_workspace returns leads * groups * B * (4 K + 2) * 8 bytes, B = ceil(8 * CUs /
+ *      (leads * groups)) (a NULL handle counts 256 CUs; 0 for sizes it refuses); ws must be 8-byte aligned.  Refused without a
+ *      launch, in this order: leads, groups or run < 1; negative strides, shifts or count_dec; width outside 4 .. 512 or not dividing
+ *      run; w_len < 1 or not dividing run / width, with weights; null fc, ob, twiddles, sums or norm; more than 2^20 cells, or 2^31
+ *      longitude rows in a cell; a workspace too small or misaligned; a null handle.  The caller guarantees that every addressed
+ *      element exists (dlwp_amd.ops.verify_spectrum_sums checks it).  Marks a recording tape foreign.                        */
+size_t dlwp_verify_spectrum_workspace(dlwp_handle_t, int leads, int groups, int width);
+int dlwp_verify_spectrum_sums(dlwp_handle_t, const void* fc, long long fc_lead_stride, long long fc_sample_stride, int fc_shift,
+                              const void* ob, long long ob_lead_stride, long long ob_sample_stride, int ob_shift, int leads, int count0,
+                              int count_dec, int groups, long long run, int width, const void* weights, int w_len,
+                              const void* twiddles, void* sums, void* norm, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- batches of a series generator cut out of an HBM-resident series (csrc/series.hip; DLWP/model/generators.py:323-629,
  *      SeriesDataGenerator.generate).  One launch fills X and every target block of a batch:
  *        dst[g.dst][i * row_d + g.dst_at + e] = src[g.src][(samples[i] + g.shift) * row_s + g.src_at + e],  e < g.len, i < n
