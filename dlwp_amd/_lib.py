@@ -376,6 +376,10 @@ _sig('dlwp_verify_label_nanmean_workspace', [_vp, _i, ctypes.c_longlong, _i], _s
 _sig('dlwp_verify_label_nanmean', [_vp, _vp, _i, ctypes.c_longlong, _P(_i), _vp, _i, _vp, _vp, _sz, _vp])
 _sig('dlwp_verify_label_error_sums', [_vp, _vp, _i, ctypes.c_longlong, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp])
 _sig('dlwp_gather_rows_fill', [_vp, _vp, ctypes.c_longlong, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _vp])
+_sig('dlwp_verify_label_quantiles_plan', [_vp, _i, ctypes.c_longlong, _i, _P(_i), _P(_i)])
+_sig('dlwp_verify_label_quantiles_workspace', [_vp, _i, ctypes.c_longlong, _i, _i], _sz)
+_sig('dlwp_verify_label_quantiles', [_vp, _vp, _i, ctypes.c_longlong, _P(_i), _vp, _i, _P(ctypes.c_double), _i, _i, _i, _vp, _vp, _vp,
+                                     _sz, _vp])
 _sig('dlwp_verify_skill_workspace', [_vp, _i, _i], _sz)
 _sig('dlwp_verify_skill_sums', [_vp, _vp, ctypes.c_longlong, ctypes.c_longlong, _i, _vp, ctypes.c_longlong, ctypes.c_longlong, _i,
                                 _i, _i, _i, _i, ctypes.c_longlong, _vp, _i, _vp, ctypes.c_longlong, _i, _vp, _i, ctypes.c_longlong,

@@ -29,7 +29,8 @@ Event verification (event_scores, ensemble_exceedance, finish_events; csrc/event
 does the ensemble say the field exceeds a threshold, and are those probabilities any good.  Thresholds are float32, K of them
 (1 <= K <= 8 on the device, any K >= 1 on the host).  A 1-D `thresholds` of K values applies to every point; anything with more
 axes is broadcast (numpy rules) to (K, *field): a threshold per point, such as climatological terciles, or per variable through
-shape (K, V, 1, 1).
+shape (K, V, 1, 1).  verify.climatological_quantiles(record, [1 / 3, 2 / 3], ...)[:, m] -- the terciles of label (month) m, taken on
+the device where the record lives -- is a valid `thresholds` argument as it stands, CUDA tensor or numpy array.
 
 * event='above': member i shows the event when x_i > thr and the event verified when y > thr; event='below': x_i < thr and
   y < thr.  Comparisons are made on the float32 values; ties are no event (the rank rule: ties count as not below).

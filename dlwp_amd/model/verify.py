@@ -43,6 +43,10 @@ zonal power spectrum of the forecast beside that of the truth, the power of the 
 Spectrum tuple.  On the device dlwp_verify_spectrum_sums (csrc/spectrum.hip) transforms the longitude rows of valid and of d =
 forecast - valid on the fp32 matrix cores and leaves four float64 sums per wavenumber; spectrum_sums returns them (they add over ranks
 or sample chunks), finish_spectrum finishes them; the host path states the definition with np.fft.rfft in float64.  DESIGN.md 5.41.
+climatological_quantiles gives the other statistic of the record that verification needs beside the monthly mean: quantiles per grid
+point and label (calendar month, a grouping of one's own, or the whole record) -- the per-point `thresholds` of ensemble.event_scores.
+On the device dlwp_verify_label_quantiles (csrc/quantile.hip) selects exactly, by bisection on the ordered bits of the values, so the
+record is not downloaded; label_quantiles_host is the same definition in numpy, and both return the same bits.  DESIGN.md 5.42.
 
 A caveat of return_device=True: the tensor may alias the cached series buffer of the model's captured rollout, which the next
 rollout of that model overwrites -- verify it (or clone it) before rolling the model out again.
@@ -573,6 +577,117 @@ def monthly_climatology(da, device=None):
             x = x.movedim(ax, 0).contiguous()
         table = ops.verify_label_nanmean(x, months, 12)
         return table if isinstance(da.values, torch.Tensor) else table.cpu().numpy()
+
+
+# -- climatological quantiles: per-point event thresholds (no counterpart in the reference module) ----------------------------------- #
+def _order_keys(x):
+    """the unsigned keys that order float32 values by their bits: -0.0 < +0.0, infinities at the ends; NaNs get the largest key"""
+    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
+    keys = np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000))
+    return np.where(np.isnan(x), np.uint32(0xffffffff), keys)
+
+
+def _from_keys(keys):
+    return np.where(keys & np.uint32(0x80000000), keys ^ np.uint32(0x80000000), ~keys).astype(np.uint32).view(np.float32)
+
+
+def label_quantiles_host(x, labels, n_labels, q, method='linear', return_count=False):
+    """The definition dlwp_verify_label_quantiles implements (include/dlwp_hip.h), in numpy: x (count, ...) float32, integer labels
+    (count,) in [0, n_labels), q a scalar or K probabilities -> (K, n_labels) + x.shape[1:] float32.  Per label and column the NaNs are
+    dropped, the n values left are sorted by the key of their bits into s, h = (n - 1) * q in float64, and 'lower' / 'higher' /
+    'nearest' return s[floor(h)] / s[ceil(h)] / s[rint(h)] with the sample's bits, 'linear' a = s[floor(h)] where h is whole and else
+    float32(a + (b - a) * (h - floor(h))) in float64 with b the next sample; NaN where n == 0.  return_count adds the (n_labels,) +
+    x.shape[1:] int32 array of n.  numpy.nanquantile on a float64 copy gives the same values; this one fixes the bits as well."""
+    from .. import ops
+    m = ops.quantile_method(method, 'label_quantiles_host')
+    q = ops.quantile_probabilities(q, None, 'label_quantiles_host')
+    x, labels = np.asarray(x), np.asarray(labels)
+    if x.dtype != np.float32 or x.ndim < 2:
+        raise TypeError('label_quantiles_host: x must be a float32 array (count, ...), got %s of rank %d' % (x.dtype, x.ndim))
+    if labels.shape != (x.shape[0],) or labels.dtype.kind not in 'iu':
+        raise ValueError('label_quantiles_host: labels must be %d integers, got %s %r' % (x.shape[0], labels.dtype, labels.shape))
+    if n_labels < 1 or (labels.size and (int(labels.min()) < 0 or int(labels.max()) >= n_labels)):
+        raise ValueError('label_quantiles_host: labels must lie in [0, %d)' % n_labels)
+    inner = x.shape[1:]
+    flat = x.reshape(x.shape[0], -1)
+    out = np.full((q.size, n_labels, flat.shape[1]), np.nan, np.float32)
+    counts = np.zeros((n_labels, flat.shape[1]), np.int32)
+    for l in range(n_labels):
+        rows = flat[labels == l]
+        if not rows.shape[0]:
+            continue
+        keys = np.sort(_order_keys(rows), axis=0)            # NaNs last
+        n = np.count_nonzero(~np.isnan(rows), axis=0)
+        counts[l] = n
+        last = np.maximum(n - 1, 0)
+
+        def pick(rank):
+            return _from_keys(np.take_along_axis(keys, np.minimum(rank.astype(np.int64), last)[None], axis=0)[0])
+        for k in range(q.size):
+            h = last.astype(np.float64) * q[k]
+            lo = np.floor(h)
+            if m == 0:
+                a, b, g = pick(lo), pick(lo + 1), h - lo
+                with np.errstate(invalid='ignore', over='ignore'):
+                    mid = (a.astype(np.float64) + (b.astype(np.float64) - a.astype(np.float64)) * g).astype(np.float32)
+                mid = np.where(np.isnan(mid), np.float32(np.nan), mid)         # one NaN: 0x7fc00000
+                val = np.where(g == 0, a, mid)
+            else:
+                val = pick(lo if m == 1 else (np.ceil(h) if m == 2 else np.rint(h)))
+            out[k, l] = np.where(n > 0, val, np.float32(np.nan))
+    out = out.reshape((q.size, n_labels) + inner)
+    return (out, counts.reshape((n_labels,) + inner)) if return_count else out
+
+
+def climatological_quantiles(da, q, labels='month', n_labels=None, method='linear', return_count=False, device=None):
+    """Quantiles of a record per grid point: the per-point `thresholds` of ensemble.event_scores / ensemble_exceedance -- terciles, "the
+    95th percentile of this month".  `da` is a LabeledArray with a datetime64 'sample' or 'time' coordinate, which becomes the leading
+    axis as in monthly_climatology; q a scalar or a sequence of K probabilities (at most 8 on the device).  labels='month' groups by
+    calendar month (12 labels, month_labels), labels=None takes the whole record as one label, an integer array (one label per time)
+    with n_labels any other grouping, seasons for instance.  Returns (K, n_labels, ...) float32 -- a scalar q keeps the leading axis of
+    length 1 -- NaN where a label has no non-NaN sample at a point, and with return_count the (n_labels, ...) int32 sample counts.
+    method: 'linear' | 'lower' | 'higher' | 'nearest' as in numpy.nanquantile.  device='cuda' or CUDA values select on the device
+    (dlwp_verify_label_quantiles: the record is not downloaded); the result is a CUDA tensor for CUDA values and numpy otherwise.
+    Host and device return the same bits (label_quantiles_host is the definition)."""
+    from .. import ops
+    who = 'climatological_quantiles'
+    on_device = isinstance(da.values, torch.Tensor) or device is not None
+    m = ops.quantile_method(method, who)
+    q = ops.quantile_probabilities(q, ops.QUANTILE_MAX_K if on_device else None, who)
+    time_dim = 'sample' if 'sample' in da.dims else 'time'
+    ax = da.dims.index(time_dim)
+    count = int(da.values.shape[ax])
+    if isinstance(labels, str):
+        if labels != 'month':
+            raise ValueError("%s: labels %r, expected 'month', None or an integer array" % (who, labels))
+        labels, n_labels = _months(np.asarray(da.coords[time_dim])), 12
+    elif labels is None:
+        labels, n_labels = np.zeros(count, np.int32), 1
+    else:
+        labels = np.asarray(labels)
+        if n_labels is None:
+            raise ValueError('%s: an array of labels needs n_labels' % who)
+    n_labels = int(n_labels)
+    if labels.shape != (count,) or labels.dtype.kind not in 'iu':
+        raise ValueError('%s: labels must be %d integers, got %s %r' % (who, count, labels.dtype, labels.shape))
+    if not 1 <= n_labels <= ops.VERIFY_MAX_LABELS or (count and (int(labels.min()) < 0 or int(labels.max()) >= n_labels)):
+        raise ValueError('%s: labels must lie in [0, n_labels) with n_labels in 1 .. %d' % (who, ops.VERIFY_MAX_LABELS))
+    if on_device and not isinstance(da.values, torch.Tensor) and np.asarray(da.values).dtype != np.float32:
+        raise TypeError("'da' must be float32 on the device path, got %s" % np.asarray(da.values).dtype)
+    dev = _cuda_device(da.values, device)
+    if dev is None:
+        x = np.moveaxis(da.values, ax, 0)
+        if x.dtype != np.float32:
+            x = x.astype(np.float32)
+        return label_quantiles_host(x, labels, n_labels, q, method, return_count)
+    with torch.cuda.device(dev):
+        x = _to_device(da.values, dev)
+        if ax:
+            x = x.movedim(ax, 0).contiguous()
+        res = ops.verify_label_quantiles(x, labels, n_labels, q, method, want_count=return_count)
+        if isinstance(da.values, torch.Tensor):
+            return res
+        return tuple(t.cpu().numpy() for t in res) if return_count else res.cpu().numpy()
 
 
 def _skill_groups_run(who, inner, axis, lead_axes):

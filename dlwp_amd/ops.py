@@ -2074,6 +2074,66 @@ def verify_label_nanmean(x, labels, n_labels, ws=None):
     return mean
 
 
+QUANTILE_METHODS = ('linear', 'lower', 'higher', 'nearest')      # DLWP_QUANTILE_* of include/dlwp_hip.h, in that order
+QUANTILE_MAX_K = 8
+
+
+def quantile_probabilities(q, max_k=None, who='verify_label_quantiles'):
+    """q (a scalar or a 1-D sequence) as a contiguous float64 array of K >= 1 finite probabilities in [0, 1]; at most max_k of them"""
+    q = np.atleast_1d(np.asarray(q, dtype=np.float64))
+    if q.ndim != 1 or q.size < 1:
+        raise ValueError('%s: q must be a scalar or a 1-D sequence of at least one probability, got shape %r' % (who, q.shape))
+    if not np.all(np.isfinite(q)) or q.min() < 0.0 or q.max() > 1.0:
+        raise ValueError('%s: every q must be finite and lie in [0, 1], got %r' % (who, q.tolist()))
+    if max_k is not None and q.size > max_k:
+        raise ValueError('%s: %d probabilities, at most %d on the device' % (who, q.size, max_k))
+    return np.ascontiguousarray(q)
+
+
+def quantile_method(method, who='verify_label_quantiles'):
+    if method not in QUANTILE_METHODS:
+        raise ValueError("%s: method %r, expected one of %s" % (who, method, ', '.join(QUANTILE_METHODS)))
+    return QUANTILE_METHODS.index(method)
+
+
+def verify_label_quantiles_plan(max_len, row, route=0, device_index=None):
+    """include/dlwp_hip.h: dlwp_verify_label_quantiles_plan.  (route, cols) the kernel takes for a longest label list of max_len rows of
+    `row` floats: route 1 (LDS, tiles of cols = 64 / 32 / 16 columns) or 2 (streaming).  Host logic: runs without a GPU."""
+    r, c = ctypes.c_int(0), ctypes.c_int(0)
+    h = _lib.handle_or_none(device_index)
+    _lib.check(_lib.lib.dlwp_verify_label_quantiles_plan(h, int(max_len), int(row), int(route), ctypes.byref(r), ctypes.byref(c)))
+    return r.value, c.value
+
+
+def verify_label_quantiles(x, labels, n_labels, q, method='linear', route=0, want_count=False, ws=None):
+    """include/dlwp_hip.h: dlwp_verify_label_quantiles.  x: (count, ...) contiguous float32 device tensor; labels: HOST integer array
+    (count,) in [0, n_labels); q: a scalar or up to 8 probabilities in [0, 1]; all of it checked here before anything is uploaded.
+    Returns a NEW float32 tensor (K, n_labels) + x.shape[1:], the NaN-skipping quantiles of the rows of each label (NaN where a label
+    has no non-NaN sample) -- and with want_count a NEW int32 tensor (n_labels,) + x.shape[1:] of the samples counted.  method:
+    'linear' | 'lower' | 'higher' | 'nearest' as in numpy.nanquantile; route: 0 planner, 1 LDS, 2 streaming (same bits)."""
+    _check_f32(x)
+    m = quantile_method(method)
+    q = quantile_probabilities(q, QUANTILE_MAX_K)
+    if route not in (0, 1, 2):
+        raise ValueError('verify_label_quantiles: route %r, expected 0 (planner), 1 (LDS) or 2 (streaming)' % (route,))
+    count, row = _rows_of(x, 'verify_label_quantiles')
+    offsets, index = label_lists(labels, n_labels)
+    if index.size != count:
+        raise ValueError('verify_label_quantiles: %d labels for %d samples' % (index.size, count))
+    n_labels, k = int(n_labels), int(q.size)
+    h = _lib.handle(_dev(x))
+    if ws is None:
+        need = int(_lib.lib.dlwp_verify_label_quantiles_workspace(h, count, row, n_labels, k))
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=x.device)
+    index_d = torch.from_numpy(index).to(x.device)
+    out = torch.empty((k, n_labels) + tuple(x.shape[1:]), dtype=torch.float32, device=x.device)
+    counts = torch.empty((n_labels,) + tuple(x.shape[1:]), dtype=torch.int32, device=x.device) if want_count else None
+    _lib.check(_lib.lib.dlwp_verify_label_quantiles(h, _ptr(x), count, row, offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                                                    _ptr(index_d), n_labels, q.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), k, m,
+                                                    int(route), _ptr(out), _ptr(counts), _ptr(ws), ws.numel(), _stream(x)))
+    return (out, counts) if want_count else out
+
+
 def verify_label_error_sums(x, rows, labels, table, anomaly=False, ws=None):
     """include/dlwp_hip.h: dlwp_verify_label_error_sums.  x: (count_x, ...) and table: (n_labels, ...) contiguous float32 device
     tensors with equal rows; rows, labels: HOST integer arrays (m,), checked here against count_x and n_labels before they are

@@ -1148,6 +1148,48 @@ int dlwp_verify_label_error_sums(dlwp_handle_t, const void* x, int count_x, long
 int dlwp_gather_rows_fill(dlwp_handle_t, const void* src, long long src_rows, long long row, const void* rows, long long n, void* dst,
                           void* stream);
 
+/* ---- climatological quantiles (csrc/quantile.hip; no counterpart in the reference module: the per-point event thresholds of
+ *      dlwp_ens_event_counts -- terciles, "the 95th percentile of this month" -- from the record itself).  Conventions as above:
+ *      float32 data, 64-bit offsets, no synchronisation, no atomics; the selection counts integers, so the result does not depend on
+ *      scheduling and there is no float64 sum.  dlwp_verify_label_quantiles marks a recording tape foreign.
+ *      dlwp_verify_label_quantiles: x (count, row) contiguous float32, labels as the per-label lists of dlwp_verify_label_nanmean
+ *      (`offsets` HOST, n_labels + 1 ints; `index` DEVICE, count ints; an index outside [0, count) is skipped, never read), q a HOST
+ *      array of k probabilities, 1 <= k <= 8, each finite and in [0, 1] -> out (k, n_labels, row) float32 and, if counts is not NULL,
+ *      counts (n_labels, row) int32, the non-NaN samples.  Per (label, column): NaNs (v != v) are dropped, n values are left; every
+ *      output of the column is the quiet NaN 0x7fc00000 when n == 0.  The values are ordered by the unsigned key of their bits u
+ *      (u ^ 0xffffffff with the sign bit set, else u | 0x80000000: a total order, -0.0 < +0.0, infinities at the ends) into
+ *      s[0] <= ... <= s[n - 1]; h = (n - 1) * q is ONE float64 product, and
+ *        DLWP_QUANTILE_LOWER    s[floor(h)]           DLWP_QUANTILE_HIGHER   s[ceil(h)]
+ *        DLWP_QUANTILE_NEAREST  s[rint(h)], halves to even
+ *        DLWP_QUANTILE_LINEAR   a = s[floor(h)], b = s[min(floor(h) + 1, n - 1)], g = h - floor(h): a when g == 0, else
+ *                               float32(a + (b - a) * g), every operation rounded once in float64 (no fused multiply-add) and the
+ *                               sum rounded once to float32; a NaN result (inf - inf) is stored as 0x7fc00000.
+ *      The order statistics keep the bits of the sample (the sign of a zero included).  numpy.nanquantile on a float64 copy, rounded to
+ *      float32, gives the same values.  Algorithm: bisection on the key, most significant bit first -- 32 sweeps over the column's
+ *      keys, each counting for every rank the keys below prefix | bit -- after one sweep that counts n.
+ *      route 1, LDS: a workgroup of four waves owns (label, tile of cols adjacent columns), gathers the label's rows of the tile into
+ *      LDS once as keys (16-byte loads when row % 4 == 0 and x is 16-byte aligned, else scalar) and sweeps there; cols is the widest
+ *      of 64, 32, 16 with round_up(max_len, 256 / cols) * cols * 4 <= 81920 bytes (half of the CU's 160 KiB: two workgroups per CU),
+ *      max_len the longest list: 320, 640 or 1280 rows.  route 2, streaming: the same sweeps read x through the index list (33 reads
+ *      of the label's rows, 64 columns per workgroup); no limit on max_len.  route 0: LDS when max_len fits, else streaming.  Both
+ *      routes return the same bits.  dlwp_verify_label_quantiles_plan reports the choice (route_out: 1 or 2) and the tile width
+ *      (cols_out) for a longest list of max_len rows; it needs no handle.  dlwp_verify_label_quantiles_workspace returns
+ *      n_labels * row * 4 bytes rounded up to 16 (0 for sizes it refuses): ws receives the counts when `counts` is NULL, and must be
+ *      16-byte aligned.
+ *      Refused without a launch, in this order: count or row < 1, n_labels outside 1 .. 64, k outside 1 .. 8, a q that is NULL, not
+ *      finite or outside [0, 1], an unknown method, an unknown route, null pointers (x, offsets, index, out, ws), offsets that do not
+ *      run from 0 to count without decreasing, a row too long for one grid, route 1 with a list that does not fit, a workspace that is
+ *      too small or misaligned, a null handle.                                                                                     */
+#define DLWP_QUANTILE_LINEAR  0
+#define DLWP_QUANTILE_LOWER   1
+#define DLWP_QUANTILE_HIGHER  2
+#define DLWP_QUANTILE_NEAREST 3
+int dlwp_verify_label_quantiles_plan(dlwp_handle_t, int max_len, long long row, int route, int* route_out, int* cols_out);
+size_t dlwp_verify_label_quantiles_workspace(dlwp_handle_t, int count, long long row, int n_labels, int k);
+int dlwp_verify_label_quantiles(dlwp_handle_t, const void* x, int count, long long row, const int* offsets, const void* index,
+                                int n_labels, const double* q, int k, int method, int route, void* out, void* counts /* may be NULL */,
+                                void* ws, size_t ws_bytes, void* stream);
+
 /* ---- latitude-weighted forecast skill (csrc/skill.hip; no counterpart in the reference module, which stops at unweighted mse / mae /
  *      rmse; the anomaly correlation is the reference's training metric, DLWP/custom.py anomaly_correlation).  dlwp_verify_skill_sums
  *      reads a forecast fc and an observation ob addressed exactly as a and b of dlwp_verify_error_sums (strides in ELEMENTS, all
