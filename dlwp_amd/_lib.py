@@ -159,6 +159,14 @@ class LaunchInfo(ctypes.Structure):
                 ('matrix_flops', ctypes.c_double), ('bf16_matrix', ctypes.c_int), ('x_loader', ctypes.c_int)]
 
 
+class RowconvLaunchInfo(ctypes.Structure):
+    """dlwp_rowconv_launch_info (include/dlwp_hip.h): what one pass of the row-connected layer launches"""
+    _fields_ = [('kind', ctypes.c_int), ('targ', ctypes.c_int * 2), ('grid', ctypes.c_int), ('block_threads', ctypes.c_int),
+                ('lds_bytes', ctypes.c_int), ('circ', ctypes.c_int), ('fold', ctypes.c_int), ('reason', ctypes.c_int),
+                ('n_cb', ctypes.c_int), ('n_sg', ctypes.c_int), ('n_cg', ctypes.c_int), ('n_mg', ctypes.c_int),
+                ('samples', ctypes.c_int)]
+
+
 class DlwpError(RuntimeError):
     """A non-zero status from libdlwp_hip.so (message from dlwp_last_error())."""
 
@@ -265,7 +273,8 @@ _sig('dlwp_conv2d_wgrad_pick_config', [_vp, Shape4, _P(Conv2d)])
 _sig('dlwp_rowconv2d_fwd', [_vp, _vp, _vp, _vp, _vp, Shape4, _P(Conv2d), _i, _vp])
 _sig('dlwp_rowconv2d_fwd_direct', [_vp, _vp, _vp, _vp, _vp, Shape4, _P(Conv2d), _i, _vp])
 _sig('dlwp_rowconv2d_uses_matrix_cores', [_vp, Shape4, _P(Conv2d), _i])
-_sig('dlwp_rowconv2d_bwd_workspace', [_vp, Shape4, _P(Conv2d), _P(_sz)])
+_sig('dlwp_rowconv2d_launch_info', [_vp, Shape4, _P(Conv2d), _i, _P(RowconvLaunchInfo)])
+_sig('dlwp_rowconv2d_bwd_workspace',[_vp, Shape4, _P(Conv2d), _P(_sz)])
 _sig('dlwp_rowconv2d_bwd_data', [_vp, _vp, _vp, _vp, Shape4, _P(Conv2d), _i, _vp, _sz, _vp])
 _sig('dlwp_rowconv2d_bwd_weight', [_vp, _vp, _vp, _vp, _vp, Shape4, _P(Conv2d), _i, _i, _vp])
 _sig('dlwp_act_bwd', [_vp, _vp, _vp, _vp, _sz, _i, _i, _vp])

@@ -507,7 +507,7 @@ __global__ __launch_bounds__(256, 2) void rowconv2d_wgrad_mfma(const RowArgs a) 
   const int n_frag = min(a.NF, m_total - mf0);          // this workgroup's fragments, 3 per wave at most
   constexpr unsigned DROP = 0x7ffffff0u;
   const int iy = dlwp_map_coord_tile(r + ky - a.pad_top, a.H, a.mode_h);
-  const int ksteps = (a.Wo + 3) >> 2, wo4 = ksteps * 4;
+  const int kfull = a.Wo >> 2, ktail = a.Wo & 3, wo4 = (kfull + (ktail ? 1 : 0)) * 4;      // whole k steps, columns of a ragged last one
   // lane offsets of the column slots (0.0 beyond the descriptors: zero halo, columns past Wo)
   unsigned xoff[NSLOT], zoff[NSLOT];
 #pragma unroll
@@ -607,7 +607,7 @@ __global__ __launch_bounds__(256, 2) void rowconv2d_wgrad_mfma(const RowArgs a) 
     // every wave multiplies 3 fragments (one that owns fewer repeats its last); two k steps per iteration, their 8 LDS
     // reads issued before the first MFMA
     int kc = 0;
-    for (; kc + 1 < ksteps; kc += 2) {
+    for (; kc + 1 < kfull; kc += 2) {
       float bv[2], av[2][3];
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
@@ -620,10 +620,18 @@ __global__ __launch_bounds__(256, 2) void rowconv2d_wgrad_mfma(const RowArgs a) 
 #pragma unroll
         for (int i = 0; i < 3; ++i) acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[h][i], bv[h], acc[i], 0, 0, 0);
     }
-    if (kc < ksteps) {
+    if (kc < kfull) {
       const float bv = zs[zbase + 4 * kc];
 #pragma unroll
       for (int i = 0; i < 3; ++i) acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(xs[abase[i] + 4 * kc], bv, acc[i], 0, 0, 0);
+    }
+    // the ragged last step: its columns past Wo hold dz = 0.0, but the x beside them is real data (columns a SMALLER kx reads
+    // legitimately) -- masked as well, or a NaN / Inf there would reach, as 0 x NaN, a dw[.., kx, ..] that never reads it
+    if (ktail) {
+      const float bv = zs[zbase + 4 * kfull];
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+        acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(kq < ktail ? xs[abase[i] + 4 * kfull] : 0.f, bv, acc[i], 0, 0, 0);
     }
     __syncthreads();
   }
@@ -706,8 +714,8 @@ int ilog2(int v) {
 }
 
 int validate_row(const char* fn, dlwp_handle_t h, dlwp_shape4 xs, const dlwp_conv2d* cd, int dtype, dlwp_shape4* ys,
-                 bool upsampled_ok = true) {
-  DLWP_CHECK_ARG(h && cd, "%s: null handle or descriptor", fn);
+                 bool upsampled_ok = true, bool host_only = false) {
+  DLWP_CHECK_ARG((h || host_only) && cd, "%s: null handle or descriptor", fn);
   DLWP_CHECK_ARG(dtype == DLWP_F32, "%s: float32 only (dtype 0x%x)", fn, dtype);
   DLWP_CHECK_ARG(xs.n >= 0 && xs.c > 0 && xs.h > 0 && xs.w > 0, "%s: bad input shape (%d,%d,%d,%d)", fn, xs.n, xs.c, xs.h,
                  xs.w);
@@ -738,8 +746,11 @@ RowArgs base_args(dlwp_shape4 xs, const dlwp_conv2d* cd, dlwp_shape4 ys) {
   return a;
 }
 
-// forward tiling; returns the LDS bytes, 0 when the matrix-core kernel does not cover the geometry
-size_t plan_fwd(RowArgs& a) {
+// why a planner hands a pass to its vector kernel (dlwp_rowconv_launch_info.reason)
+enum { kWhyNone = 0, kWhyKernelHeight = 1, kWhyWidth = 2, kWhyLds = 3, kWhyOffsets = 4, kWhyEmptyBatch = 5 };
+
+// forward tiling; returns the LDS bytes, 0 (and the reason in *why) when the matrix-core kernel does not cover the geometry
+size_t plan_fwd(RowArgs& a, int* why) {
   int cout_p = 16;
   if (a.Cout <= 8) {
     cout_p = 1;
@@ -762,7 +773,8 @@ size_t plan_fwd(RowArgs& a) {
   if (a.S > a.N) a.S = a.N > 0 ? a.N : 1;
   a.n_sg = dlwp_ceil_div(a.N, a.S);
   a.TW_in = a.FX * 16 * P + a.kw - 1;
-  if (a.TW_in > 64 * kMaxSlots || a.kh > kKhMax) return 0;
+  if (a.kh > kKhMax) return *why = kWhyKernelHeight, 0;
+  if (a.TW_in > 64 * kMaxSlots) return *why = kWhyWidth, 0;
   const int q_min = a.FX * 16 + ((a.U - 1) >> a.P_log2) + 1;
   // staging writes 32 consecutive columns = 32 / P consecutive positions in each of the P groups: a group stride that is an
   // odd multiple of 32 / P keeps the groups on disjoint banks
@@ -774,7 +786,7 @@ size_t plan_fwd(RowArgs& a) {
   a.RS = a.Q * P;
   a.PS = round_mod32(a.kh * a.RS, 16);
   if ((double)a.in_c_total * a.Hs * a.Ws * 8.0 >= 2.0e9 || (double)a.kh * a.kw * a.Cin * a.Cout * 4.0 >= 2.0e9)
-    return 0;                               // 32-bit descriptor offsets (two samples' channel windows; one row's filters)
+    return *why = kWhyOffsets, 0;           // 32-bit descriptor offsets (two samples' channel windows; one row's filters)
   const int plane_cap = dlwp_ceil_div(a.TW_in, 64) > 4 ? 4 : 8;   // (sample, channel) planes of one staging round (registers)
   if (a.S > plane_cap / 4) {
     a.S = plane_cap / 4;
@@ -788,10 +800,10 @@ size_t plan_fwd(RowArgs& a) {
     if (bytes < 2 * 3 * 4 * 64 * sizeof(float)) bytes = 2 * 3 * 4 * 64 * sizeof(float);    // the k halves' hand-over area
     if (bytes <= (size_t)kLdsBudget) return bytes;
   }
-  return 0;
+  return *why = kWhyLds, 0;
 }
 
-size_t plan_dgrad(RowArgs& a) {
+size_t plan_dgrad(RowArgs& a, int* why) {
   a.CK = (a.Cout + 3) & ~3;                      // co padded to whole k steps
   const int cfr = dlwp_ceil_div(a.Cin, 16);
   a.NF = cfr < 2 ? cfr : 2;
@@ -804,19 +816,20 @@ size_t plan_dgrad(RowArgs& a) {
   if (a.S > a.N) a.S = a.N > 0 ? a.N : 1;
   a.n_sg = dlwp_ceil_div(a.N, a.S);
   a.TW_in = a.FX * 16 + a.kw - 1;
-  if (a.TW_in > 128) return 0;              // the kernel stages two 64-lane column slots per tile row (goff[2])
+  if (a.kh > kKhMax) return *why = kWhyKernelHeight, 0;       // unrolled rows
+  if (a.TW_in > 128) return *why = kWhyWidth, 0;      // the kernel stages two 64-lane column slots per tile row (goff[2])
   a.RS = a.TW_in;
   a.PS = round_mod32(a.kh * a.RS, 16);
   a.SS = a.CK * a.PS;
   a.w_off = a.S * a.SS;
   const size_t bytes = ((size_t)a.w_off + (size_t)a.kh * a.kw * (a.CK / 4) * a.NF * 64) * sizeof(float);
-  if (a.kh > kKhMax || (double)a.Ho * a.kh * a.kw * a.Cin * a.Cout * 4.0 >= 2.0e9 ||
-      (double)a.S * a.out_c_total * a.Ho * a.Wo * 4.0 >= 2.0e9)
-    return 0;                               // unrolled rows; 32-bit descriptor offsets
-  return bytes <= (size_t)kLdsBudget ? bytes : 0;
+  if ((double)a.Ho * a.kh * a.kw * a.Cin * a.Cout * 4.0 >= 2.0e9 || (double)a.S * a.out_c_total * a.Ho * a.Wo * 4.0 >= 2.0e9)
+    return *why = kWhyOffsets, 0;           // 32-bit descriptor offsets
+  if (bytes > (size_t)kLdsBudget) return *why = kWhyLds, 0;
+  return bytes;
 }
 
-size_t plan_wgrad(RowArgs& a) {
+size_t plan_wgrad(RowArgs& a, int* why) {
   const int c16 = dlwp_ceil_div(a.Cin, 16);
   const int m_total = a.kw * c16;
   a.n_mg = dlwp_ceil_div(m_total, 12);
@@ -824,11 +837,13 @@ size_t plan_wgrad(RowArgs& a) {
   a.n_cg = dlwp_ceil_div(a.Cout, 16);
   const int wo4 = (a.Wo + 3) & ~3;
   a.TW_in = wo4 + a.kw - 1;
-  if (a.TW_in > 64 * kMaxSlots || (double)a.Cin * a.Hs * a.Ws * 4.0 >= 2.0e9 || (double)a.Ho * a.Wo * 64.0 >= 2.0e9) return 0;
+  if (a.TW_in > 64 * kMaxSlots) return *why = kWhyWidth, 0;
+  if ((double)a.Cin * a.Hs * a.Ws * 4.0 >= 2.0e9 || (double)a.Ho * a.Wo * 64.0 >= 2.0e9) return *why = kWhyOffsets, 0;
   a.PS = round_mod32(a.TW_in, 2);
   a.w_off = c16 * 16 * a.PS;
   const size_t bytes = ((size_t)a.w_off + 16 * (size_t)a.PS) * sizeof(float);
-  return bytes <= 96 * 1024 ? bytes : 0;
+  if (bytes > 96 * 1024) return *why = kWhyLds, 0;
+  return bytes;
 }
 
 template <class K>
@@ -841,6 +856,78 @@ int set_lds(K kernel, size_t bytes) {
 int grid_1d(long long total, int block) {
   long long g = (total + block - 1) / block;
   return (int)(g < 1 ? 1 : (g > 65535 * 16 ? 65535 * 16 : g));
+}
+
+// What one pass launches.  Decided once, here, for the entry point and for dlwp_rowconv2d_launch_info alike: the entry points
+// switch on (mfma, t0, t1) and launch `grid` workgroups of `block` threads with `lds` bytes, nothing else.
+struct RowRoute {
+  int mfma;          // 1: the matrix-core kernel <t0, t1>; 0: the vector kernel, for `reason` (grid 0: nothing is launched)
+  int t0, t1;        // forward NSLOT, C4N; data gradient NF, 0; weight gradient NSLOT, XR
+  long long grid;
+  int block, reason;
+  int fold;          // data gradient: dlwp_pad2d_bwd follows (the kernel wrote the padded temporary)
+  size_t lds;
+};
+
+RowRoute route_fwd(RowArgs& a) {
+  RowRoute rt = {};
+  rt.block = 256;
+  if (a.N == 0) return rt.reason = kWhyEmptyBatch, rt;
+  rt.lds = plan_fwd(a, &rt.reason);
+  if (rt.lds == 0) {
+    rt.grid = grid_1d((long long)a.N * a.Cout * a.Ho * a.Wo, 256);
+    return rt;
+  }
+  const int slots = dlwp_ceil_div(a.TW_in, 64);
+  rt.mfma = 1;
+  rt.t0 = slots <= 2 ? 2 : (slots <= 4 ? 4 : kMaxSlots);
+  rt.t1 = a.CK / 4;
+  rt.grid = (long long)a.Ho * a.n_sg * a.n_cg * a.n_cb;
+  return rt;
+}
+
+RowRoute route_dgrad(RowArgs& a) {
+  RowRoute rt = {};
+  rt.block = 256;
+  if (a.N == 0) return rt.reason = kWhyEmptyBatch, rt;
+  const int halo_w = a.Wp - a.W, halo_h = a.Hp - a.H;      // left + right, top + bottom
+  // The call-site halo -- periodic columns that make the convolution circular (left + right = kw - 1: Wo == W), zero rows --
+  // needs no padded temporary and no folding pass: the gradient of a zero halo row is dropped, and the periodic images of a
+  // column are reached by letting dz wrap while it is staged (the fold was a third of this pass: 0.062 of 0.205 ms)
+  const bool circ = a.mode_w == DLWP_PAD_WRAP && halo_w == a.kw - 1 && halo_w > 0 && (a.mode_h == DLWP_PAD_ZERO || halo_h == 0) &&
+                    a.Wo == a.W && a.kw - 1 <= a.W;       // (dz wraps once while it is staged)
+  if (circ) {
+    a.circ = 1; a.OH = a.H; a.OW = a.W;
+  }
+  rt.lds = plan_dgrad(a, &rt.reason);
+  if (rt.lds == 0) {
+    a.circ = 0; a.OH = a.Hp; a.OW = a.Wp;
+    rt.grid = grid_1d((long long)a.N * a.Cin * a.Hp * a.Wp, 256);
+  } else {
+    rt.mfma = 1;
+    rt.t0 = a.NF;
+    rt.block = 128;
+    rt.grid = (long long)a.OH * a.n_sg * a.n_cg * a.n_cb;
+  }
+  rt.fold = (halo_w || halo_h) && !a.circ;
+  return rt;
+}
+
+RowRoute route_wgrad(RowArgs& a) {
+  RowRoute rt = {};
+  rt.block = 256;
+  if (a.N > 0) rt.lds = plan_wgrad(a, &rt.reason);
+  else rt.reason = kWhyEmptyBatch;        // no sample to stage: the vector kernel writes the zeros (or keeps dw, accumulating)
+  if (rt.lds == 0) {
+    rt.grid = grid_1d((long long)a.Ho * a.kh * a.kw * a.Cin * a.Cout, 256);
+    return rt;
+  }
+  rt.mfma = 1;
+  rt.t0 = dlwp_ceil_div(a.TW_in, 64) <= 3 ? 3 : kMaxSlots;
+  // channel rows per wave and sample held in registers (the wide rows have no 8-row instance: rounds of 4 before the k loop)
+  rt.t1 = a.Cin <= 16 ? 4 : (a.Cin <= 32 && rt.t0 == 3 ? 8 : 0);
+  rt.grid = (long long)a.Ho * a.kh * a.n_cg * a.n_mg;
+  return rt;
 }
 
 }  // namespace
@@ -857,30 +944,28 @@ int dlwp_rowconv2d_fwd(dlwp_handle_t h, const void* x, const void* w, const void
   RowArgs a = base_args(xs, cd, ys);
   a.x = (const float*)x; a.w = (const float*)w; a.bias = (const float*)bias; a.y = (float*)y;
   hipStream_t s = (hipStream_t)stream;
-  const size_t lds = plan_fwd(a);
-  if (lds == 0) {
-    hipLaunchKernelGGL(rowconv2d_fwd_simple, dim3(grid_1d((long long)a.N * a.Cout * a.Ho * a.Wo, 256)), dim3(256), 0, s, a);
+  const RowRoute rt = route_fwd(a);
+  if (!rt.mfma) {
+    hipLaunchKernelGGL(rowconv2d_fwd_simple, dim3((unsigned)rt.grid), dim3(rt.block), 0, s, a);
     DLWP_LAUNCH_CHECK("rowconv2d_fwd_simple");
     return DLWP_OK;
   }
-  const long long grid = (long long)a.Ho * a.n_sg * a.n_cg * a.n_cb;
-  DLWP_CHECK_ARG(grid < (1ll << 31), "dlwp_rowconv2d_fwd: grid too large");
-  const int slots = dlwp_ceil_div(a.TW_in, 64);
+  DLWP_CHECK_ARG(rt.grid < (1ll << 31), "dlwp_rowconv2d_fwd: grid too large");
   auto launch = [&](auto kernel) -> int {
-    DLWP_HIP((hipError_t)set_lds(kernel, lds));
-    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(256), lds, s, a);
+    DLWP_HIP((hipError_t)set_lds(kernel, rt.lds));
+    hipLaunchKernelGGL(kernel, dim3((unsigned)rt.grid), dim3(rt.block), rt.lds, s, a);
     DLWP_LAUNCH_CHECK("rowconv2d_fwd_mfma");
     return DLWP_OK;
   };
-  if (a.CK == 8) {
-    if (slots <= 2) return launch(rowconv2d_fwd_mfma<2, 2>);
-    if (slots <= 4) return launch(rowconv2d_fwd_mfma<4, 2>);
-    return launch(rowconv2d_fwd_mfma<kMaxSlots, 2>);
+  switch (rt.t0 * 10 + rt.t1) {
+    case 21: return launch(rowconv2d_fwd_mfma<2, 1>);
+    case 22: return launch(rowconv2d_fwd_mfma<2, 2>);
+    case 41: return launch(rowconv2d_fwd_mfma<4, 1>);
+    case 42: return launch(rowconv2d_fwd_mfma<4, 2>);
+    case kMaxSlots * 10 + 1: return launch(rowconv2d_fwd_mfma<kMaxSlots, 1>);
+    // no <kMaxSlots, 2>: more than 4 slots leave plan_fwd 4 planes per staging round, one sample of 4 channels (tests/test_rowconv_cases_cpu.py)
   }
-  if (slots <= 2) return launch(rowconv2d_fwd_mfma<2, 1>);
-  if (slots <= 4) return launch(rowconv2d_fwd_mfma<4, 1>);
-  return launch(rowconv2d_fwd_mfma<kMaxSlots, 1>);
-  return DLWP_OK;
+  DLWP_FAIL(DLWP_EUNSUPPORTED, "dlwp_rowconv2d_fwd: no rowconv2d_fwd_mfma<%d, %d> instance", rt.t0, rt.t1);
 }
 
 int dlwp_rowconv2d_fwd_direct(dlwp_handle_t h, const void* x, const void* w, const void* bias, void* y, dlwp_shape4 xs,
@@ -902,7 +987,28 @@ int dlwp_rowconv2d_uses_matrix_cores(dlwp_handle_t h, dlwp_shape4 xs, const dlwp
   dlwp_shape4 ys;
   if (!cd || dlwp_conv2d_out_shape(xs, cd, &ys) != DLWP_OK) return 0;
   RowArgs a = base_args(xs, cd, ys);
-  return (pass == 0 ? plan_fwd(a) : (pass == 1 ? plan_dgrad(a) : plan_wgrad(a))) != 0;
+  return (pass == 0 ? route_fwd(a) : (pass == 1 ? route_dgrad(a) : route_wgrad(a))).mfma;
+}
+
+int dlwp_rowconv2d_launch_info(dlwp_handle_t h, dlwp_shape4 xs, const dlwp_conv2d* cd, int pass, dlwp_rowconv_launch_info* info) {
+  DLWP_CHECK_ARG(info && pass >= 0 && pass <= 2, "dlwp_rowconv2d_launch_info: null pointer or pass %d not in 0 .. 2", pass);
+  dlwp_shape4 ys;
+  if (int rc = validate_row("dlwp_rowconv2d_launch_info", h, xs, cd, DLWP_F32, &ys, pass != 1, true)) return rc;
+  RowArgs a = base_args(xs, cd, ys);
+  const RowRoute rt = pass == 0 ? route_fwd(a) : (pass == 1 ? route_dgrad(a) : route_wgrad(a));
+  memset(info, 0, sizeof(*info));
+  info->kind = rt.mfma;
+  info->targ[0] = rt.t0; info->targ[1] = rt.t1;
+  info->grid = (int)(rt.grid < (1ll << 31) ? rt.grid : -1);      // (-1: the entry point refuses this grid)
+  info->block_threads = rt.block;
+  info->lds_bytes = (int)rt.lds;
+  info->reason = rt.reason;
+  info->circ = a.circ; info->fold = rt.fold;
+  if (rt.mfma) {
+    info->n_cb = pass == 2 ? 1 : a.n_cb; info->n_sg = pass == 2 ? 1 : a.n_sg; info->n_cg = a.n_cg;
+    info->n_mg = pass == 2 ? a.n_mg : 1; info->samples = pass == 2 ? 1 : a.S;
+  }
+  return DLWP_OK;
 }
 
 int dlwp_rowconv2d_bwd_workspace(dlwp_handle_t h, dlwp_shape4 xs, const dlwp_conv2d* cd, size_t* bytes) {
@@ -926,39 +1032,24 @@ int dlwp_rowconv2d_bwd_data(dlwp_handle_t h, const void* dz, const void* w, void
                  need, ws_bytes);
   RowArgs a = base_args(xs, cd, ys);
   a.dz = (const float*)dz; a.w = (const float*)w;
-  a.y = need ? (float*)ws : (float*)dx;
-  a.OH = a.Hp; a.OW = a.Wp;
-  // The call-site halo -- periodic columns that make the convolution circular (left + right = kw - 1: Wo == W), zero rows --
-  // needs no padded temporary and no folding pass: the gradient of a zero halo row is dropped, and the periodic images of a
-  // column are reached by letting dz wrap while it is staged (the fold was a third of this pass: 0.062 of 0.205 ms)
-  const dlwp_pad2d& hp = cd->halo;
-  const bool circ = need && hp.mode_w == DLWP_PAD_WRAP && hp.left + hp.right == cd->kw - 1 && hp.left + hp.right > 0 &&
-                    (hp.mode_h == DLWP_PAD_ZERO || hp.top + hp.bottom == 0) && ys.w == xs.w &&
-                    cd->kw - 1 <= xs.w;       // (dz wraps once while it is staged)
-  if (circ) {
-    a.circ = 1; a.OH = xs.h; a.OW = xs.w;
-    a.y = (float*)dx;
-  }
   hipStream_t s = (hipStream_t)stream;
-  const size_t lds = plan_dgrad(a);
-  if (lds == 0) {
-    a.circ = 0; a.OH = a.Hp; a.OW = a.Wp;
-    a.y = need ? (float*)ws : (float*)dx;
-    hipLaunchKernelGGL(rowconv2d_dgrad_simple, dim3(grid_1d((long long)a.N * a.Cin * a.Hp * a.Wp, 256)), dim3(256), 0, s, a);
+  const RowRoute rt = route_dgrad(a);      // (a.circ: the kernel writes dx itself, on the stored grid)
+  a.y = rt.fold ? (float*)ws : (float*)dx;
+  if (!rt.mfma) {
+    hipLaunchKernelGGL(rowconv2d_dgrad_simple, dim3((unsigned)rt.grid), dim3(rt.block), 0, s, a);
     DLWP_LAUNCH_CHECK("rowconv2d_dgrad_simple");
   } else {
-    const long long grid = (long long)a.OH * a.n_sg * a.n_cg * a.n_cb;
-    DLWP_CHECK_ARG(grid < (1ll << 31), "dlwp_rowconv2d_bwd_data: grid too large");
-    if (a.NF == 2) {
-      DLWP_HIP((hipError_t)set_lds(rowconv2d_dgrad_mfma<2>, lds));
-      hipLaunchKernelGGL(rowconv2d_dgrad_mfma<2>, dim3((unsigned)grid), dim3(128), lds, s, a);
+    DLWP_CHECK_ARG(rt.grid < (1ll << 31), "dlwp_rowconv2d_bwd_data: grid too large");
+    if (rt.t0 == 2) {
+      DLWP_HIP((hipError_t)set_lds(rowconv2d_dgrad_mfma<2>, rt.lds));
+      hipLaunchKernelGGL(rowconv2d_dgrad_mfma<2>, dim3((unsigned)rt.grid), dim3(rt.block), rt.lds, s, a);
     } else {
-      DLWP_HIP((hipError_t)set_lds(rowconv2d_dgrad_mfma<1>, lds));
-      hipLaunchKernelGGL(rowconv2d_dgrad_mfma<1>, dim3((unsigned)grid), dim3(128), lds, s, a);
+      DLWP_HIP((hipError_t)set_lds(rowconv2d_dgrad_mfma<1>, rt.lds));
+      hipLaunchKernelGGL(rowconv2d_dgrad_mfma<1>, dim3((unsigned)rt.grid), dim3(rt.block), rt.lds, s, a);
     }
     DLWP_LAUNCH_CHECK("rowconv2d_dgrad_mfma");
   }
-  if (need && !a.circ) return dlwp_pad2d_bwd(h, ws, dx, xs.n * xs.c, xs.h, xs.w, 1, cd->halo, DLWP_F32, stream);
+  if (rt.fold) return dlwp_pad2d_bwd(h, ws, dx, xs.n * xs.c, xs.h, xs.w, 1, cd->halo, DLWP_F32, stream);
   return DLWP_OK;
 }
 
@@ -972,27 +1063,27 @@ int dlwp_rowconv2d_bwd_weight(dlwp_handle_t h, const void* x, const void* dz, vo
   a.x = (const float*)x; a.dz = (const float*)dz; a.y = (float*)dw; a.db = (float*)db;
   a.accumulate = accumulate ? 1 : 0;
   hipStream_t s = (hipStream_t)stream;
-  const size_t lds = xs.n > 0 ? plan_wgrad(a) : 0;
-  if (lds == 0) {
-    hipLaunchKernelGGL(rowconv2d_wgrad_simple, dim3(grid_1d((long long)a.Ho * a.kh * a.kw * a.Cin * a.Cout, 256)), dim3(256),
-                       0, s, a);
+  const RowRoute rt = route_wgrad(a);
+  if (!rt.mfma) {
+    hipLaunchKernelGGL(rowconv2d_wgrad_simple, dim3((unsigned)rt.grid), dim3(rt.block), 0, s, a);
     DLWP_LAUNCH_CHECK("rowconv2d_wgrad_simple");
   } else {
-    const long long grid = (long long)a.Ho * a.kh * a.n_cg * a.n_mg;
-    DLWP_CHECK_ARG(grid < (1ll << 31), "dlwp_rowconv2d_bwd_weight: grid too large");
-    const int slots = dlwp_ceil_div(a.TW_in, 64);
+    DLWP_CHECK_ARG(rt.grid < (1ll << 31), "dlwp_rowconv2d_bwd_weight: grid too large");
     auto launch = [&](auto kernel) -> int {
-      DLWP_HIP((hipError_t)set_lds(kernel, lds));
-      hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(256), lds, s, a);
+      DLWP_HIP((hipError_t)set_lds(kernel, rt.lds));
+      hipLaunchKernelGGL(kernel, dim3((unsigned)rt.grid), dim3(rt.block), rt.lds, s, a);
       DLWP_LAUNCH_CHECK("rowconv2d_wgrad_mfma");
       return DLWP_OK;
     };
-    const int xr = a.Cin <= 16 ? 4 : (a.Cin <= 32 ? 8 : 0);     // channel rows per wave and sample held in registers
     int rc;
-    if (slots <= 3)
-      rc = xr == 4 ? launch(rowconv2d_wgrad_mfma<3, 4>) : (xr == 8 ? launch(rowconv2d_wgrad_mfma<3, 8>) : launch(rowconv2d_wgrad_mfma<3, 0>));
-    else
-      rc = xr == 4 ? launch(rowconv2d_wgrad_mfma<kMaxSlots, 4>) : launch(rowconv2d_wgrad_mfma<kMaxSlots, 0>);
+    switch (rt.t0 * 10 + rt.t1) {
+      case 34: rc = launch(rowconv2d_wgrad_mfma<3, 4>); break;
+      case 38: rc = launch(rowconv2d_wgrad_mfma<3, 8>); break;
+      case 30: rc = launch(rowconv2d_wgrad_mfma<3, 0>); break;
+      case kMaxSlots * 10 + 4: rc = launch(rowconv2d_wgrad_mfma<kMaxSlots, 4>); break;
+      case kMaxSlots * 10 + 0: rc = launch(rowconv2d_wgrad_mfma<kMaxSlots, 0>); break;
+      default: DLWP_FAIL(DLWP_EUNSUPPORTED, "dlwp_rowconv2d_bwd_weight: no rowconv2d_wgrad_mfma<%d, %d> instance", rt.t0, rt.t1);
+    }
     if (rc) return rc;
   }
   if (db) {

@@ -1122,6 +1122,21 @@ def rowconv2d_uses_matrix_cores(xs_nchw, cd, which=0):
                                                           ctypes.byref(cd), int(which)))
 
 
+ROWCONV_REASONS = ('', 'kernel height', 'staged width', 'LDS footprint', '32-bit offsets', 'empty batch')
+
+
+def rowconv2d_launch_info(xs_nchw, cd, which=0):
+    """Host logic (no GPU needed): what pass `which` (0 forward, 1 data gradient, 2 weight gradient) of this geometry launches
+    (dlwp_rowconv2d_launch_info) -> dict(kind 'mfma' | 'simple', targ (template arguments of the matrix-core instance), grid,
+    block, lds, circ, fold, reason (of the vector fall-back, ROWCONV_REASONS), n_cb, n_sg, n_cg, n_mg, samples)."""
+    info = _lib.RowconvLaunchInfo()
+    _lib.check(_lib.lib.dlwp_rowconv2d_launch_info(_lib.handle_or_none(), Shape4(*[int(v) for v in xs_nchw]), ctypes.byref(cd),
+                                                   int(which), ctypes.byref(info)))
+    return dict(kind='mfma' if info.kind else 'simple', targ=(info.targ[0], info.targ[1]), grid=info.grid, block=info.block_threads,
+                lds=info.lds_bytes, circ=bool(info.circ), fold=bool(info.fold), reason=ROWCONV_REASONS[info.reason], n_cb=info.n_cb,
+                n_sg=info.n_sg, n_cg=info.n_cg, n_mg=info.n_mg, samples=info.samples)
+
+
 def rowconv2d_bwd_data(dz, kernel, cd, xs, dx):
     """dx: dense (n, cin, h, w) <- dL/dx of the row-connected layer (halo adjoint included)."""
     _check_f32(dz, kernel, dx)

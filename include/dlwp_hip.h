@@ -342,6 +342,24 @@ int dlwp_rowconv2d_fwd(dlwp_handle_t, const void* x, const void* w, const void* 
 int dlwp_rowconv2d_fwd_direct(dlwp_handle_t, const void* x, const void* w, const void* bias, void* y, dlwp_shape4 xs,
                               const dlwp_conv2d* cd, int dtype, void* stream);
 int dlwp_rowconv2d_uses_matrix_cores(dlwp_handle_t, dlwp_shape4 xs, const dlwp_conv2d* cd, int pass);
+/* What pass 0 = forward | 1 = data | 2 = weight gradient of this geometry launches (host logic, no stream; the handle may be
+ * NULL).  The three entry points above take their launch from the same decision, so this is what runs.  The bias gradient
+ * (rowconv2d_bias_grad, cout x ho workgroups behind the weight gradient when db is given) is not part of the report.       */
+typedef struct {
+  int kind;                 /* 1: the matrix-core kernel instance <targ[0], targ[1]>; 0: the one-thread-per-output vector kernel */
+  int targ[2];              /* forward: rowconv2d_fwd_mfma<NSLOT, C4N>; data gradient: rowconv2d_dgrad_mfma<NF> (targ[1] = 0);
+                             * weight gradient: rowconv2d_wgrad_mfma<NSLOT, XR>; 0, 0 for the vector kernels                  */
+  int grid, block_threads, lds_bytes;   /* grid 0: nothing is launched (forward / data gradient of an empty batch)           */
+  int circ;                 /* data gradient: 1 when the periodic column halo is resolved while dz is staged (dx written directly) */
+  int fold;                 /* data gradient: 1 when the kernel writes the padded temporary and dlwp_pad2d_bwd follows          */
+  int reason;               /* kind 0: 1 kernel taller than the unrolled 5 rows, 2 staged row too wide, 3 LDS footprint, 4 tensor
+                             * beyond 32-bit descriptor offsets, 5 empty batch; kind 1: 0                                      */
+  int n_cb, n_sg, n_cg, n_mg;   /* kind 1, the grid's factors: column blocks, sample groups, 16-channel groups (cout; data
+                                 * gradient: cin fragments / NF), weight gradient M groups of (kx, ci) fragments -- 1 where the
+                                 * pass has no such factor (grid = rows x their product; weight gradient: rows x kh x ...)  */
+  int samples;              /* kind 1, forward / data gradient: samples per workgroup (S)                                   */
+} dlwp_rowconv_launch_info;
+int dlwp_rowconv2d_launch_info(dlwp_handle_t, dlwp_shape4 xs, const dlwp_conv2d* cd, int pass, dlwp_rowconv_launch_info* info);
 int dlwp_rowconv2d_bwd_workspace(dlwp_handle_t, dlwp_shape4 xs, const dlwp_conv2d* cd, size_t* bytes);
 int dlwp_rowconv2d_bwd_data(dlwp_handle_t, const void* dz, const void* w, void* dx, dlwp_shape4 xs, const dlwp_conv2d* cd,
                             int dtype, void* ws, size_t ws_bytes, void* stream);
