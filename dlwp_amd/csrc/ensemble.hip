@@ -15,32 +15,19 @@
 // key of every run stays in its head register, which keeps M = 256 at 8 x 31 x 256 B + the histogram below 64 KB of static LDS.
 //
 // Conventions of verify.hip: 64-bit offsets, entry points that never synchronise and read no size from the device, two-stage sums
-// on a fixed tree (lanes, one partial per block, a second kernel over a cell's partials in index order), no global atomics and no
-// "last block" scheme.  The histogram uses integer LDS atomics inside a block (integer adds commute) and the same second kernel:
+// on the fixed tree of verify_common.h (a block is one wave here, so the block stage is the lane tree alone), no global atomics and
+// no "last block" scheme.  The histogram uses integer LDS atomics inside a block (integer adds commute) and the same second kernel:
 // repeated launches give identical bits.
-#include "common.h"
+#include "verify_common.h"
 
 #include <climits>
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
 constexpr int ENS_THREADS = 256;           // mean / spread and the final kernel
 constexpr int ENS_RUN = 32;                // members a lane sorts in registers
 constexpr int ENS_MAX_MEMBERS = 256;       // 8 runs
-constexpr int ENS_DEFAULT_CU = 256;        // dlwp_ens_score_workspace without a handle: an MI355X
 constexpr int ENS_LDS_PER_CU = 160 * 1024;
-
-// the lane tree of verify.hip (kept there unchanged; four lines are not worth a header both files depend on)
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-
-inline bool mult4(long long v) { return (v & 3) == 0; }
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // ---- mean and spread fields --------------------------------------------------------------------------------------------------------- //
 struct MomentArgs {
@@ -277,8 +264,8 @@ __global__ __launch_bounds__(64) void ens_score_kernel(ScoreArgs p, double* __re
   for (int b = lane; b <= M; b += 64) oh[b] = hist[b];
 }
 
-// stage 2: one block per cell.  Wave 0: lane l sums partials l, l + 64, ... of its cell in index order, then the lane tree; every
-// thread adds the partial histograms of its bins in index order.
+// stage 2: one block per cell.  Wave 0 is the cell stage of verify_common.h; every thread adds the partial histograms of its bins
+// in index order.
 __global__ __launch_bounds__(ENS_THREADS) void ens_score_final_kernel(const double* __restrict__ psums,
                                                                       const unsigned long long* __restrict__ phist, int bpc,
                                                                       int members, double* __restrict__ sums,
@@ -291,18 +278,7 @@ __global__ __launch_bounds__(ENS_THREADS) void ens_score_final_kernel(const doub
     for (int i = 0; i < bpc; ++i) acc += src[(long long)i * bins];
     hist[cell * bins + b] = (long long)acc;
   }
-  if (threadIdx.x < 64) {
-    double a[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    const double* src = psums + 6ll * cell * bpc;
-    for (int i = threadIdx.x; i < bpc; i += 64)
-#pragma unroll
-      for (int k = 0; k < 6; ++k) a[k] += src[6 * i + k];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) a[k] = wave_sum_f64(a[k]);
-    if (threadIdx.x == 0)
-#pragma unroll
-      for (int k = 0; k < 6; ++k) sums[6 * cell + k] = a[k];
-  }
+  if (threadIdx.x < 64) cell_final<6>(psums, bpc, cell, true, threadIdx.x, sums);
 }
 
 inline int ens_runs(int members) { return (members + ENS_RUN - 1) / ENS_RUN; }
@@ -315,12 +291,6 @@ inline int ens_blocks_per_cu(int members) {
   if (members <= ENS_RUN) return 12;
   const int by_lds = ENS_LDS_PER_CU / ens_lds_bytes(ens_runs(members));
   return by_lds < 12 ? by_lds : 12;
-}
-
-// blocks per cell the handle's CU count allows for this many cells (rounded down, at least 1)
-inline long long ens_bpc_cap(dlwp_handle_t h, long long cells, int members) {
-  const long long want = (long long)(h ? h->cu_count : ENS_DEFAULT_CU) * ens_blocks_per_cu(members) / cells;
-  return want < 1 ? 1 : want;
 }
 
 inline size_t ens_partial_bytes(int members) { return 6 * sizeof(double) + (size_t)(members + 1) * sizeof(unsigned long long); }
@@ -368,7 +338,7 @@ int dlwp_ens_mean_spread(dlwp_handle_t h, const void* x, int leads, int samples,
 size_t dlwp_ens_score_workspace(dlwp_handle_t h, int leads, int groups, int members) {
   if (leads < 1 || groups < 1 || members < 2 || members > ENS_MAX_MEMBERS) return 0;
   const long long cells = (long long)leads * groups;
-  return (size_t)cells * (size_t)ens_bpc_cap(h, cells, members) * ens_partial_bytes(members);
+  return (size_t)cells * (size_t)cell_bpc_cap(h, cells, ens_blocks_per_cu(members)) * ens_partial_bytes(members);
 }
 
 int dlwp_ens_score_sums(dlwp_handle_t h, const void* x, long long lead_stride, long long sample_stride, long long member_stride,
@@ -386,7 +356,7 @@ int dlwp_ens_score_sums(dlwp_handle_t h, const void* x, long long lead_stride, l
   const long long tiles_per_row = (run + 63) / 64;
   DLWP_CHECK_ARG(tiles_per_row < (1ll << 31) / samples, "dlwp_ens_score_sums: %d samples of %lld floats are too many tiles", samples, run);
   const long long tiles = (long long)samples * tiles_per_row;
-  const long long cap = ens_bpc_cap(h, cells, members);
+  const long long cap = cell_bpc_cap(h, cells, ens_blocks_per_cu(members));
   const int bpc = (int)(tiles < cap ? tiles : cap);
   const size_t ws_need = (size_t)cells * (size_t)bpc * ens_partial_bytes(members);
   DLWP_CHECK_ARG(ws_bytes >= ws_need, "dlwp_ens_score_sums: workspace too small (%zu < %zu)", ws_bytes, ws_need);

@@ -19,9 +19,7 @@
 // Conventions of ensemble.hip / verify.hip: 64-bit offsets, no synchronisation, no size read from the device, no global atomics and
 // no "last block" scheme.  Each block writes its partial table (32-bit: the host checks that a block counts fewer than 2^31
 // columns) to the workspace and a second kernel adds a cell's partials in index order: repeated calls give identical bits.
-#include "common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "verify_common.h"
 
 namespace {
 
@@ -32,10 +30,6 @@ constexpr int EV_TABLE_INTS = 10240;       // at most 40 KB of (dynamic) LDS for
 constexpr int EV_MAX_COPIES = 32;          // one replica per LDS bank
 constexpr int EV_MATCH_ROUNDS = 4;
 constexpr int EV_BLOCKS_PER_CU = 10;       // grid cap: twice the blocks a CU holds
-constexpr int EV_DEFAULT_CU = 256;         // dlwp_ens_event_workspace without a handle: an MI355X
-
-inline bool mult4(long long v) { return (v & 3) == 0; }
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 struct EventArgs {
   const float* x;
@@ -220,12 +214,6 @@ inline bool ev_sizes_ok(int leads, int groups, int members, int thresholds) {
   return leads >= 1 && groups >= 1 && members >= 2 && members <= EV_MAX_MEMBERS && thresholds >= 1 && thresholds <= EV_MAX_THRESHOLDS;
 }
 
-// blocks per cell the handle's CU count allows for this many cells (rounded down, at least 1)
-inline long long ev_bpc_cap(dlwp_handle_t h, long long cells) {
-  const long long want = (long long)(h ? h->cu_count : EV_DEFAULT_CU) * EV_BLOCKS_PER_CU / cells;
-  return want < 1 ? 1 : want;
-}
-
 inline size_t ev_partial_bytes(int members, int thresholds) { return (size_t)thresholds * (members + 1) * 2 * sizeof(unsigned); }
 
 inline size_t ev_lds_bytes(const EventArgs& p) {
@@ -263,7 +251,7 @@ extern "C" {
 size_t dlwp_ens_event_workspace(dlwp_handle_t h, int leads, int groups, int members, int thresholds) {
   if (!ev_sizes_ok(leads, groups, members, thresholds)) return 0;
   const long long cells = (long long)leads * groups;
-  return (size_t)cells * (size_t)ev_bpc_cap(h, cells) * ev_partial_bytes(members, thresholds);
+  return (size_t)cells * (size_t)cell_bpc_cap(h, cells, EV_BLOCKS_PER_CU) * ev_partial_bytes(members, thresholds);
 }
 
 int dlwp_ens_event_counts(dlwp_handle_t h, const void* x, long long lead_stride, long long sample_stride, long long member_stride,
@@ -291,7 +279,7 @@ int dlwp_ens_event_counts(dlwp_handle_t h, const void* x, long long lead_stride,
   DLWP_CHECK_ARG(tiles_per_row < (1ll << 31) / samples, "dlwp_ens_event_counts: %d samples of %lld floats are too many tiles", samples,
                  run);
   const long long tiles = (long long)samples * tiles_per_row;
-  const long long cap = ev_bpc_cap(h, cells);
+  const long long cap = cell_bpc_cap(h, cells, EV_BLOCKS_PER_CU);
   const int bpc = (int)(tiles < cap ? tiles : cap);
   // the partial tables are 32-bit: a block counts (tiles / bpc rounded up) * tile_points columns at most
   DLWP_CHECK_ARG((tiles + bpc - 1) / bpc < (1ll << 31) / tile_points,

@@ -9,13 +9,10 @@
 //   series_merge_time  the final reshape/transpose of predict_timeseries (DLWP/model/models.py:294-300)
 //
 // All of these move each byte once: algorithmic bytes = bytes(in) + bytes(out); roofline = HBM.
-#include "common.h"
+#include "verify_common.h"      // f32x4, aligned16
 #include "tape.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-static inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
 static inline int grid_for(long long work_items, int block, int cu_count) {
   long long want = (work_items + block - 1) / block;

@@ -17,7 +17,7 @@
 // inside the wave, so the selection needs no barrier and no LDS besides the keys.
 // Counts are integers: the result does not depend on scheduling, there are no atomics and no float64 sums.  The interpolation of
 // 'linear' is three float64 operations, each rounded once (contraction into an fma is switched off), and one rounding to float32.
-#include "common.h"
+#include "verify_common.h"      // mult4, aligned16
 
 #include <cmath>
 
@@ -344,7 +344,7 @@ int dlwp_verify_label_quantiles(dlwp_handle_t h, const void* x, int count, long 
                  QUANT_LDS_BYTES / (16 * 4), QUANT_LDS_BYTES, max_len);
   const size_t ws_need = quant_ws_bytes(row, n_labels);
   DLWP_CHECK_ARG(ws_bytes >= ws_need, "dlwp_verify_label_quantiles: workspace too small (%zu < %zu)", ws_bytes, ws_need);
-  DLWP_CHECK_ARG(((uintptr_t)ws & 15) == 0, "dlwp_verify_label_quantiles: workspace must be 16-byte aligned");
+  DLWP_CHECK_ARG(aligned16(ws), "dlwp_verify_label_quantiles: workspace must be 16-byte aligned");
   DLWP_CHECK_ARG(h, "dlwp_verify_label_quantiles: null handle");
   QuantArgs p;
   p.x = (const unsigned*)x;
@@ -355,7 +355,7 @@ int dlwp_verify_label_quantiles(dlwp_handle_t h, const void* x, int count, long 
   p.count = count, p.n_labels = n_labels, p.k = k, p.method = method;
   p.tiles = (int)((row + cols - 1) / cols);
   p.len_pad = lds ? quant_round_up(max_len, QUANT_THREADS / cols) : 0;
-  p.vec = (row & 3) == 0 && ((uintptr_t)x & 15) == 0;
+  p.vec = mult4(row) && aligned16(x);
   for (int i = 0; i < QUANT_MAX_K; ++i) p.q[i] = i < k ? q[i] : 0.0;
   for (int l = 0; l <= QUANT_MAX_LABELS; ++l) p.off[l] = offsets[l < n_labels ? l : n_labels];
   const int ranks = method == DLWP_QUANTILE_LINEAR ? 2 * k : k;

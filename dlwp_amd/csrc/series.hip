@@ -14,7 +14,7 @@
 // stores, and walks the (sample, chunk) list with the stride of the grid.  Everything that selects the segment is the same in
 // every lane of a block: the chunk index comes from blockIdx, the segment from one ballot over the chunk prefix, its
 // descriptors from the kernel arguments.  No atomics, no LDS, no synchronisation, 64-bit offsets.
-#include "common.h"
+#include "verify_common.h"      // mult4, aligned16
 
 #include <type_traits>
 
@@ -92,8 +92,6 @@ __global__ __launch_bounds__(SERIES_THREADS) void series_window_gather_kernel(co
   }
 }
 
-inline bool mult4(long long v) { return (v & 3) == 0; }
-inline bool aligned16(const void* q) { return ((uintptr_t)q & 15) == 0; }
 constexpr long long SERIES_MAX_FLOATS = 0x7fffffffffffffffll / 4;
 
 }  // namespace

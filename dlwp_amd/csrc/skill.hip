@@ -5,18 +5,14 @@
 // include/dlwp_hip.h) and adds what that kernel has no place for: a climatology c looked up per pair of sample rows in a table of at
 // most 64 rows (the month-aware table of dlwp_verify_label_nanmean), a weight per latitude row, and the cross products.  Per pair
 // d = fc - ob, fa = fc - c, oa = ob - c are rounded once in float32, as numpy rounds float32 operands; a pair with a NaN among them
-// is skipped in every sum, the count included; everything behind that is float64.  The tree is verify.hip's: per-thread sums, lanes,
-// waves through LDS, one partial of ten doubles per block in ws, a second kernel that adds the partials of a cell in index order -- no
-// atomics, no "last block" scheme, no size read from the device, no synchronisation: repeated calls give identical bits.
-#include "common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+// is skipped in every sum, the count included; everything behind that is float64.  The tree is verify_common.h's with one partial of
+// ten doubles per block in ws: no size read from the device, no synchronisation, repeated calls give identical bits.
+#include "verify_common.h"
 
 namespace {
 
 constexpr int SKILL_THREADS = 256;
 constexpr int SKILL_BLOCKS_PER_CU = 8;
-constexpr int SKILL_DEFAULT_CU = 256;     // dlwp_verify_skill_workspace without a handle: an MI355X
 constexpr int SKILL_SUMS = 10;
 constexpr int SKILL_MAX_LABELS = 64;
 
@@ -25,14 +21,12 @@ constexpr int SKILL_MAX_LABELS = 64;
 enum { W_NONE = 0, W_UNIT = 1, W_ELEM = 2 };
 
 struct SkillArgs {
-  const float* fc;
-  const float* ob;
+  Window fc, ob;
   const float* climo;                    // (n_labels, groups * run) or null
   const int* labels;                     // may be null: label 0
   const float* weights;                  // w_len floats or null
-  long long fc_ls, fc_ss, ob_ls, ob_ss;  // lead / sample strides in elements
   long long lab_ls;
-  int fc_shift, ob_shift, lab_shift;
+  int lab_shift;
   int count0, count_dec;
   int groups, bpc;                       // blocks per (lead, group) cell
   int n_labels, w_len;
@@ -42,12 +36,6 @@ struct SkillArgs {
   long long step_wcol;                   // the same step inside the weight period w_len x w_inner, as (latitude rows, columns)
   int step_wrow;
 };
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
 
 struct SkillAcc {
   double s[SKILL_SUMS - 1];              // S0 .. S8
@@ -114,37 +102,38 @@ __device__ __forceinline__ void unit_weights(const SkillArgs& p, int wrow, long 
 // wrow < w_len; run is a multiple of the period, so the carry from col into row does not touch it, and the host's (step_wrow,
 // step_wcol) advances it with two carries and no division.  The label of the NEXT unit is fetched while this one's data are in
 // flight (the table address needs it), so no load waits for another.  Eight waves per SIMD (64 registers) keep the launch's eight
-// blocks per CU resident.
+// blocks per CU resident.  The walk is this kernel's own and not verify_common.h's UnitWalk: its row is unsigned and clamped to cnt
+// (the loop's only test) and the operand offsets are carried beside it; on UnitWalk the weighted 16-byte instances spill at 64.
 template <bool VEC, int WMODE, bool CLIMO>
 __global__ __launch_bounds__(SKILL_THREADS, SKILL_BLOCKS_PER_CU) void skill_partial_kernel(SkillArgs p, double* __restrict__ partial) {
   constexpr int W = VEC ? 4 : 1;
   const unsigned cell = blockIdx.x / (unsigned)p.bpc;
   const unsigned blk = blockIdx.x - cell * (unsigned)p.bpc;
   const unsigned f = cell / (unsigned)p.groups, g = cell - f * (unsigned)p.groups;
-  const unsigned cnt = (unsigned)((long long)p.count0 - (long long)f * p.count_dec);     // > 0: the host launches active leads only
+  const unsigned cnt = (unsigned)window_pairs(p.count0, p.count_dec, f);      // > 0: the host launches active leads only
   const long long units = p.run / W;
   const unsigned step_row = (unsigned)p.step_row;     // <= bpc * 256 <= 8 CUs * 256
-  const float* pf = p.fc + (long long)f * p.fc_ls + (long long)f * p.fc_shift * p.fc_ss + (long long)g * p.run;
-  const float* po = p.ob + (long long)f * p.ob_ls + (long long)f * p.ob_shift * p.ob_ss + (long long)g * p.run;
+  const float* pf = p.fc.lead(f, g, p.run);
+  const float* po = p.ob.lead(f, g, p.run);
   const float* pc = CLIMO ? p.climo + (long long)g * p.run : nullptr;
   const int* pl = CLIMO && p.labels ? p.labels + (long long)f * p.lab_ls + (long long)f * p.lab_shift : nullptr;
   const long long trow = (long long)p.groups * p.run;
   // a step moves an operand by step_row rows and step_col units; a carry of col by one more row less a run
-  const long long f_step = (long long)step_row * p.fc_ss + W * p.step_col, f_carry = p.fc_ss - p.run;
-  const long long o_step = (long long)step_row * p.ob_ss + W * p.step_col, o_carry = p.ob_ss - p.run;
+  const long long f_step = (long long)step_row * p.fc.ss + W * p.step_col, f_carry = p.fc.ss - p.run;
+  const long long o_step = (long long)step_row * p.ob.ss + W * p.step_col, o_carry = p.ob.ss - p.run;
   const float qnan = __builtin_nanf("");
   SkillAcc acc;
 #pragma unroll
   for (int k = 0; k < SKILL_SUMS - 1; ++k) acc.s[k] = 0.0;
   acc.n = 0;
   // the wave's number lives in a scalar register and the lane is recomputed behind the loop: no thread index is kept across it
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int wave = wave_number();
   const long long q = (long long)blk * SKILL_THREADS + threadIdx.x;
   const long long row0 = q / units;
   long long col = q - row0 * units;
   // row < cnt <=> the unit exists (col < units always); unsigned: row + step_row + 1 < 2^31 + 8 CUs * 256 does not wrap
   unsigned row = row0 < cnt ? (unsigned)row0 : cnt;
-  long long f_at = row0 * p.fc_ss + W * col, o_at = row0 * p.ob_ss + W * col;
+  long long f_at = row0 * p.fc.ss + W * col, o_at = row0 * p.ob.ss + W * col;
   long long wcol = 0;
   int wrow = 0;
   if (WMODE != W_NONE) {
@@ -205,55 +194,8 @@ __global__ __launch_bounds__(SKILL_THREADS, SKILL_BLOCKS_PER_CU) void skill_part
   v[0] = WMODE == W_NONE ? v[SKILL_SUMS - 1] : acc.s[0];
 #pragma unroll
   for (int k = 1; k < SKILL_SUMS - 1; ++k) v[k] = acc.s[k];
-  // block-wide sums, valid in thread 0: 64 lanes, then the four waves in wave order
-  __shared__ double sm[SKILL_SUMS][SKILL_THREADS / 64];
-  const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-#pragma unroll
-  for (int k = 0; k < SKILL_SUMS; ++k) {
-    v[k] = wave_sum_f64(v[k]);
-    if (lane == 0) sm[k][wave] = v[k];
-  }
-  __syncthreads();
-  if (wave == 0 && lane < SKILL_SUMS) {
-    const int k = lane;
-    partial[(long long)SKILL_SUMS * blockIdx.x + k] = ((sm[k][0] + sm[k][1]) + sm[k][2]) + sm[k][3];
-  }
+  block_sums<SKILL_SUMS>(v, wave, partial + (long long)SKILL_SUMS * blockIdx.x);
 }
-
-// stage 2: one wave per cell.  Lane l sums partials l, l + 64, ... of its cell in index order, then the lane tree.  Cells of leads
-// without pairs (cell >= active_cells) read nothing and store zeros.
-__global__ __launch_bounds__(64) void skill_final_kernel(const double* __restrict__ partial, int bpc, int active_cells,
-                                                         double* __restrict__ sums) {
-  const int cell = blockIdx.x;
-  double v[SKILL_SUMS];
-#pragma unroll
-  for (int k = 0; k < SKILL_SUMS; ++k) v[k] = 0.0;
-  if (cell < active_cells) {
-    const double* src = partial + (long long)SKILL_SUMS * cell * bpc;
-    for (int i = threadIdx.x; i < bpc; i += 64) {
-#pragma unroll
-      for (int k = 0; k < SKILL_SUMS; ++k) v[k] += src[(long long)SKILL_SUMS * i + k];
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < SKILL_SUMS; ++k) v[k] = wave_sum_f64(v[k]);
-  if (threadIdx.x == 0) {
-    double* o = sums + (long long)SKILL_SUMS * cell;
-#pragma unroll
-    for (int k = 0; k < SKILL_SUMS; ++k) o[k] = v[k];
-  }
-}
-
-inline int skill_cu(dlwp_handle_t h) { return h ? h->cu_count : SKILL_DEFAULT_CU; }
-
-// blocks per cell the handle's CU count allows for this many cells: the whole launch aims at 8 blocks per CU
-inline int skill_bpc_cap(dlwp_handle_t h, long long cells) {
-  const long long want = (long long)skill_cu(h) * SKILL_BLOCKS_PER_CU / (cells > 0 ? cells : 1);
-  return (int)(want < 1 ? 1 : want);
-}
-
-inline bool mult4(long long v) { return (v & 3) == 0; }
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 template <bool VEC, int WMODE>
 void skill_launch(const SkillArgs& p, unsigned grid, double* ws, hipStream_t s) {
@@ -269,10 +211,7 @@ extern "C" {
 
 size_t dlwp_verify_skill_workspace(dlwp_handle_t h, int leads, int groups) {
   if (leads < 1 || groups < 1) return 0;
-  const long long cells = (long long)leads * groups;
-  // B rounded UP: cells * B covers 8 blocks per CU, which is what a launch over fewer (active) leads may spread over its cells
-  const long long per_cell = ((long long)skill_cu(h) * SKILL_BLOCKS_PER_CU + cells - 1) / cells;
-  return (size_t)cells * (size_t)per_cell * SKILL_SUMS * sizeof(double);
+  return cell_workspace_bytes(h, (long long)leads * groups, SKILL_BLOCKS_PER_CU, SKILL_SUMS * sizeof(double));
 }
 
 int dlwp_verify_skill_sums(dlwp_handle_t h, const void* fc, long long fc_lead_stride, long long fc_sample_stride, int fc_shift,
@@ -283,8 +222,10 @@ int dlwp_verify_skill_sums(dlwp_handle_t h, const void* fc, long long fc_lead_st
   DLWP_UNTAPED(dlwp_verify_skill_sums);
   DLWP_CHECK_ARG(leads >= 1 && groups >= 1 && run >= 1, "dlwp_verify_skill_sums: leads %d, groups %d, run %lld must all be >= 1",
                  leads, groups, run);
-  DLWP_CHECK_ARG(count_dec >= 0 && fc_shift >= 0 && ob_shift >= 0 && fc_lead_stride >= 0 && fc_sample_stride >= 0 &&
-                     ob_lead_stride >= 0 && ob_sample_stride >= 0 && label_lead_stride >= 0 && label_shift >= 0,
+  SkillArgs p;
+  p.fc = window_of(fc, fc_lead_stride, fc_sample_stride, fc_shift);
+  p.ob = window_of(ob, ob_lead_stride, ob_sample_stride, ob_shift);
+  DLWP_CHECK_ARG(count_dec >= 0 && window_nonneg(p.fc) && window_nonneg(p.ob) && label_lead_stride >= 0 && label_shift >= 0,
                  "dlwp_verify_skill_sums: negative stride, shift or count_dec");
   DLWP_CHECK_ARG(!climo || (n_labels >= 1 && n_labels <= SKILL_MAX_LABELS), "dlwp_verify_skill_sums: n_labels %d, expected 1 .. %d",
                  n_labels, SKILL_MAX_LABELS);
@@ -293,33 +234,26 @@ int dlwp_verify_skill_sums(dlwp_handle_t h, const void* fc, long long fc_lead_st
                  "dlwp_verify_skill_sums: %d weights of %lld elements each do not divide a run of %lld", w_len, w_inner, run);
   DLWP_CHECK_ARG(fc && ob && sums, "dlwp_verify_skill_sums: null pointer");
   const long long cells = (long long)leads * groups;
+  // inherited: at most 2^20 cells here and in spectrum.hip, fewer than 2^20 in verify.hip
   DLWP_CHECK_ARG(cells <= (1ll << 20), "dlwp_verify_skill_sums: %lld (lead, group) cells, at most 2^20", cells);
-  // leads with pairs: count0 - f * count_dec > 0
-  long long active = count0 <= 0 ? 0 : (count_dec == 0 ? leads : ((long long)count0 + count_dec - 1) / count_dec);
-  if (active > leads) active = leads;
-  const bool vec = mult4(run) && mult4(fc_lead_stride) && mult4(fc_sample_stride) && mult4(ob_lead_stride) &&
-                   mult4(ob_sample_stride) && aligned16(fc) && aligned16(ob) && aligned16(climo);
+  const long long active = window_active_leads(leads, count0, count_dec);
+  const bool vec = mult4(run) && window_vec(p.fc) && window_vec(p.ob) && aligned16(climo);
   const long long units = vec ? run / 4 : run;
-  int bpc = 0;
-  if (active > 0) {
-    // no more blocks in a cell than lead 0 (the longest) has 256-unit slices
-    const long long need = ((long long)count0 * units + SKILL_THREADS - 1) / SKILL_THREADS;
-    const long long cap = skill_bpc_cap(h, active * groups);
-    bpc = (int)(need < cap ? need : cap);
-  }
+  // no more blocks in a cell than lead 0 (the longest) has 256-unit slices
+  const int bpc = cell_plan_bpc(h, active, groups, ((long long)count0 * units + SKILL_THREADS - 1) / SKILL_THREADS,
+                                SKILL_BLOCKS_PER_CU);
   const size_t ws_need = (size_t)active * groups * bpc * SKILL_SUMS * sizeof(double);
+  // inherited: a null workspace is accepted where no partial is written (verify.hip wants one regardless)
   DLWP_CHECK_ARG(ws_bytes >= ws_need && (ws || ws_need == 0), "dlwp_verify_skill_sums: workspace too small (%zu < %zu)", ws_bytes,
                  ws_need);
   DLWP_CHECK_ARG(((uintptr_t)ws & 7) == 0, "dlwp_verify_skill_sums: workspace must be 8-byte aligned");
   DLWP_CHECK_ARG(h, "dlwp_verify_skill_sums: null handle");
   hipStream_t s = (hipStream_t)stream;
   if (active > 0) {
-    SkillArgs p;
-    p.fc = (const float*)fc, p.ob = (const float*)ob, p.climo = (const float*)climo;
+    p.climo = (const float*)climo;
     p.labels = (const int*)labels, p.weights = (const float*)weights;
-    p.fc_ls = fc_lead_stride, p.fc_ss = fc_sample_stride, p.ob_ls = ob_lead_stride, p.ob_ss = ob_sample_stride;
     p.lab_ls = label_lead_stride;
-    p.fc_shift = fc_shift, p.ob_shift = ob_shift, p.lab_shift = label_shift;
+    p.lab_shift = label_shift;
     p.count0 = count0, p.count_dec = count_dec;
     p.groups = groups, p.bpc = bpc;
     p.n_labels = climo ? n_labels : 1;
@@ -346,7 +280,7 @@ int dlwp_verify_skill_sums(dlwp_handle_t h, const void* fc, long long fc_lead_st
       skill_launch<true, W_ELEM>(p, grid, part, s);
     }
   }
-  skill_final_kernel<<<(unsigned)cells, 64, 0, s>>>((const double*)ws, bpc, (int)(active * groups), (double*)sums);
+  cell_final_kernel<SKILL_SUMS><<<(unsigned)cells, 64, 0, s>>>((const double*)ws, bpc, (int)(active * groups), (double*)sums);
   DLWP_LAUNCH_CHECK("verify_skill_sums kernels");
   return DLWP_OK;
 }

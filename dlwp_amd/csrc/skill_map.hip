@@ -9,27 +9,22 @@
 // one lead and walks that lead's samples -- or one of `split` chunks of them -- in sample order with its sums in registers.  With one
 // chunk the same launch makes the scores; with several, the chunks' planes go to the workspace and a second launch adds them in chunk
 // order.  No atomics, no "last block" scheme, no size read from the device, no synchronisation: repeated calls give identical bits.
-#include "common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "verify_common.h"
 
 namespace {
 
 constexpr int MAP_THREADS = 256;
 constexpr int MAP_BLOCKS_PER_CU = 8;     // the split rule of dlwp_verify_label_nanmean: chunks until 8 blocks per CU exist
-constexpr int MAP_DEFAULT_CU = 256;      // without a handle: an MI355X
 constexpr int MAP_SUMS = 9;
 constexpr int MAP_SCORES = 6;
 constexpr int MAP_MAX_LABELS = 64;
 
 struct MapArgs {
-  const float* fc;
-  const float* ob;
+  Window fc, ob;
   const float* climo;                    // (n_labels, row) or null
   const int* labels;                     // may be null: label 0
-  long long fc_ls, fc_ss, ob_ls, ob_ss;  // lead / sample strides in elements
   long long lab_ls;
-  int fc_shift, ob_shift, lab_shift;
+  int lab_shift;
   int count0, count_dec;
   int n_labels, split, tiles;
   long long row;
@@ -142,11 +137,11 @@ __global__ __launch_bounds__(MAP_THREADS, 2) void skill_map_kernel(MapArgs p) {
   const unsigned f = cell / (unsigned)p.split, chunk = cell - f * (unsigned)p.split;
   const long long c = ((long long)tile * MAP_THREADS + threadIdx.x) * W;
   if (c >= p.row) return;
-  long long cnt = (long long)p.count0 - (long long)f * p.count_dec;
+  long long cnt = window_pairs(p.count0, p.count_dec, f);
   if (cnt < 0) cnt = 0;
   const long long lo = cnt * chunk / p.split, end = cnt * (chunk + 1) / p.split;
-  const float* pf = p.fc + (long long)f * p.fc_ls + (long long)f * p.fc_shift * p.fc_ss + c;
-  const float* po = p.ob + (long long)f * p.ob_ls + (long long)f * p.ob_shift * p.ob_ss + c;
+  const float* pf = p.fc.lead(f) + c;
+  const float* po = p.ob.lead(f) + c;
   const float* pc = CLIMO ? p.climo + c : nullptr;
   const int* pl = CLIMO && p.labels ? p.labels + (long long)f * p.lab_ls + (long long)f * p.lab_shift : nullptr;
   double s[MAP_SUMS - 1][W];
@@ -169,8 +164,8 @@ __global__ __launch_bounds__(MAP_THREADS, 2) void skill_map_kernel(MapArgs p) {
       const long long r = live ? i + u : end - 1;      // lo <= r < end: a row of this chunk
       const bool in = !CLIMO || (unsigned)label[u] < (unsigned)p.n_labels;      // a label out of range is never an address
       use[u] = live && in;
-      const float* qf = pf + r * p.fc_ss;
-      const float* qo = po + r * p.ob_ss;
+      const float* qf = pf + r * p.fc.ss;
+      const float* qo = po + r * p.ob.ss;
       const float* qc = CLIMO ? pc + (long long)(in ? label[u] : 0) * p.row : nullptr;
       if (VEC) {
         const f32x4 xv = *reinterpret_cast<const f32x4*>(qf);
@@ -245,9 +240,6 @@ __global__ __launch_bounds__(MAP_THREADS) void skill_map_final_kernel(const doub
   map_store<1>(v, f, row, c, sums, scores, counts);
 }
 
-inline int map_cu(dlwp_handle_t h) { return h ? h->cu_count : MAP_DEFAULT_CU; }
-inline bool mult4(long long v) { return (v & 3) == 0; }
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 inline long long map_tiles(long long row, bool vec) { return ((vec ? row / 4 : row) + MAP_THREADS - 1) / MAP_THREADS; }
 
 // chunks of the sample axis.  split = 0: only as many as leads x column tiles leave the chip unfilled; a positive split as given;
@@ -255,8 +247,7 @@ inline long long map_tiles(long long row, bool vec) { return ((vec ? row / 4 : r
 inline int map_split(dlwp_handle_t h, int leads, int count0, long long row, int split, bool vec) {
   long long want = split;
   if (split == 0) {
-    want = (long long)map_cu(h) * MAP_BLOCKS_PER_CU / ((long long)leads * map_tiles(row, vec));
-    if (want < 1) want = 1;
+    want = cell_bpc_cap(h, (long long)leads * map_tiles(row, vec), MAP_BLOCKS_PER_CU);
   }
   if (want > count0) want = count0;
   return (int)(want < 1 ? 1 : want);
@@ -288,16 +279,17 @@ int dlwp_verify_skill_map(dlwp_handle_t h, const void* fc, long long fc_lead_str
                           size_t ws_bytes, void* stream) {
   DLWP_UNTAPED(dlwp_verify_skill_map);
   DLWP_CHECK_ARG(leads >= 1 && row >= 1, "dlwp_verify_skill_map: leads %d and row %lld must be >= 1", leads, row);
-  DLWP_CHECK_ARG(count_dec >= 0 && fc_shift >= 0 && ob_shift >= 0 && fc_lead_stride >= 0 && fc_sample_stride >= 0 &&
-                     ob_lead_stride >= 0 && ob_sample_stride >= 0 && label_lead_stride >= 0 && label_shift >= 0,
+  MapArgs p;
+  p.fc = window_of(fc, fc_lead_stride, fc_sample_stride, fc_shift);
+  p.ob = window_of(ob, ob_lead_stride, ob_sample_stride, ob_shift);
+  DLWP_CHECK_ARG(count_dec >= 0 && window_nonneg(p.fc) && window_nonneg(p.ob) && label_lead_stride >= 0 && label_shift >= 0,
                  "dlwp_verify_skill_map: negative stride, shift or count_dec");
   DLWP_CHECK_ARG(!climo || (n_labels >= 1 && n_labels <= MAP_MAX_LABELS), "dlwp_verify_skill_map: n_labels %d, expected 1 .. %d",
                  n_labels, MAP_MAX_LABELS);
   DLWP_CHECK_ARG(climo || !labels, "dlwp_verify_skill_map: labels without a climatology table");
   DLWP_CHECK_ARG(fc && ob && (sums || scores || counts), "dlwp_verify_skill_map: null operand, or no output at all");
   DLWP_CHECK_ARG(split >= 0, "dlwp_verify_skill_map: split %d must be >= 0", split);
-  const bool vec = mult4(row) && mult4(fc_lead_stride) && mult4(fc_sample_stride) && mult4(ob_lead_stride) &&
-                   mult4(ob_sample_stride) && aligned16(fc) && aligned16(ob) && aligned16(climo);
+  const bool vec = mult4(row) && window_vec(p.fc) && window_vec(p.ob) && aligned16(climo);
   const int chunks = map_split(h, leads, count0, row, split, vec);
   const long long tiles = map_tiles(row, vec), ftiles = map_tiles(row, false);
   DLWP_CHECK_ARG((long long)leads * chunks * tiles < (1ll << 31) && (long long)leads * ftiles < (1ll << 31),
@@ -308,11 +300,9 @@ int dlwp_verify_skill_map(dlwp_handle_t h, const void* fc, long long fc_lead_str
   DLWP_CHECK_ARG(((uintptr_t)ws & 7) == 0, "dlwp_verify_skill_map: workspace must be 8-byte aligned");
   DLWP_CHECK_ARG(h, "dlwp_verify_skill_map: null handle");
   hipStream_t s = (hipStream_t)stream;
-  MapArgs p;
-  p.fc = (const float*)fc, p.ob = (const float*)ob, p.climo = (const float*)climo, p.labels = (const int*)labels;
-  p.fc_ls = fc_lead_stride, p.fc_ss = fc_sample_stride, p.ob_ls = ob_lead_stride, p.ob_ss = ob_sample_stride;
+  p.climo = (const float*)climo, p.labels = (const int*)labels;
   p.lab_ls = label_lead_stride;
-  p.fc_shift = fc_shift, p.ob_shift = ob_shift, p.lab_shift = label_shift;
+  p.lab_shift = label_shift;
   p.count0 = count0, p.count_dec = count_dec;
   p.n_labels = climo ? n_labels : 1, p.split = chunks, p.tiles = (int)tiles;
   p.row = row;

@@ -13,11 +13,11 @@
 // A wave owns 32-wavenumber tiles (mw, mw + nw, ...) of the block's 32 rows and keeps the four products (O cos, O sin, D cos,
 // D sin) of a tile in 64 accumulator registers; behind the product everything is float64 and stays in registers: re, im widened, the
 // four terms weighted and added over the lane's 16 rows into per-thread sums that live across the block's row tiles.  One partial
-// (4 K + 2 doubles) per block in ws; a second launch adds a cell's partials in index order.  No atomics, no synchronisation with the
-// host, identical bits on repeated calls.  A row with a non-finite fc, ob or d is zeroed in LDS and has weight 0 and no count.
-#include "common.h"
+// (4 K + 2 doubles) per block in ws; a second launch adds a cell's partials in index order (the window, the plan and the lane tree are
+// verify_common.h's; the partial's length varies with the width, so the cell stage is this file's own).  No atomics, no
+// synchronisation with the host, identical bits on repeated calls.  A row with a non-finite fc, ob or d is zeroed in LDS and has weight 0 and no count.
+#include "verify_common.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace {
@@ -26,32 +26,22 @@ constexpr int SPEC_ROWS = 32;             // longitude rows of a tile: M of the 
 constexpr int SPEC_MAX_WIDTH = 512;
 constexpr int SPEC_MIN_WIDTH = 4;
 constexpr int SPEC_BLOCKS_PER_CU = 8;
-constexpr int SPEC_DEFAULT_CU = 256;      // dlwp_verify_spectrum_workspace without a handle: an MI355X
 constexpr int SPEC_TPW = 3;               // wavenumber tiles a wave may own: ceil(9 / 3) at width 512
 constexpr int SPEC_FINAL_THREADS = 256;
 constexpr int SPEC_THREADS = 256;         // four waves stage a tile; nw of them own wavenumber tiles
 constexpr int SPEC_BATCH = 8;             // units a thread has in flight in stage 1
 
 struct SpecArgs {
-  const float* fc;
-  const float* ob;
+  Window fc, ob;
   const float* weights;                  // w_len floats or null
   const float* tw;                       // width cosines, then width sines
-  long long fc_ls, fc_ss, ob_ls, ob_ss;  // lead / sample strides in elements
   long long run;                         // floats of one group in one sample row
-  int fc_shift, ob_shift;
   int count0, count_dec;
   int groups, bpc;                       // blocks per (lead, group) cell
   int width, rpr;                        // W; longitude rows of a run
   int w_len;
   int K, pitch, nT, nw;                  // wavenumbers; floats of a row in LDS; 32-wavenumber tiles; waves that own tiles
 };
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
 
 // the LDS of a block: doubles in front
 struct SpecLds {
@@ -94,11 +84,11 @@ __global__ __launch_bounds__(SPEC_THREADS, 2) void spectrum_partial_kernel(SpecA
   const unsigned cell = blockIdx.x / (unsigned)p.bpc;
   const unsigned blk = blockIdx.x - cell * (unsigned)p.bpc;
   const unsigned f = cell / (unsigned)p.groups, g = cell - f * (unsigned)p.groups;
-  const unsigned cnt = (unsigned)((long long)p.count0 - (long long)f * p.count_dec);     // > 0: the host launches active leads only
+  const unsigned cnt = (unsigned)window_pairs(p.count0, p.count_dec, f);      // > 0: the host launches active leads only
   const unsigned rows_total = cnt * (unsigned)p.rpr;                                     // < 2^31: checked by the host
   const unsigned n_tiles = (rows_total + SPEC_ROWS - 1) / SPEC_ROWS;
-  const float* pf = p.fc + (long long)f * p.fc_ls + (long long)f * p.fc_shift * p.fc_ss + (long long)g * p.run;
-  const float* po = p.ob + (long long)f * p.ob_ls + (long long)f * p.ob_shift * p.ob_ss + (long long)g * p.run;
+  const float* pf = p.fc.lead(f, g, p.run);
+  const float* po = p.ob.lead(f, g, p.run);
 
   for (int i = t; i < 2 * W; i += T) L.tw[i] = p.tw[i];
 
@@ -122,8 +112,8 @@ __global__ __launch_bounds__(SPEC_THREADS, 2) void spectrum_partial_kernel(SpecA
       const bool valid = R < rows_total;
       const unsigned i = valid ? R / (unsigned)p.rpr : 0u;
       const unsigned r = valid ? R - i * (unsigned)p.rpr : 0u;
-      L.off_f[t] = (long long)i * p.fc_ss + (long long)r * W;
-      L.off_o[t] = (long long)i * p.ob_ss + (long long)r * W;
+      L.off_f[t] = (long long)i * p.fc.ss + (long long)r * W;
+      L.off_o[t] = (long long)i * p.ob.ss + (long long)r * W;
       L.okf[t] = valid ? 1 : 0;
       L.wl[t] = valid ? (p.weights ? (double)p.weights[r % (unsigned)p.w_len] : 1.0) : 0.0;
     }
@@ -308,20 +298,13 @@ __global__ __launch_bounds__(SPEC_FINAL_THREADS) void spectrum_final_kernel(cons
   }
 }
 
-inline int spec_cu(dlwp_handle_t h) { return h ? h->cu_count : SPEC_DEFAULT_CU; }
-inline bool mult4(long long v) { return (v & 3) == 0; }
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
 
 extern "C" {
 
 size_t dlwp_verify_spectrum_workspace(dlwp_handle_t h, int leads, int groups, int width) {
   if (leads < 1 || groups < 1 || width < SPEC_MIN_WIDTH || width > SPEC_MAX_WIDTH) return 0;
-  const long long cells = (long long)leads * groups;
-  // B rounded UP: cells * B covers 8 blocks per CU, which is what a launch over fewer (active) leads may spread over its cells
-  const long long per_cell = ((long long)spec_cu(h) * SPEC_BLOCKS_PER_CU + cells - 1) / cells;
-  return (size_t)cells * (size_t)per_cell * (size_t)(4 * (width / 2 + 1) + 2) * sizeof(double);
+  return cell_workspace_bytes(h, (long long)leads * groups, SPEC_BLOCKS_PER_CU, (size_t)(4 * (width / 2 + 1) + 2) * sizeof(double));
 }
 
 int dlwp_verify_spectrum_sums(dlwp_handle_t h, const void* fc, long long fc_lead_stride, long long fc_sample_stride, int fc_shift,
@@ -331,8 +314,10 @@ int dlwp_verify_spectrum_sums(dlwp_handle_t h, const void* fc, long long fc_lead
   DLWP_UNTAPED(dlwp_verify_spectrum_sums);
   DLWP_CHECK_ARG(leads >= 1 && groups >= 1 && run >= 1, "dlwp_verify_spectrum_sums: leads %d, groups %d, run %lld must all be >= 1",
                  leads, groups, run);
-  DLWP_CHECK_ARG(count_dec >= 0 && fc_shift >= 0 && ob_shift >= 0 && fc_lead_stride >= 0 && fc_sample_stride >= 0 &&
-                     ob_lead_stride >= 0 && ob_sample_stride >= 0,
+  SpecArgs p;
+  p.fc = window_of(fc, fc_lead_stride, fc_sample_stride, fc_shift);
+  p.ob = window_of(ob, ob_lead_stride, ob_sample_stride, ob_shift);
+  DLWP_CHECK_ARG(count_dec >= 0 && window_nonneg(p.fc) && window_nonneg(p.ob),
                  "dlwp_verify_spectrum_sums: negative stride, shift or count_dec");
   DLWP_CHECK_ARG(width >= SPEC_MIN_WIDTH && width <= SPEC_MAX_WIDTH && run % width == 0,
                  "dlwp_verify_spectrum_sums: width %d must lie in %d .. %d and divide a run of %lld", width, SPEC_MIN_WIDTH,
@@ -342,33 +327,24 @@ int dlwp_verify_spectrum_sums(dlwp_handle_t h, const void* fc, long long fc_lead
                  "dlwp_verify_spectrum_sums: %d weights do not divide the %lld longitude rows of a run", w_len, rpr);
   DLWP_CHECK_ARG(fc && ob && sums && norm && twiddles, "dlwp_verify_spectrum_sums: null pointer");
   const long long cells = (long long)leads * groups;
+  // inherited: at most 2^20 cells here and in skill.hip, fewer than 2^20 in verify.hip
   DLWP_CHECK_ARG(cells <= (1ll << 20), "dlwp_verify_spectrum_sums: %lld (lead, group) cells, at most 2^20", cells);
   DLWP_CHECK_ARG(count0 <= 0 || (long long)count0 * rpr < (1ll << 31) - SPEC_ROWS,
                  "dlwp_verify_spectrum_sums: %lld longitude rows in a cell, fewer than 2^31 expected", (long long)count0 * rpr);
-  // leads with pairs: count0 - f * count_dec > 0
-  long long active = count0 <= 0 ? 0 : (count_dec == 0 ? leads : ((long long)count0 + count_dec - 1) / count_dec);
-  if (active > leads) active = leads;
+  const long long active = window_active_leads(leads, count0, count_dec);
   const int K = width / 2 + 1;
-  int bpc = 0;
-  if (active > 0) {
-    // no more blocks in a cell than lead 0 (the longest) has row tiles
-    const long long need = ((long long)count0 * rpr + SPEC_ROWS - 1) / SPEC_ROWS;
-    long long cap = (long long)spec_cu(h) * SPEC_BLOCKS_PER_CU / (active * groups);
-    if (cap < 1) cap = 1;
-    bpc = (int)(need < cap ? need : cap);
-  }
+  // no more blocks in a cell than lead 0 (the longest) has row tiles
+  const int bpc = cell_plan_bpc(h, active, groups, ((long long)count0 * rpr + SPEC_ROWS - 1) / SPEC_ROWS, SPEC_BLOCKS_PER_CU);
   const size_t ws_need = (size_t)active * groups * bpc * (size_t)(4 * K + 2) * sizeof(double);
+  // inherited: a null workspace is accepted where no partial is written (verify.hip wants one regardless)
   DLWP_CHECK_ARG(ws_bytes >= ws_need && (ws || ws_need == 0), "dlwp_verify_spectrum_sums: workspace too small (%zu < %zu)", ws_bytes,
                  ws_need);
   DLWP_CHECK_ARG(((uintptr_t)ws & 7) == 0, "dlwp_verify_spectrum_sums: workspace must be 8-byte aligned");
   DLWP_CHECK_ARG(h, "dlwp_verify_spectrum_sums: null handle");
   hipStream_t s = (hipStream_t)stream;
   if (active > 0) {
-    SpecArgs p;
-    p.fc = (const float*)fc, p.ob = (const float*)ob, p.weights = (const float*)weights, p.tw = (const float*)twiddles;
-    p.fc_ls = fc_lead_stride, p.fc_ss = fc_sample_stride, p.ob_ls = ob_lead_stride, p.ob_ss = ob_sample_stride;
+    p.weights = (const float*)weights, p.tw = (const float*)twiddles;
     p.run = run;
-    p.fc_shift = fc_shift, p.ob_shift = ob_shift;
     p.count0 = count0, p.count_dec = count_dec;
     p.groups = groups, p.bpc = bpc;
     p.width = width, p.rpr = (int)rpr;
@@ -379,8 +355,7 @@ int dlwp_verify_spectrum_sums(dlwp_handle_t h, const void* fc, long long fc_lead
     const int per = (p.nT + 3) / 4;      // tiles per wave with at most four waves: 1 .. 3
     p.nw = (p.nT + per - 1) / per;       // waves that own tiles: 3 at width 180 (3 tiles) and 360 (6 tiles)
     const size_t lds = spec_lds_bytes(width, p.pitch);
-    const bool vec = mult4(width) && mult4(fc_lead_stride) && mult4(fc_sample_stride) && mult4(ob_lead_stride) &&
-                     mult4(ob_sample_stride) && aligned16(fc) && aligned16(ob);
+    const bool vec = mult4(width) && window_vec(p.fc) && window_vec(p.ob);
     const void* kern = vec ? (const void*)spectrum_partial_kernel<true> : (const void*)spectrum_partial_kernel<false>;
     // the largest image (width 512) is allowed once per instance and device; every width's image fits below it
     static unsigned lds_allowed[2];      // per instance: a bit per device.  Setting the attribute twice is harmless, so no lock

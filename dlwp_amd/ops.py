@@ -1764,21 +1764,34 @@ def verify_extent(strides, leads, count0, count_dec, groups, run):
     return need
 
 
+def _window_operands(who, leads, count0, count_dec, groups, run, operands, table=None, label_strides=(0, 0),
+                     sizes='leads, groups, run'):
+    """The operand block of the windowed wrappers.  operands: (name, tensor, (lead_stride, sample_stride, shift)) each; all of them
+    and `table` on one device, every size >= 1 (`sizes` names them in the refusal) and no stride, shift or count_dec below 0,
+    every element the strides address inside its tensor.  Returns (device index, leads, count0, count_dec, groups, run) as ints."""
+    d = _dev(operands[0][1])
+    if any(_dev(t) != d for _, t, _ in operands[1:]) or (table is not None and _dev(table) != d):
+        raise ValueError('%s: operands on different devices' % who)
+    leads, count0, count_dec, groups, run = int(leads), int(count0), int(count_dec), int(groups), int(run)
+    if (leads < 1 or groups < 1 or run < 1 or count_dec < 0 or min(label_strides) < 0
+            or any(min(st) < 0 for _, _, st in operands)):
+        raise ValueError('%s: %s must be >= 1; strides, shifts and count_dec >= 0' % (who, sizes))
+    for name, t, st in operands:
+        need = verify_extent(st, leads, count0, count_dec, groups, run)
+        if need > t.numel():
+            raise ValueError('%s: operand %s holds %d elements, the strides address %d' % (who, name, t.numel(), need))
+    return d, leads, count0, count_dec, groups, run
+
+
 def verify_error_sums(a, a_strides, b, b_strides, leads, count0, count_dec, groups, run):
     """include/dlwp_hip.h: dlwp_verify_error_sums.  a, b: contiguous float32 device tensors read as flat arrays through
     x_strides = (lead_stride, sample_stride, shift) in elements.  Returns a NEW (leads, groups, 3) float64 device tensor: sum d^2,
     sum |d| and the pairs counted (d = a - b; NaN pairs skipped) per lead and group, enqueued on the current stream."""
     _check_f32(a, b)
-    d = _dev(a)
-    if _dev(b) != d:
-        raise ValueError('verify_error_sums: operands on devices %d and %d' % (d, _dev(b)))
-    leads, count0, count_dec, groups, run = int(leads), int(count0), int(count_dec), int(groups), int(run)
-    if leads < 1 or groups < 1 or run < 1 or count_dec < 0 or min(a_strides) < 0 or min(b_strides) < 0:
-        raise ValueError('verify_error_sums: leads, groups, run must be >= 1; strides, shifts and count_dec >= 0')
-    for name, t, st in (('a', a, a_strides), ('b', b, b_strides)):
-        need = verify_extent(st, leads, count0, count_dec, groups, run)
-        if need > t.numel():
-            raise ValueError('verify_error_sums: operand %s holds %d elements, the strides address %d' % (name, t.numel(), need))
+    if _dev(b) != _dev(a):      # this wrapper names the devices
+        raise ValueError('verify_error_sums: operands on devices %d and %d' % (_dev(a), _dev(b)))
+    d, leads, count0, count_dec, groups, run = _window_operands('verify_error_sums', leads, count0, count_dec, groups, run,
+                                                                (('a', a, a_strides), ('b', b, b_strides)))
     h = _lib.handle(d)
     ws = torch.empty(max(int(_lib.lib.dlwp_verify_error_workspace(h, leads, groups)), 8), dtype=torch.uint8, device=a.device)
     sums = torch.empty((leads, groups, 3), dtype=torch.float64, device=a.device)
@@ -1829,6 +1842,27 @@ def skill_weights(weights):
     return weights
 
 
+def _climo_labels(who, climo, labels, label_strides, leads, count0, count_dec, trow):
+    """The climatology block of verify_skill_sums and verify_skill_map: the table has rows of `trow` floats and at most
+    VERIFY_MAX_LABELS of them, labels need a table, lie in [-1, n_labels) and hold every index label_strides address.  Returns
+    (n_labels, the labels as a flat HOST int32 array or None)."""
+    n_labels = 0
+    if climo is not None:
+        n_labels, have = _rows_of(climo, who)
+        if have != trow:
+            raise ValueError('%s: table rows of %d floats, sample rows of %d' % (who, have, trow))
+        if n_labels > VERIFY_MAX_LABELS:
+            raise ValueError('%s: %d labels, at most %d' % (who, n_labels, VERIFY_MAX_LABELS))
+    elif labels is not None:
+        raise ValueError('%s: labels without a climatology table' % who)
+    if labels is not None:
+        labels = skill_labels(labels, n_labels)
+        need = verify_label_extent(label_strides, leads, count0, count_dec)
+        if need > labels.size:
+            raise ValueError('%s: %d labels, the strides address %d' % (who, labels.size, need))
+    return n_labels, labels
+
+
 def verify_skill_sums(fc, fc_strides, ob, ob_strides, leads, count0, count_dec, groups, run, climo=None, labels=None,
                       label_strides=(0, 0), weights=None, w_inner=1):
     """include/dlwp_hip.h: dlwp_verify_skill_sums.  fc, ob: contiguous float32 device tensors read as flat arrays through
@@ -1839,31 +1873,10 @@ def verify_skill_sums(fc, fc_strides, ob, ob_strides, leads, count0, count_dec, 
     checked here and then uploaded.  Returns a NEW (leads, groups, 10) float64 device tensor: sum w, w d, w d^2, w |d|, w fa, w oa,
     w fa oa, w fa^2, w oa^2 and the pairs counted (d = fc - ob, fa = fc - c, oa = ob - c), enqueued on the current stream."""
     _check_f32(fc, ob, climo)
-    d = _dev(fc)
-    if _dev(ob) != d or (climo is not None and _dev(climo) != d):
-        raise ValueError('verify_skill_sums: operands on different devices')
-    leads, count0, count_dec, groups, run = int(leads), int(count0), int(count_dec), int(groups), int(run)
-    if (leads < 1 or groups < 1 or run < 1 or count_dec < 0 or min(fc_strides) < 0 or min(ob_strides) < 0
-            or min(label_strides) < 0):
-        raise ValueError('verify_skill_sums: leads, groups, run must be >= 1; strides, shifts and count_dec >= 0')
-    for name, t, st in (('fc', fc, fc_strides), ('ob', ob, ob_strides)):
-        need = verify_extent(st, leads, count0, count_dec, groups, run)
-        if need > t.numel():
-            raise ValueError('verify_skill_sums: operand %s holds %d elements, the strides address %d' % (name, t.numel(), need))
-    n_labels = 0
-    if climo is not None:
-        n_labels, trow = _rows_of(climo, 'verify_skill_sums')
-        if trow != groups * run:
-            raise ValueError('verify_skill_sums: table rows of %d floats, sample rows of %d' % (trow, groups * run))
-        if n_labels > VERIFY_MAX_LABELS:
-            raise ValueError('verify_skill_sums: %d labels, at most %d' % (n_labels, VERIFY_MAX_LABELS))
-    elif labels is not None:
-        raise ValueError('verify_skill_sums: labels without a climatology table')
-    if labels is not None:
-        labels = skill_labels(labels, n_labels)
-        need = verify_label_extent(label_strides, leads, count0, count_dec)
-        if need > labels.size:
-            raise ValueError('verify_skill_sums: %d labels, the strides address %d' % (labels.size, need))
+    d, leads, count0, count_dec, groups, run = _window_operands(
+        'verify_skill_sums', leads, count0, count_dec, groups, run, (('fc', fc, fc_strides), ('ob', ob, ob_strides)),
+        table=climo, label_strides=label_strides)
+    n_labels, labels = _climo_labels('verify_skill_sums', climo, labels, label_strides, leads, count0, count_dec, groups * run)
     w_len, w_inner = 0, int(w_inner)
     if weights is not None:
         weights = skill_weights(weights)
@@ -1894,34 +1907,15 @@ def verify_skill_map(fc, fc_strides, ob, ob_strides, leads, count0, count_dec, r
     NEW device tensors (leads, 9, row) float64, (leads, 6, row) float32 and (leads, row) int32, enqueued on the current stream; sums
     is None without want_sums, scores and counts are None without want_scores."""
     _check_f32(fc, ob, climo)
-    d = _dev(fc)
-    if _dev(ob) != d or (climo is not None and _dev(climo) != d):
-        raise ValueError('verify_skill_map: operands on different devices')
-    leads, count0, count_dec, row, split = int(leads), int(count0), int(count_dec), int(row), int(split)
-    if leads < 1 or row < 1 or count_dec < 0 or min(fc_strides) < 0 or min(ob_strides) < 0 or min(label_strides) < 0:
-        raise ValueError('verify_skill_map: leads and row must be >= 1; strides, shifts and count_dec >= 0')
+    split = int(split)
     if split < 0:
         raise ValueError('verify_skill_map: split must be >= 0, got %d' % split)
     if not (want_sums or want_scores):
         raise ValueError('verify_skill_map: neither sums nor scores wanted')
-    for name, t, st in (('fc', fc, fc_strides), ('ob', ob, ob_strides)):
-        need = verify_extent(st, leads, count0, count_dec, 1, row)
-        if need > t.numel():
-            raise ValueError('verify_skill_map: operand %s holds %d elements, the strides address %d' % (name, t.numel(), need))
-    n_labels = 0
-    if climo is not None:
-        n_labels, trow = _rows_of(climo, 'verify_skill_map')
-        if trow != row:
-            raise ValueError('verify_skill_map: table rows of %d floats, sample rows of %d' % (trow, row))
-        if n_labels > VERIFY_MAX_LABELS:
-            raise ValueError('verify_skill_map: %d labels, at most %d' % (n_labels, VERIFY_MAX_LABELS))
-    elif labels is not None:
-        raise ValueError('verify_skill_map: labels without a climatology table')
-    if labels is not None:
-        labels = skill_labels(labels, n_labels)
-        need = verify_label_extent(label_strides, leads, count0, count_dec)
-        if need > labels.size:
-            raise ValueError('verify_skill_map: %d labels, the strides address %d' % (labels.size, need))
+    d, leads, count0, count_dec, _, row = _window_operands(
+        'verify_skill_map', leads, count0, count_dec, 1, row, (('fc', fc, fc_strides), ('ob', ob, ob_strides)),
+        table=climo, label_strides=label_strides, sizes='leads and row')
+    n_labels, labels = _climo_labels('verify_skill_map', climo, labels, label_strides, leads, count0, count_dec, row)
     h = _lib.handle(d)
     labels_d = None if labels is None else torch.from_numpy(labels).to(fc.device)
     ws = torch.empty(max(int(_lib.lib.dlwp_verify_skill_map_workspace(h, leads, count0, row, split)), 8), dtype=torch.uint8,
@@ -1985,12 +1979,7 @@ def verify_spectrum_sums(fc, fc_strides, ob, ob_strides, leads, count0, count_de
     exists) before anything is uploaded or launched.  Returns NEW device tensors (sums (leads, groups, 4, width // 2 + 1), norm
     (leads, groups, 2)), float64, enqueued on the current stream."""
     _check_f32(fc, ob)
-    d = _dev(fc)
-    if _dev(ob) != d:
-        raise ValueError('verify_spectrum_sums: operands on different devices')
-    leads, count0, count_dec, groups, run, width = int(leads), int(count0), int(count_dec), int(groups), int(run), int(width)
-    if leads < 1 or groups < 1 or run < 1 or count_dec < 0 or min(fc_strides) < 0 or min(ob_strides) < 0:
-        raise ValueError('verify_spectrum_sums: leads, groups, run must be >= 1; strides, shifts and count_dec >= 0')
+    leads, count0, groups, run, width = int(leads), int(count0), int(groups), int(run), int(width)
     if width < SPECTRUM_MIN_WIDTH or width > SPECTRUM_MAX_WIDTH:
         raise ValueError('verify_spectrum_sums: rows of %d longitudes, the device kernel takes %d .. %d'
                          % (width, SPECTRUM_MIN_WIDTH, SPECTRUM_MAX_WIDTH))
@@ -1999,10 +1988,8 @@ def verify_spectrum_sums(fc, fc_strides, ob, ob_strides, leads, count0, count_de
     if max(count0, 0) * (run // width) >= 2 ** 31 - 32 or leads * groups > 2 ** 20:
         raise ValueError('verify_spectrum_sums: %d longitude rows in a cell, %d cells: at most 2^31 and 2^20'
                          % (max(count0, 0) * (run // width), leads * groups))
-    for name, t, st in (('fc', fc, fc_strides), ('ob', ob, ob_strides)):
-        need = verify_extent(st, leads, count0, count_dec, groups, run)
-        if need > t.numel():
-            raise ValueError('verify_spectrum_sums: operand %s holds %d elements, the strides address %d' % (name, t.numel(), need))
+    d, leads, count0, count_dec, groups, run = _window_operands('verify_spectrum_sums', leads, count0, count_dec, groups, run,
+                                                                (('fc', fc, fc_strides), ('ob', ob, ob_strides)))
     w_len = 0
     if weights is not None:
         weights = skill_weights(weights)
